@@ -2,7 +2,7 @@
 """Benchmark of the video->characters hot path on MI355X.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--regime pixels|landmarks|landmarks_attn|all]
-                  [--model gru256|lstm768|lstm700|lstm512|gru800] [--batch B]
+                  [--model gru256|lstm768|lstm700|lstm512|gru800] [--batch B] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic input already resident in HBM:
 (frontend ->) VideoEncoder forward -> CTC 'mean' loss -> backward -> clip_grad_norm_(50) ->
@@ -545,8 +545,32 @@ def probe_main(args):
                       "master": "%s:%s" % (os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"])}), flush=True)
 
 
-def run_regime(args, regime, world, rank, dev, recurrence=None):
-  """Builds the model, times `args.steps` steps, measures the dominant kernels.  Returns a dict."""
+DUMP_MAX_ELEMS = 1 << 20     # per array: 4 MB of float32, so that every regime of --regime all stays under 64 MB
+
+
+def dump_sample(t):
+  """A device tensor -> a flat host array for --dump-outputs: float64 for scalars and integer words, float32
+  otherwise; past DUMP_MAX_ELEMS elements a fixed seeded sample (the same indices for every array of that size)."""
+  import numpy as np
+  a = t.detach().reshape(-1)
+  a = (a.double() if a.numel() == 1 or not a.is_floating_point() else a.float()).cpu().numpy()
+  if a.size > DUMP_MAX_ELEMS:
+    a = a[np.sort(np.random.RandomState(a.size % (1 << 31)).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+  return np.ascontiguousarray(a)
+
+
+def write_outputs(directory, results):
+  """--dump-outputs: DIR/<regime>_<output>.npy for every run that carries "outputs"."""
+  import numpy as np
+  os.makedirs(directory, exist_ok=True)
+  for tag, r in results:
+    for name, a in sorted((r.get("outputs") or {}).items()):
+      np.save(os.path.join(directory, "%s_%s.npy" % (tag, name)), a)
+
+
+def run_regime(args, regime, world, rank, dev, recurrence=None, dump=False):
+  """Builds the model, times `args.steps` steps, measures the dominant kernels.  Returns a dict; with `dump`, its
+  "outputs" hold what the last timed step returned (dump_sample)."""
   import torch
   import torch.distributed as dist
   from lipreading_amd import _C
@@ -650,11 +674,13 @@ def run_regime(args, regime, world, rank, dev, recurrence=None):
   from lipreading_amd import train as T
   graphs = T.StepGraphs(enabled=use_graph)
   flags = (True,) * (LABEL_LEN + 1)     # teacher_forcing_ratio 1: every step of the decoder loop is teacher forced
+  last_dloss = [None]                   # the decoder loss of the latest step (--dump-outputs)
 
   def step(graphs=graphs, sync=None, dec_sync=None):
     if attn:
       dloss, loss, status = T.decoder_step(enc, dec, (opt, dec_opt), frames, frame_lens, chars, char_lens, flags, 1, 0,
                                            grad_norm=50, max_len=T_FRAMES, grad_sync=(sync, dec_sync), graphs=graphs)
+      last_dloss[0] = dloss
       if loss is None:   # enable_ctc False: the decoder loss is the step's loss, nothing can be skipped
         return dloss, _zero_status
       return loss, status
@@ -723,6 +749,15 @@ def run_regime(args, regime, world, rank, dev, recurrence=None):
       loss, status = step(**step_sync)
     fence()
     elapsed_all.append(time.perf_counter() - t0)
+  # what the last timed step handed its caller — the losses, the status word and the updated weights — copied before
+  # the eager steps below move the weights on
+  outputs = None
+  if dump:
+    outputs = {"loss": loss, "status": status, "params": flat.data[flat.first:]}
+    if attn:
+      outputs["decoder_loss"] = last_dloss[0]
+      outputs["decoder_params"] = dec_flat.data[dec_flat.first:]
+    outputs = {k: dump_sample(v) for k, v in outputs.items()}
 
   # roofline leg (after the timed region, same process, same tensors).  Per-kernel durations are taken with the conv
   # backward on ONE stream: in the timed step a layer's weight gradient runs on a side stream beside its data
@@ -780,7 +815,7 @@ def run_regime(args, regime, world, rank, dev, recurrence=None):
   res = {"regime": regime, "elapsed": elapsed, "loss": float(loss.item()), "skipped": int(status.item()),
          "layers": layers, "use_graph": use_graph, "graph_note": graph_note,
          "rccl_ranks": dist.get_world_size() if DIST_ON else 1, "all_reduce_buckets": bucket_us,
-         "launch_choice": launch_choice}
+         "launch_choice": launch_choice, "outputs": outputs}
   if sync is not None:
     sync.close()
   if dec_sync is not None:
@@ -1058,7 +1093,12 @@ def main():
   ap.add_argument("--no-cpu-baseline", action="store_true")
   ap.add_argument("--cpu-budget", type=float, default=12.0,
                   help="seconds of timed CPU-oracle steps per regime (never fewer than 10 steps)")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="after the timed steps, write what each regime's last timed step returned (losses, status word, "
+                       "updated weights; a fixed seeded sample of large arrays) to DIR/<regime>_<name>.npy")
   args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error("--steps must be at least 1 and --warmup at least 0")
 
   if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
     # started as plain `python bench.py --gpus N`: become the launcher of N ranks (one per GPU)
@@ -1085,11 +1125,15 @@ def main():
 
   order = {"both": ["pixels", "landmarks"],
            "all": ["pixels", "landmarks", "landmarks_attn", "pixels_tfm"]}.get(args.regime, [args.regime])
-  results = [run_regime(args, r, world, rank, dev) for r in order]
+  dump = args.dump_outputs is not None and rank == 0
+  results = [run_regime(args, r, world, rank, dev, dump=dump) for r in order]
   # the reference-faithful regime once more on the OTHER recurrence: the per-step fp32 launches (every shape's fallback)
   options = {}
   if "landmarks" in order and args.regime in ("all", "landmarks"):
-    options["f32"] = run_regime(args, "landmarks", world, rank, dev, recurrence="f32")
+    options["f32"] = run_regime(args, "landmarks", world, rank, dev, recurrence="f32", dump=dump)
+  if dump:
+    write_outputs(args.dump_outputs, [(r["regime"], r) for r in results] +
+                  [("landmarks_" + name, o) for name, o in options.items()])
   if rank == 0:
     head = results[0]
     out = {

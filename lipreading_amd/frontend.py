@@ -68,7 +68,9 @@ _conv_side = None
 def _conv_side_stream(device):
   global _conv_side
   if _conv_side is None or _conv_side.device != device:
-    _conv_side = torch.cuda.Stream(device=device)
+    # high priority: a hardware queue apart from the default stream's whatever else the process has opened
+    # (encoder._get_side_stream)
+    _conv_side = torch.cuda.Stream(device=device, priority=-1)
   return _conv_side
 
 

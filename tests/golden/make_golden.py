@@ -28,7 +28,16 @@ Pins (see oracle/torch_oracle.py header):
   prn_cases.npz     reference PRN.process + get_landmarks (prnet.py:112-170) composed as
                     generate_dataview.py:58-64, network output replaced by a seeded position map;
                     skimage's estimate_transform stood in by oracle.umeyama_similarity  SHIMMED
+  ref_flag_files.json  the reference's trainer flag files (config/, every non-empty file outside
+                    config/gen_dataview), as data: {path relative to config/: text}        DATA
+  ref_loader_cases.npz  reference FrameCaptionDataset (cache branch, data_loader.py:175-176) reading
+                    the pickles lipreading_amd.dataset writes for the synthetic 'nano' dataview
+                    (5 videos x 6 captions, seed 123456; split RandomState(1)): its char2idx, every
+                    caption, and every frames array as shape, dtype, first frame and SHA-256   CLEAN
+
+  python tests/golden/make_golden.py ref_flag_files ref_loader_cases   # only the files named
 """
+import hashlib
 import os
 import sys
 import types
@@ -445,7 +454,60 @@ def gen_prn(face, prnet):
   np.savez_compressed(os.path.join(OUT, "prn_cases.npz"), **cases)
 
 
+def gen_ref_flag_files():
+  import json
+  cfg = os.path.join(REF, "config")
+  files = {}
+  for root, _, names in os.walk(cfg):
+    if "gen_dataview" in root:
+      continue
+    for n in names:
+      path = os.path.join(root, n)
+      if os.path.getsize(path) > 0:
+        with open(path) as f:
+          files[os.path.relpath(path, cfg)] = f.read()
+  with open(os.path.join(OUT, "ref_flag_files.json"), "w") as f:
+    json.dump(files, f, indent=1, sort_keys=True)
+    f.write("\n")
+
+
+def gen_ref_loader_cases():
+  import tempfile
+  sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+  from lipreading_amd import dataset as DS
+  with tempfile.TemporaryDirectory() as root:
+    DS.write_synthetic_dataview(root, "synthetic/nano", n_videos=5, captions_per_video=6)
+    tr, _, _ = DS.split_dataset(root, "synthetic/nano", 0.8, np.random.RandomState(1))
+    DS.FrameCaptionDataset(root, "synthetic/nano", "train", tr)        # writes the pickle cache the reference reads
+    os.environ["LIP_READING_WS_PATH"] = root
+    sys.path.insert(0, REF)
+    sys.modules.setdefault("spacy", types.ModuleType("spacy"))          # inert: only sentence splitting uses it
+    import src.utils.utility as ref_util
+    ref_util._ws_dir = None
+    import src.data.data_loader as ref_dl
+    theirs = ref_dl.FrameCaptionDataset("synthetic/nano", "train", tr)
+    keys = sorted(theirs.char2idx, key=theirs.char2idx.get)
+    cases = {"char2idx/keys": np.array(keys), "char2idx/ids": np.array([theirs.char2idx[k] for k in keys]),
+             "n": np.array(len(theirs))}
+    # the landmark frames are float64 random walks (incompressible, ~2 MB): each is stored as its shape, dtype, first
+    # frame and the SHA-256 of its bytes, which pins every value exactly; the captions are stored as they are
+    for i in range(len(theirs)):
+      f_r, c_r = theirs[i]
+      f_r = np.ascontiguousarray(f_r)
+      cases["frames_shape/%d" % i] = np.array(f_r.shape)
+      cases["frames_dtype/%d" % i] = np.array(f_r.dtype.str)
+      cases["frames_first/%d" % i] = f_r[0]
+      cases["frames_sha256/%d" % i] = np.array(hashlib.sha256(f_r.tobytes()).hexdigest())
+      cases["chars/%d" % i] = np.asarray(c_r)
+  np.savez_compressed(os.path.join(OUT, "ref_loader_cases.npz"), **cases)
+
+
 def main():
+  only = sys.argv[1:]
+  if only:
+    for name in only:
+      {"ref_flag_files": gen_ref_flag_files, "ref_loader_cases": gen_ref_loader_cases}[name]()
+    return
   sys.path.insert(0, REF)
   os.environ.setdefault("LIP_READING_WS_PATH", REF)
   install_stubs()
@@ -470,6 +532,8 @@ def main():
   import src.utils.data.face as ref_face                      # clean apart from the inert stubs
   gen_lmk(ref_face)
   gen_prn(ref_face, ref_prnet)
+  gen_ref_flag_files()
+  gen_ref_loader_cases()
   for f in sorted(os.listdir(OUT)):
     if f.endswith(".npz"):
       print("%-20s %8d bytes" % (f, os.path.getsize(os.path.join(OUT, f))))

@@ -207,23 +207,29 @@ def test_six_hardware_queues_are_set_for_ranks_only():
   assert queues(WORLD_SIZE="8", GPU_MAX_HW_QUEUES="4") == "4"
 
 
-REF_CONFIG = "/root/reference/config"
+REF_FLAG_FILES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_flag_files.json")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CONFIG), reason="build container only: the reference tree is not on the GPU box")
-def test_every_reference_flag_file_parses_to_the_model_it_describes():
+def test_every_reference_flag_file_parses_to_the_model_it_describes(tmp_path):
   """Every non-empty flag file the reference ships for its trainers — config/defaults.txt, config/train/**,
   config/archive/experiments/** — goes through driver.parse_flags unchanged (the reference reads them through
   src/utils/cmd_line.py:91-141 into src/scripts/train.py:134-167's keyword arguments), and the model the flags imply
   is the one this test reads out of the file with its own three-line tokenizer: encoder cell / width / directions,
   CTC head or not, batch, attention, and the decoder width CharDecodingStep derives (better_model.py:134-148:
-  hidden = directions x encoder hidden).  config/gen_dataview/* drive the ETL, which is out of scope."""
+  hidden = directions x encoder hidden).  config/gen_dataview/* drive the ETL, which is out of scope.
+  The files are stored as data in tests/golden/ref_flag_files.json (make_golden.py) and written back out as files."""
+  import json
   from lipreading_amd import driver
+  REF_CONFIG = str(tmp_path / "config")
+  with open(REF_FLAG_FILES) as fh:
+    stored = json.load(fh)
   files = []
-  for root, _, names in os.walk(REF_CONFIG):
-    if "gen_dataview" in root:
-      continue
-    files += [os.path.join(root, n) for n in names]
+  for rel, text in stored.items():
+    path = os.path.join(REF_CONFIG, rel)
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as fh:
+      fh.write(text)
+    files.append(path)
   files = sorted(f for f in files if os.path.getsize(f) > 0)
   assert len(files) >= 61                       # 52 archived experiments + defaults + 6 attention files + micro + nano
   truthy = lambda v: v.lower() not in ("false", "0", "no")
