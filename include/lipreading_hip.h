@@ -682,6 +682,27 @@ int lr_ctc_greedy_decode(const float* probs, int64_t stride_b, int64_t stride_t,
                          int32_t* out_offsets, int32_t* out_lens, int B, int T, int C, int blank,
                          lr_stream_t stream);
 
+/* ---- A6b: CTC prefix beam search — src/models/lipreader/decoder.py:90-143 (BeamCTCDecoder) ------- */
+/* The reference delegates to ctcdecode's CTCBeamDecoder(lm_path=None) on the CPU; the specification
+ * here is this build's (lipreading_amd/csrc/lr_ctc_beam.hip).  No language model.
+ *   probs     element (b,t,c) at probs[b*stride_b + t*stride_t + c], fp32; log_input = 1 when the values
+ *             are log-probabilities.  sizes [B] int32 or NULL (= T); frames t >= sizes[b] are never read.
+ *   cutoff_top_n, cutoff_prob, beam_width, blank: ctcdecode's parameters of the same names.
+ *   out_ids / out_offsets [B][W][T] int32 (-1 padded), out_lens [B][W] int32 (0 = empty slot),
+ *   out_scores [B][W] fp32 = -log P(prefix), ascending (+inf in empty slots).
+ * Limits: beam_width <= 128, cutoff_top_n <= 64, C <= 256, 1 + T*beam_width < 2^31 (else LR_ERR_UNSUPPORTED). */
+
+/* Workspace lr_ctc_beam_decode needs (0 for arguments it rejects) — replaces the CPU buffers of
+ * ctcdecode's CTCBeamDecoder.decode (decoder.py:139-140). */
+size_t lr_ctc_beam_workspace_bytes(int B, int T, int C, int beam_width, int cutoff_top_n);
+
+/* CTCBeamDecoder.decode (decoder.py:139-140): per-frame pruning across the chip, then one workgroup per
+ * utterance for the frame loop. */
+int lr_ctc_beam_decode(const float* probs, int64_t stride_b, int64_t stride_t, const int32_t* sizes,
+                       int log_input, int cutoff_top_n, float cutoff_prob, int beam_width, int blank,
+                       int32_t* out_ids, int32_t* out_offsets, int32_t* out_lens, float* out_scores,
+                       void* workspace, size_t workspace_bytes, int B, int T, int C, lr_stream_t stream);
+
 /* ---- A8 (BUILD-DEFINED, no reference symbol): 3-D conv frontend on bf16 MFMA -------------- */
 /* The reference has no conv frontend (src/models/lipreader/model.py:122,153-156 are comments, the
  * `ced` configs are empty); BASELINE.json's north_star asks for one ("im2col + MFMA GEMM for the 3D

@@ -1,0 +1,472 @@
+// lr_ctc_beam.hip — CTC prefix beam search without a language model for gfx950.
+//
+// Replaces src/models/lipreader/decoder.py:90-143 (BeamCTCDecoder), which hands the search to the external
+// `ctcdecode` C++ library (CTCBeamDecoder with lm_path=None) after a probs.cpu() copy.  ctcdecode is not part of this
+// build, so the specification is this build's own:
+//
+//   Input    probs element (b,t,c) at probs[b*stride_b + t*stride_t + c], fp32.  log_input = 0: the values are
+//            probabilities (the reference's contract); 1: log-probabilities (what VideoEncoder returns).
+//            sizes[B] int32 or NULL (= T), clamped to [0, T].  Frames t >= sizes[b] are never read.
+//   Pruning  per frame (ctcdecode's cutoff_top_n / cutoff_prob): sort the classes by probability, descending, ties to
+//            the lower index (as torch.max and lr_ctc_greedy_decode); keep the first cutoff_top_n; if cutoff_prob < 1,
+//            keep only the shortest prefix of that list whose cumulative probability (float64) is >= cutoff_prob,
+//            with at least one class.
+//   State    per hypothesis (log p_blank, log p_nonblank); score = logaddexp of the two.  The empty prefix starts
+//            with (0, -inf).  At frame t, for each hypothesis p with last character l and each kept class c:
+//              c == blank  p.p_blank'    += score(p) * p(c)
+//              c == l      p.p_nonblank' += p_nonblank(p) * p(c)    and   (p+c).p_nonblank' += p_blank(p) * p(c)
+//              otherwise   (p+c).p_nonblank' += score(p) * p(c)
+//            An extension p+c that equals a hypothesis already in the beam merges into it.  A candidate of
+//            probability zero (score -inf) is not a hypothesis and is never kept.
+//   Select   the beam_width best candidates by score; ties go to the lower (parent rank, class), the parent's own
+//            continuation ranking before its extensions.  ctcdecode's `min_cutoff` early-out (skip classes whose
+//            log p(c) falls below the worst kept score) is NOT applied: a stated deviation from ctcdecode.
+//   Offsets  a hypothesis that already existed keeps its offsets; one first created at frame t takes its parent's
+//            offsets plus t.  With beam_width = 1 and cutoff_top_n = 1 the ids and offsets are exactly
+//            lr_ctc_greedy_decode's.
+//   Output   out_ids[B][W][T], out_offsets[B][W][T] int32, padded with -1; out_lens[B][W] (0 for beam slots that
+//            hold no hypothesis); out_scores[B][W] = -log P(prefix) fp32, ascending (+inf in empty slots).  This is
+//            ctcdecode's score convention as the reference reads it; no ctcdecode is available to compare against,
+//            so the convention is checked only against exhaustive enumeration (tests/test_gpu_beam.py).
+//
+// Limits: beam_width <= 128, cutoff_top_n <= 64 (values above C act as C), C <= 256, 1 + T*beam_width < 2^31;
+// anything else is LR_ERR_UNSUPPORTED.
+//
+// Layout: two launches.
+//   1. beam_prune_kernel — one wave per (b,t) frame across the whole chip: cutoff_top_n rounds of a 64-lane argmax
+//      over (value, index) keys pick the kept classes in order, a float64 wave scan applies cutoff_prob, and the
+//      compact (class, log p) list goes to the workspace.  The sequential loop never touches the C axis.
+//   2. beam_loop_kernel — one workgroup per utterance, one pass per frame.  Hypotheses are trie node ids; the node
+//      table (parent, class, frame) lives in the workspace, at most beam_width new nodes per frame (node 1+t*W+r is
+//      the one created at frame t for rank r).  The beam's (node, parent node, class, depth, masses) stay in LDS, so
+//      the table is only written during the loop and read at the end.  An extension p+c equals beam entry q iff
+//      prefix(parent(q)) == prefix(p) && class(q) == c.  Node ids alone do not decide that: a prefix that leaves the
+//      beam and comes back is a new node while its children that stayed keep the old one as parent.  So every beam
+//      entry carries a 64-bit hash of its prefix, each q looks its parent's prefix hash up in an LDS table of the
+//      beam's hashes, and a hit is confirmed exactly — same parent node, or both node chains walked back to a common
+//      node with equal classes on the way (the rare case).  q then takes over that extension's mass.  The top-W of the W*(n+1) candidates is a radix select on 48-bit
+//      (score, tie-break) keys — 8-bit digits, LDS histograms, stopping at the first digit that closes the count —
+//      followed by a rank count among the W survivors.  At the end each beam walks its node chain backwards.
+#include "lr_common.h"
+
+namespace {
+
+constexpr int kBeamMaxW = 128;
+constexpr int kBeamMaxN = 64;
+constexpr int kBeamMaxC = 256;
+constexpr int kMaxCand = kBeamMaxW * (kBeamMaxN + 1);
+constexpr int kHash = 512;            // >= 4 * kBeamMaxW: open addressing at load <= 1/4
+constexpr int kLoopThreads = 512;
+constexpr int kPruneWaves = 4;
+
+__device__ __forceinline__ uint32_t ord_f32(float v) {
+  const uint32_t u = __float_as_uint(v);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float unord_f32(uint32_t o) {
+  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+
+struct BeamWs {
+  int32_t* kcls;   // [B][T][n] kept classes, most probable first
+  float* klp;      // [B][T][n] their log-probabilities
+  int32_t* kcnt;   // [B][T]    how many were kept
+  int32_t* npar;   // [B][NN]   trie: parent node
+  int32_t* ncls;   // [B][NN]   trie: class
+  int32_t* nfrm;   // [B][NN]   trie: frame the node was created at
+};
+
+__host__ __device__ inline int64_t beam_nodes(int T, int W) { return 1 + (int64_t)T * W; }
+
+inline size_t beam_ws_bytes(int B, int T, int n, int W) {
+  const size_t frames = (size_t)B * T;
+  size_t s = lr_align_up(frames * n * 4, 256) * 2 + lr_align_up(frames * 4, 256);
+  s += 3 * lr_align_up((size_t)B * beam_nodes(T, W) * 4, 256);
+  return s;
+}
+
+inline BeamWs beam_ws_carve(void* ws, int B, int T, int n, int W) {
+  char* p = static_cast<char*>(ws);
+  const size_t frames = (size_t)B * T;
+  BeamWs w;
+  w.kcls = reinterpret_cast<int32_t*>(p); p += lr_align_up(frames * n * 4, 256);
+  w.klp = reinterpret_cast<float*>(p);    p += lr_align_up(frames * n * 4, 256);
+  w.kcnt = reinterpret_cast<int32_t*>(p); p += lr_align_up(frames * 4, 256);
+  const size_t nodes = lr_align_up((size_t)B * beam_nodes(T, W) * 4, 256);
+  w.npar = reinterpret_cast<int32_t*>(p); p += nodes;
+  w.ncls = reinterpret_cast<int32_t*>(p); p += nodes;
+  w.nfrm = reinterpret_cast<int32_t*>(p);
+  return w;
+}
+
+// ---------------------------------------------------------------------------------------
+// 1. per-frame top-n + cutoff: one wave per frame, lanes along the class axis (C <= 256: 4 per lane)
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kPruneWaves * LR_WAVE) void beam_prune_kernel(
+    const float* __restrict__ probs, int64_t stride_b, int64_t stride_t, const int32_t* __restrict__ sizes,
+    int log_input, float cutoff_prob, int32_t* __restrict__ kcls, float* __restrict__ klp,
+    int32_t* __restrict__ kcnt, int B, int T, int C, int n) {
+  const int lane = threadIdx.x & (LR_WAVE - 1);
+  const int64_t f = (int64_t)blockIdx.x * kPruneWaves + (threadIdx.x >> 6);
+  if (f >= (int64_t)B * T) return;
+  const int b = (int)(f / T), t = (int)(f - (int64_t)b * T);
+  int len = sizes ? sizes[b] : T;
+  len = len < 0 ? 0 : (len > T ? T : len);
+  if (t >= len) return;
+  const float* pr = probs + (int64_t)b * stride_b + (int64_t)t * stride_t;
+  // key = (order-preserving value bits, ~class): the largest key is the most probable class, lowest index on ties.
+  // 0 marks "absent or taken"; a real key is never 0 (its low word ~c is > 0 for c < 2^32-1).
+  uint64_t key[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int c = lane + r * LR_WAVE;
+    key[r] = c < C ? ((uint64_t)ord_f32(pr[c]) << 32) | (uint64_t)(0xffffffffu - (uint32_t)c) : 0ull;
+  }
+  const int nn = n < C ? n : C;
+  uint64_t mine = 0;   // lane k ends up with the k-th kept key
+  for (int k = 0; k < nn; ++k) {
+    uint64_t w = key[0] > key[1] ? key[0] : key[1];
+    const uint64_t w2 = key[2] > key[3] ? key[2] : key[3];
+    w = w > w2 ? w : w2;
+#pragma unroll
+    for (int off = LR_WAVE / 2; off > 0; off >>= 1) {
+      const uint64_t o = __shfl_xor(w, off);
+      w = o > w ? o : w;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (key[r] == w) key[r] = 0ull;
+    if (lane == k) mine = w;
+  }
+  const bool have = lane < nn;
+  const int c = (int)(0xffffffffu - (uint32_t)mine);
+  const float v = unord_f32((uint32_t)(mine >> 32));
+  int cnt = nn;
+  if (cutoff_prob < 1.f) {
+    double cum = have ? (log_input ? exp((double)v) : (double)v) : 0.0;
+#pragma unroll
+    for (int off = 1; off < LR_WAVE; off <<= 1) {
+      const double o = __shfl_up(cum, off);
+      if (lane >= off) cum += o;
+    }
+    const uint64_t hit = __ballot(have && cum >= (double)cutoff_prob);
+    if (hit) cnt = __ffsll((unsigned long long)hit);   // first hit's lane + 1
+  }
+  if (lane < cnt) {
+    kcls[f * n + lane] = c;
+    klp[f * n + lane] = log_input ? v : logf(v);
+  }
+  if (lane == 0) kcnt[f] = cnt;
+}
+
+// ---------------------------------------------------------------------------------------
+// 2. the frame loop: one workgroup per utterance
+// ---------------------------------------------------------------------------------------
+struct BeamSmem {
+  float score[kMaxCand];          // candidate s = i*(n+1) + j: j = 0 parent i's own continuation, j = 1+k extension by
+                                  // kept class k; -inf = not a hypothesis
+  int hist[2][256];               // radix-select histograms (alternating, so clearing one never races the other)
+  int hslot[kHash];               // prefix hash -> beam slot (open addressing; the key is hpre[cur][slot])
+  uint64_t hpre[2][kBeamMaxW], hpar[2][kBeamMaxW];   // hash of the prefix and of its parent prefix
+  int node[2][kBeamMaxW], par[2][kBeamMaxW], cls[2][kBeamMaxW], depth[2][kBeamMaxW];
+  float pb[2][kBeamMaxW], pnb[2][kBeamMaxW];
+  float spb[kBeamMaxW], spnb[kBeamMaxW];   // this frame's own-continuation masses
+  int kc[kBeamMaxN];
+  float kl[kBeamMaxN];
+  int c2k[kBeamMaxC];             // class -> kept rank this frame, -1 if pruned
+  uint64_t selkey[kBeamMaxW];
+  int selslot[kBeamMaxW];
+  int ctl[8];                     // [0] digit [1] need [2] count in digit [3] total [4] selected
+};
+
+// prefix hash of p+c from that of p (splitmix64's finaliser over the parent hash and the class)
+__device__ __forceinline__ uint64_t prefix_hash(uint64_t h, int c) {
+  uint64_t x = h ^ ((uint64_t)(c + 1) * 0x9e3779b97f4a7c15ull);
+  x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
+  x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
+  return x ^ (x >> 31);
+}
+__device__ __forceinline__ uint32_t hash_slot(uint64_t key) { return (uint32_t)(key >> (64 - 9)); }   // kHash = 2^9
+
+// node-table reads that bypass the CU's L1: the entries were written by other threads of this workgroup in earlier
+// frames (ordered by the frame's barriers)
+__device__ __forceinline__ int node_ld(const int32_t* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// nodes a and b of equal depth spell the same prefix
+__device__ bool same_prefix(int a, int b, const int32_t* gpar, const int32_t* gcls) {
+  while (a != b) {
+    if (node_ld(gcls + a) != node_ld(gcls + b)) return false;
+    a = node_ld(gpar + a);
+    b = node_ld(gpar + b);
+  }
+  return true;
+}
+
+// 48-bit selection key: score bits above the tie-break (parent rank, then own continuation before extensions in
+// class order); larger is better.  tb <= 127*257 + 256 < 2^16.
+__device__ __forceinline__ uint64_t cand_key(float sc, int s, int n1, const int* kc) {
+  const int i = s / n1, j = s - i * n1;
+  const int tb = i * (kBeamMaxC + 1) + (j == 0 ? 0 : 1 + kc[j - 1]);
+  return ((uint64_t)ord_f32(sc) << 16) | (uint64_t)(0xffffu - (uint32_t)tb);
+}
+
+__global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
+    const int32_t* __restrict__ kcls, const float* __restrict__ klp, const int32_t* __restrict__ kcnt,
+    const int32_t* __restrict__ sizes, int32_t* __restrict__ npar, int32_t* __restrict__ ncls,
+    int32_t* __restrict__ nfrm, int32_t* __restrict__ out_ids, int32_t* __restrict__ out_off,
+    int32_t* __restrict__ out_lens, float* __restrict__ out_scores, int T, int W, int n, int blank) {
+  __shared__ BeamSmem sm;
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int nt = blockDim.x;
+  const int n1 = n + 1;
+  int len = sizes ? sizes[b] : T;
+  len = len < 0 ? 0 : (len > T ? T : len);
+  const int64_t nbase = (int64_t)b * beam_nodes(T, W);
+  int32_t* gpar = npar + nbase;
+  int32_t* gcls = ncls + nbase;
+  int32_t* gfrm = nfrm + nbase;
+
+  for (int c = tid; c < kBeamMaxC; c += nt) sm.c2k[c] = -1;
+  if (tid == 0) {
+    sm.node[0][0] = 0; sm.par[0][0] = -1; sm.cls[0][0] = -1; sm.depth[0][0] = 0;
+    sm.pb[0][0] = 0.f; sm.pnb[0][0] = LR_NEG_INF;
+    sm.hpre[0][0] = 0; sm.hpar[0][0] = 0;
+  }
+  int cur = 0, nb = 1;
+  // the kept list of the next frame is loaded one frame ahead
+  int pf_cnt = 0, pf_c = 0;
+  float pf_l = 0.f;
+  if (len > 0) {
+    const int64_t f = (int64_t)b * T;
+    pf_cnt = kcnt[f];
+    if (tid < pf_cnt) { pf_c = kcls[f * n + tid]; pf_l = klp[f * n + tid]; }
+  }
+  __syncthreads();
+
+  for (int t = 0; t < len; ++t) {
+    const int cnt = pf_cnt;
+    // -- phase 1: this frame's kept classes, fresh hash and histograms
+    for (int h = tid; h < kHash; h += nt) sm.hslot[h] = -1;
+    if (tid < cnt) { sm.kc[tid] = pf_c; sm.kl[tid] = pf_l; sm.c2k[pf_c] = tid; }
+    if (tid < 256) { sm.hist[0][tid] = 0; sm.hist[1][tid] = 0; }
+    if (tid == 0) sm.ctl[4] = 0;
+    if (t + 1 < len) {
+      const int64_t f = (int64_t)b * T + t + 1;
+      pf_cnt = kcnt[f];
+      if (tid < pf_cnt) { pf_c = kcls[f * n + tid]; pf_l = klp[f * n + tid]; }
+    }
+    __syncthreads();
+
+    // -- phase 2: prefix hash -> slot table; every candidate's mass
+    if (tid < nb) {
+      uint32_t h = hash_slot(sm.hpre[cur][tid]);
+      while (atomicCAS(&sm.hslot[h], -1, tid) != -1) h = (h + 1) & (kHash - 1);
+    }
+    const int M = nb * n1;
+    const int kblank = sm.c2k[blank];
+    for (int s = tid; s < M; s += nt) {
+      const int i = s / n1, j = s - i * n1;
+      const float pbi = sm.pb[cur][i], pnbi = sm.pnb[cur][i];
+      const int last = sm.cls[cur][i];
+      if (j == 0) {
+        const float nb_ = kblank >= 0 ? lr_lse2(pbi, pnbi) + sm.kl[kblank] : LR_NEG_INF;
+        const int kl_ = last >= 0 ? sm.c2k[last] : -1;
+        const float nnb = kl_ >= 0 ? pnbi + sm.kl[kl_] : LR_NEG_INF;
+        sm.spb[i] = nb_;
+        sm.spnb[i] = nnb;
+        sm.score[s] = lr_lse2(nb_, nnb);
+      } else {
+        const int k = j - 1;
+        float sc = LR_NEG_INF;
+        if (k < cnt) {
+          const int c = sm.kc[k];
+          if (c != blank) sc = (c == last ? pbi : lr_lse2(pbi, pnbi)) + sm.kl[k];
+        }
+        sm.score[s] = sc;
+      }
+    }
+    __syncthreads();
+
+    // -- phase 3: an extension that is already in the beam merges into that hypothesis
+    if (tid < nb && sm.depth[cur][tid] > 0) {
+      const int k = sm.c2k[sm.cls[cur][tid]];
+      int i = -1;
+      if (k >= 0) {
+        const uint64_t key = sm.hpar[cur][tid];
+        const int pdepth = sm.depth[cur][tid] - 1, pnode = sm.par[cur][tid];
+        for (uint32_t h = hash_slot(key);; h = (h + 1) & (kHash - 1)) {
+          const int c = sm.hslot[h];
+          if (c < 0) break;
+          if (sm.hpre[cur][c] == key && sm.depth[cur][c] == pdepth &&
+              (sm.node[cur][c] == pnode || same_prefix(sm.node[cur][c], pnode, gpar, gcls))) {
+            i = c;
+            break;
+          }
+        }
+        if (i >= 0) {
+          const int e = i * n1 + 1 + k;
+          const float m = sm.score[e];
+          sm.score[e] = LR_NEG_INF;
+          const float pn = lr_lse2(sm.spnb[tid], m);
+          sm.spnb[tid] = pn;
+          sm.score[tid * n1] = lr_lse2(sm.spb[tid], pn);
+        }
+      }
+    }
+    __syncthreads();
+
+    // -- phase 4: radix select of the W largest keys among the valid candidates
+    bool take_all = false;
+    uint64_t thr = 0;
+    int need = W;
+    for (int pass = 0, shift = 40; pass < 6; ++pass, shift -= 8) {
+      int* hist = sm.hist[pass & 1];
+      for (int s = tid; s < M; s += nt) {
+        const float sc = sm.score[s];
+        if (!(sc > LR_NEG_INF)) continue;
+        const uint64_t key = cand_key(sc, s, n1, sm.kc);
+        if (pass == 0 || (key >> (shift + 8)) == (thr >> (shift + 8))) atomicAdd(&hist[(key >> shift) & 255], 1);
+      }
+      __syncthreads();
+      if (tid < LR_WAVE) {
+        const int lane = tid;
+        int c4[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) c4[r] = hist[255 - 4 * lane - r];   // digits in descending order
+        const int loc = c4[0] + c4[1] + c4[2] + c4[3];
+        int inc = loc;
+#pragma unroll
+        for (int off = 1; off < LR_WAVE; off <<= 1) {
+          const int o = __shfl_up(inc, off);
+          if (lane >= off) inc += o;
+        }
+        const int ex = inc - loc;
+        if (ex < need && need <= inc) {
+          int cum = ex;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            if (need <= cum + c4[r]) {
+              sm.ctl[0] = 255 - 4 * lane - r; sm.ctl[1] = need - cum; sm.ctl[2] = c4[r];
+              break;
+            }
+            cum += c4[r];
+          }
+        }
+        if (lane == LR_WAVE - 1) sm.ctl[3] = inc;
+      }
+      __syncthreads();
+      if (pass == 0 && sm.ctl[3] <= W) { take_all = true; break; }
+      thr |= (uint64_t)sm.ctl[0] << shift;
+      need = sm.ctl[1];
+      const bool closed = sm.ctl[2] == need;
+      // this histogram is read; the next pass uses the other one, cleared in phase 1 or two passes ago
+      if (tid < 256) hist[tid] = 0;
+      if (closed) break;   // every key >= thr is in, exactly W of them
+      // (ctl is rewritten only by the next pass's scan, behind its histogram barrier)
+    }
+
+    // -- phase 5: compact the survivors, rank them, build the next beam
+    for (int s = tid; s < M; s += nt) {
+      const float sc = sm.score[s];
+      if (!(sc > LR_NEG_INF)) continue;
+      const uint64_t key = cand_key(sc, s, n1, sm.kc);
+      if (take_all || key >= thr) {
+        const int pos = atomicAdd(&sm.ctl[4], 1);
+        if (pos < W) { sm.selkey[pos] = key; sm.selslot[pos] = s; }
+      }
+    }
+    __syncthreads();
+    int nsel = sm.ctl[4];
+    nsel = nsel < W ? nsel : W;
+    const int nxt = cur ^ 1;
+    if (tid < nsel) {
+      const uint64_t key = sm.selkey[tid];
+      int r = 0;
+      for (int q = 0; q < nsel; ++q) r += sm.selkey[q] > key;
+      const int s = sm.selslot[tid];
+      const int i = s / n1, j = s - i * n1;
+      if (j == 0) {
+        sm.node[nxt][r] = sm.node[cur][i]; sm.par[nxt][r] = sm.par[cur][i];
+        sm.cls[nxt][r] = sm.cls[cur][i];   sm.depth[nxt][r] = sm.depth[cur][i];
+        sm.pb[nxt][r] = sm.spb[i];         sm.pnb[nxt][r] = sm.spnb[i];
+        sm.hpre[nxt][r] = sm.hpre[cur][i]; sm.hpar[nxt][r] = sm.hpar[cur][i];
+      } else {
+        const int c = sm.kc[j - 1];
+        const int id = 1 + t * W + r;
+        const int p = sm.node[cur][i];
+        __hip_atomic_store(gpar + id, p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(gcls + id, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        gfrm[id] = t;
+        sm.node[nxt][r] = id; sm.par[nxt][r] = p; sm.cls[nxt][r] = c; sm.depth[nxt][r] = sm.depth[cur][i] + 1;
+        sm.pb[nxt][r] = LR_NEG_INF;        sm.pnb[nxt][r] = sm.score[s];
+        sm.hpre[nxt][r] = prefix_hash(sm.hpre[cur][i], c); sm.hpar[nxt][r] = sm.hpre[cur][i];
+      }
+    }
+    if (tid < cnt) sm.c2k[sm.kc[tid]] = -1;
+    __syncthreads();
+    cur = nxt;
+    nb = nsel;
+  }
+
+  // -- output: every beam walks its node chain back to the root
+  __threadfence();
+  __syncthreads();
+  const int64_t obase = (int64_t)b * W * T;
+  for (int64_t e = tid; e < (int64_t)W * T; e += nt) {
+    const int r = (int)(e / T), d = (int)(e - (int64_t)r * T);
+    const int dep = r < nb ? sm.depth[cur][r] : 0;
+    if (d >= dep) { out_ids[obase + e] = -1; out_off[obase + e] = -1; }
+  }
+  if (tid < W) {
+    out_lens[(int64_t)b * W + tid] = tid < nb ? sm.depth[cur][tid] : 0;
+    out_scores[(int64_t)b * W + tid] =
+        tid < nb ? -lr_lse2(sm.pb[cur][tid], sm.pnb[cur][tid]) : __builtin_inff();
+  }
+  if (tid < nb) {
+    int id = sm.node[cur][tid];
+    int32_t* ids = out_ids + obase + (int64_t)tid * T;
+    int32_t* off = out_off + obase + (int64_t)tid * T;
+    for (int d = sm.depth[cur][tid] - 1; d >= 0; --d) {
+      ids[d] = gcls[id];
+      off[d] = gfrm[id];
+      id = gpar[id];
+    }
+  }
+}
+
+bool beam_supported(int T, int C, int W, int n) {
+  return W <= kBeamMaxW && n <= kBeamMaxN && C <= kBeamMaxC && beam_nodes(T, W) < INT32_MAX;
+}
+
+}  // namespace
+
+extern "C" size_t lr_ctc_beam_workspace_bytes(int B, int T, int C, int beam_width, int cutoff_top_n) {
+  if (B <= 0 || T <= 0 || C <= 0 || beam_width <= 0 || cutoff_top_n <= 0) return 0;
+  if (!beam_supported(T, C, beam_width, cutoff_top_n)) return 0;
+  return beam_ws_bytes(B, T, cutoff_top_n, beam_width);
+}
+
+extern "C" int lr_ctc_beam_decode(const float* probs, int64_t stride_b, int64_t stride_t, const int32_t* sizes,
+                                  int log_input, int cutoff_top_n, float cutoff_prob, int beam_width, int blank,
+                                  int32_t* out_ids, int32_t* out_offsets, int32_t* out_lens, float* out_scores,
+                                  void* workspace, size_t workspace_bytes, int B, int T, int C, lr_stream_t stream) {
+  LR_CHECK_ARG(probs && out_ids && out_offsets && out_lens && out_scores && workspace);
+  LR_CHECK_ARG(B > 0 && T > 0 && C > 0 && beam_width > 0 && cutoff_top_n > 0);
+  LR_CHECK_ARG(blank >= 0 && blank < C && !(cutoff_prob != cutoff_prob));
+  if (!beam_supported(T, C, beam_width, cutoff_top_n)) return LR_ERR_UNSUPPORTED;
+  const int W = beam_width, n = cutoff_top_n;
+  if (workspace_bytes < beam_ws_bytes(B, T, n, W)) return LR_ERR_WORKSPACE;
+  const BeamWs w = beam_ws_carve(workspace, B, T, n, W);
+  const int64_t frames = (int64_t)B * T;
+  LR_LAUNCH(beam_prune_kernel, dim3((unsigned)((frames + kPruneWaves - 1) / kPruneWaves)),
+            dim3(kPruneWaves * LR_WAVE), 0, stream, probs, stride_b, stride_t, sizes, log_input, cutoff_prob,
+            w.kcls, w.klp, w.kcnt, B, T, C, n);
+  int st = lr_launch_status();
+  if (st != LR_OK) return st;
+  LR_LAUNCH(beam_loop_kernel, dim3(B), dim3(kLoopThreads), 0, stream, w.kcls, w.klp, w.kcnt, sizes, w.npar, w.ncls,
+            w.nfrm, out_ids, out_offsets, out_lens, out_scores, T, W, n, blank);
+  return lr_launch_status();
+}

@@ -1,9 +1,14 @@
-"""CTC decoders — drop-in for `src/models/lipreader/decoder.py` (Decoder :23, GreedyDecoder :146).
+"""CTC decoders — drop-in for `src/models/lipreader/decoder.py` (Decoder :23, BeamCTCDecoder :90,
+GreedyDecoder :146).
 
 GreedyDecoder.decode keeps the reference's contract — `(strings, offsets)` with
 `strings[b] == [str]` and `offsets[b] == [IntTensor]` — but the per-frame Python loop with one
 `.item()` per element (decoder.py:168-169) becomes one kernel (argmax + collapse + ordered
 compaction) and a single device->host copy of the kept ids.
+
+BeamCTCDecoder keeps the reference's constructor and `(strings, offsets)` contract, but the
+search ctcdecode runs on CPU threads after `probs.cpu()` (decoder.py:139) runs on the GPU
+(lr_ctc_beam_decode: prefix beam search without a language model) with one device->host copy.
 """
 import torch
 
@@ -48,6 +53,75 @@ class Decoder(object):
 
   def decode(self, probs, sizes=None):
     raise NotImplementedError
+
+
+class BeamCTCDecoder(Decoder):
+  """decoder.py:90-143 on lr_ctc_beam_decode.  `log_probs_input` is ctcdecode's later keyword: True when
+  `probs` holds log-probabilities (VideoEncoder's output).  Classes are compared by index, as ctcdecode does:
+  no canonical-label mapping.  `num_processes`, and `alpha`/`beta` without a language model, are accepted and
+  ignored, as ctcdecode ignores them."""
+
+  def __init__(self, labels, lm_path=None, alpha=0, beta=0, cutoff_top_n=40, cutoff_prob=1.0, beam_width=100,
+               num_processes=4, blank_index=0, log_probs_input=False):
+    super(BeamCTCDecoder, self).__init__(labels, blank_index)
+    if lm_path is not None:
+      raise NotImplementedError("BeamCTCDecoder: lm_path=%r needs a KenLM scorer, which this package does not "
+                                "have; only lm_path=None (no language model) is supported" % (lm_path,))
+    if not 0 <= blank_index < len(labels):
+      raise ValueError("blank_index %d outside the %d labels" % (blank_index, len(labels)))
+    if beam_width < 1 or cutoff_top_n < 1:
+      raise ValueError("beam_width and cutoff_top_n must be >= 1")
+    self.cutoff_top_n = int(cutoff_top_n)
+    self.cutoff_prob = float(cutoff_prob)
+    self.beam_width = int(beam_width)
+    self.log_probs_input = bool(log_probs_input)
+
+  def decode_ids(self, probs, sizes=None):
+    """Device part: probs (B,T,C) -> (ids (B,W,T) int32, offsets (B,W,T) int32, lens (B,W) int32,
+    scores (B,W) fp32 = -log P, ascending) on the GPU.  Entries past lens are -1."""
+    _C.require_cuda(probs, sizes)
+    L = _C.lib()
+    if probs.dtype != torch.float32:
+      probs = probs.float()
+    if probs.stride(2) != 1:
+      probs = probs.contiguous()
+    B, T, C = probs.shape
+    if C > len(self.labels):
+      raise KeyError("probs has %d classes but only %d labels" % (C, len(self.labels)))
+    W, n = self.beam_width, self.cutoff_top_n
+    dev = probs.device
+    ids = torch.empty((B, W, T), dtype=torch.int32, device=dev)
+    off = torch.empty((B, W, T), dtype=torch.int32, device=dev)
+    lens = torch.empty((B, W), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, W), dtype=torch.float32, device=dev)
+    sz = None if sizes is None else sizes.to(device=dev, dtype=torch.int32).contiguous()
+    nbytes = L.lr_ctc_beam_workspace_bytes(B, T, C, W, n)
+    if nbytes == 0:
+      raise _C.LipReadingHipError("lr_ctc_beam_decode: unsupported shape B=%d T=%d C=%d beam_width=%d "
+                                  "cutoff_top_n=%d" % (B, T, C, W, n))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    _C.check(L.lr_ctc_beam_decode(probs.data_ptr(), probs.stride(0), probs.stride(1), _C.ptr(sz),
+                                  int(self.log_probs_input), n, self.cutoff_prob, W, self.blank_index,
+                                  ids.data_ptr(), off.data_ptr(), lens.data_ptr(), scores.data_ptr(),
+                                  ws.data_ptr(), nbytes, B, T, C, _C.stream_handle()),
+             "lr_ctc_beam_decode")
+    return ids, off, lens, scores
+
+  def decode(self, probs, sizes=None):
+    """decoder.py:128-143: probs (B,T,C) -> (strings, offsets); strings[b] holds beam_width strings, best
+    first ('' for empty beam slots), offsets[b] the matching IntTensors of frame indices."""
+    ids, off, lens, _ = self.decode_ids(probs, sizes)
+    B, W, T = ids.shape
+    host = torch.cat((ids.view(B, -1), off.view(B, -1), lens), dim=1).cpu()   # the one device->host copy
+    off = host[:, W * T:2 * W * T].view(B, W, T)
+    ids, lens = host[:, :W * T].view(B, W, T).tolist(), host[:, 2 * W * T:].tolist()
+    chars = self.int_to_char
+    strings, offsets = [], []
+    for b in range(B):
+      strings.append([''.join([chars[i] for i in ids[b][p][:n]]) for p, n in enumerate(lens[b])])
+      offsets.append([off[b, p, :n].clone() if n > 0 else torch.tensor([], dtype=torch.int)
+                      for p, n in enumerate(lens[b])])
+    return strings, offsets
 
 
 class GreedyDecoder(Decoder):

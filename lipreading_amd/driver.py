@@ -38,6 +38,9 @@ DEFAULTS = dict(  # train.py:134-167
     # --encoder=transformer swaps the recurrent encoder for the transformer (hidden_size = d_model, num_layers
     # layers, --nhead heads).  Either one selects the encoder+CTC loop with greedy CER (no attention decoder).
     frontend="none", encoder="rnn", nhead=4, crop_size=96,
+    # the CTC decoder behind the ctc_only loop's CER: greedy (the default) or beam (decoder.BeamCTCDecoder, no
+    # language model, ctcdecode's default cutoff_top_n=40) with --beam_width hypotheses
+    ctc_decoder="greedy", beam_width=100,
 )
 
 
@@ -111,6 +114,8 @@ def parse_flags(argv, defaults=DEFAULTS):
     raise SystemExit("--frontend must be none or conv3d")
   if out.get("encoder") not in ("rnn", "transformer"):
     raise SystemExit("--encoder must be rnn or transformer")
+  if out.get("ctc_decoder") not in ("greedy", "beam"):
+    raise SystemExit("--ctc_decoder must be greedy or beam")
   if out["frontend"] != "none" or out["encoder"] != "rnn":
     # the build-defined regimes are encoder + CTC (BASELINE configs[1], [4]); no attention decoder behind them
     for name in ("enable_ctc", "ctc_only"):
@@ -249,11 +254,20 @@ def run(**flags):
   encoder_path = os.path.join(weights_dir, "best_encoder.pth")
   decoder_path = os.path.join(weights_dir, "best_decoder.pth")
 
+  ctc_decoder = None
+  if ctc_only and f["ctc_decoder"] == "beam":
+    from .decoder import BeamCTCDecoder, ctc_labels
+    ctc_decoder = BeamCTCDecoder(ctc_labels(char2idx), beam_width=f["beam_width"], blank_index=0,
+                                 log_probs_input=True)
+
   def error_of(loader):
     """The live loop's "CER" is the sampled-token mismatch rate of the attention decoder (train.py:287-288
     via eval's correct/count); without a decoder it is the greedy-decoded CER of the CTC head
-    (decoder.py:64-73 on :182-197, as archive/train_model.py:351-357 composes them)."""
+    (decoder.py:64-73 on :182-197, as archive/train_model.py:351-357 composes them), or the beam-decoded one
+    with --ctc_decoder=beam."""
     if ctc_only:
+      if ctc_decoder is not None:
+        return T.ctc_cer(encoder, loader, device, char2idx, ctc_decoder)
       return T.greedy_cer(encoder, loader, device, char2idx)
     _, correct, count, _ = T.eval(encoder, decoding_step, loader, device, char2idx)
     return _cer(correct, count)

@@ -659,3 +659,38 @@ def greedy_cer(encoder, data_loader, device, char2idx):
         dist += dec.cer(hyp, ref)
         total += len(ref.replace(' ', ''))
   return dist / max(total, 1)
+
+
+def ctc_cer(encoder, data_loader, device, char2idx, decoder):
+  """greedy_cer's loop (time-out re-decode included) with any CTC decoder whose decode() returns the reference's
+  (strings, offsets) — e.g. decoder.BeamCTCDecoder(ctc_labels(char2idx), log_probs_input=True, ...); the best
+  hypothesis strings[b][0] is scored.  The encoder's output is log-probabilities: a BeamCTCDecoder here needs
+  log_probs_input=True."""
+  inv = {v: k for k, v in char2idx.items()}
+  encoder.eval()
+  dist, total = 0, 0
+  on_gpu = torch.device(device).type == "cuda"
+  flag2 = torch.zeros(2, dtype=torch.int32, device=device) if on_gpu else None
+  with torch.no_grad():
+    for frames, frame_lens, chars, char_lens in data_loader:
+      max_len = int(frame_lens.max()) if not frame_lens.is_cuda else None
+      if on_gpu:
+        _roll_faults(device)
+      log_probs, _, _ = encoder(frames.to(device), frame_lens.to(device), max_len=max_len)
+      strings, _ = decoder.decode(log_probs, frame_lens.to(device))
+      if on_gpu and not bool(_fault_keep(flag2)):
+        # the one-launch recurrence timed out (see greedy_cer): decode this batch again on the per-step kernels
+        inner = getattr(encoder, "encoder", encoder)
+        if hasattr(inner, "recurrence"):
+          saved, inner.recurrence = inner.recurrence, 'f32'
+          try:
+            log_probs, _, _ = encoder(frames.to(device), frame_lens.to(device), max_len=max_len)
+            strings, _ = decoder.decode(log_probs, frame_lens.to(device))
+          finally:
+            inner.recurrence = saved
+      for b in range(len(strings)):
+        ref = ''.join(inv[int(c)] for c in chars[b, 1:int(char_lens[b]) - 1])  # strip BOS/EOS
+        hyp = strings[b][0].replace(EOS, '')
+        dist += decoder.cer(hyp, ref)
+        total += len(ref.replace(' ', ''))
+  return dist / max(total, 1)

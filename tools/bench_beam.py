@@ -1,0 +1,96 @@
+"""CTC prefix beam search: ms per batch of lr_ctc_beam_decode (BeamCTCDecoder.decode_ids, device time by events, and
+decode() end to end with its one device->host copy and the strings) next to the float64 CPU restatement of
+tests/test_beam_cpu.py spread over a process pool.
+
+  python tools/bench_beam.py [--iters 50] [--threads 16] [--cpu-batches 1]
+
+B = 32, T = 75, C = 65 (the fallback vocabulary), model-like peaked frames; (W, n) in
+{(1,1), (8,40), (100,40), (128,64)}.  One JSON line per row and a table at the end.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+import multiprocessing
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+  sys.path.insert(0, ROOT)
+
+B, T, C = 32, 75, 65
+SHAPES = [(1, 1), (8, 40), (100, 40), (128, 64)]
+
+
+def peaked(rng):
+  x = rng.standard_normal((B, T, C)) * 0.8
+  for b in range(B):
+    t = 0
+    while t < T:
+      run = int(rng.integers(1, 5))
+      c = 0 if rng.random() < 0.5 else int(rng.integers(1, C))
+      x[b, t:t + run, c] += rng.uniform(3.0, 7.0)
+      t += run
+  x = np.exp(x - x.max(2, keepdims=True))
+  return (x / x.sum(2, keepdims=True)).astype(np.float32)
+
+
+def _ref_one(args):
+  from tests.test_beam_cpu import beam_ref
+  v, W, n = args
+  return beam_ref(v, T, W, n)
+
+
+def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument("--iters", type=int, default=50)
+  ap.add_argument("--threads", type=int, default=16)
+  ap.add_argument("--cpu-batches", type=int, default=1)
+  a = ap.parse_args()
+  import torch
+  from lipreading_amd import _build
+  from lipreading_amd.decoder import BeamCTCDecoder
+  _build.build_library()
+  dev = torch.device("cuda:0")
+  p = peaked(np.random.default_rng(0))
+  pd = torch.tensor(p, device=dev)
+  labels = ["_"] + [chr(ord("!") + i) for i in range(C - 1)]
+  rows = []
+  # spawned workers: fresh interpreters that never touch the GPU (a fork would inherit this process's device handles)
+  with multiprocessing.get_context("spawn").Pool(a.threads) as pool:
+    pool.map(_ref_one, [(p[b], 1, 1) for b in range(B)])   # start the workers outside the timed region
+    for W, n in SHAPES:
+      dec = BeamCTCDecoder(labels, beam_width=W, cutoff_top_n=n)
+      for _ in range(5):
+        dec.decode_ids(pd)
+      torch.cuda.synchronize()
+      e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      e0.record()
+      for _ in range(a.iters):
+        dec.decode_ids(pd)
+      e1.record()
+      torch.cuda.synchronize()
+      gpu_ms = e0.elapsed_time(e1) / a.iters
+      t0 = time.perf_counter()
+      for _ in range(a.iters):
+        dec.decode(pd)
+      e2e_ms = (time.perf_counter() - t0) * 1e3 / a.iters
+      t0 = time.perf_counter()
+      for _ in range(a.cpu_batches):
+        pool.map(_ref_one, [(p[b], W, n) for b in range(B)])
+      cpu_ms = (time.perf_counter() - t0) * 1e3 / a.cpu_batches
+      row = dict(W=W, n=n, B=B, T=T, C=C, gpu_decode_ids_ms=round(gpu_ms, 4), gpu_decode_ms=round(e2e_ms, 4),
+                 cpu_ref_ms=round(cpu_ms, 2), cpu_threads=a.threads)
+      rows.append(row)
+      print(json.dumps(row), flush=True)
+  print("\n| W | n | GPU decode_ids ms | GPU decode() ms | CPU restatement ms (%d procs) |" % a.threads)
+  print("|---|---|---|---|---|")
+  for r in rows:
+    print("| %d | %d | %.3f | %.3f | %.1f |" % (r["W"], r["n"], r["gpu_decode_ids_ms"], r["gpu_decode_ms"],
+                                               r["cpu_ref_ms"]))
+
+
+if __name__ == "__main__":
+  main()
