@@ -703,6 +703,35 @@ int lr_ctc_beam_decode(const float* probs, int64_t stride_b, int64_t stride_t, c
                        int32_t* out_ids, int32_t* out_offsets, int32_t* out_lens, float* out_scores,
                        void* workspace, size_t workspace_bytes, int B, int T, int C, lr_stream_t stream);
 
+/* ---- A6c: the same search with an ARPA n-gram word language model — the reference's lm_path / alpha / beta ---- */
+/* The specification and the blob's layout are in lipreading_amd/csrc/lr_ctc_beam.hip.
+ * Limits: order <= 6, vocabulary < 2^24 (the packer's LR_ERR_UNSUPPORTED); the search's limits as above. */
+
+/* Bytes of the packed LM blob (0 for arguments lr_ctc_beam_lm_pack rejects).  counts[order]: n-grams per order;
+ * dict_chars: total class ids of the dictionary's spellings. */
+size_t lr_ctc_beam_lm_pack_bytes(int order, const int64_t* counts, int64_t dict_chars);
+
+/* Host only (no device call): pack an ARPA model and its dictionary into `out` (host memory).
+ *   words       every n-gram's word ids, order 1 first, each n-gram's words oldest first; unigram i is word id i
+ *   log10_prob, log10_backoff  per n-gram, as in the ARPA text (an absent backoff is 0)
+ *   bos         word id of <s>, -1 if none
+ *   dict_word[dict_n], dict_off[dict_n+1], dict_cls[dict_off[dict_n]]: the dictionary's words and their
+ *               spellings in class ids (< n_classes <= 256).
+ * A duplicate n-gram, an n-gram whose (k-1)-gram prefix is not listed, or two words with one spelling is
+ * LR_ERR_INVALID_ARG. */
+int lr_ctc_beam_lm_pack(void* out, size_t out_bytes, int order, const int64_t* counts, const int32_t* words,
+                        const double* log10_prob, const double* log10_backoff, int bos, int64_t dict_n,
+                        const int32_t* dict_word, const int64_t* dict_off, const int32_t* dict_cls, int n_classes);
+
+/* lr_ctc_beam_decode plus the language model: lm = the packed blob on the device, class_roles [C] int32 on the
+ * device (0 transparent, 1 word character, 2 space), alpha / beta finite.  Workspace: lr_ctc_beam_workspace_bytes.
+ * out_scores = -(log mass + the final word's term), ascending. */
+int lr_ctc_beam_lm_decode(const float* probs, int64_t stride_b, int64_t stride_t, const int32_t* sizes,
+                          int log_input, int cutoff_top_n, float cutoff_prob, int beam_width, int blank,
+                          const void* lm, const int32_t* class_roles, float alpha, float beta,
+                          int32_t* out_ids, int32_t* out_offsets, int32_t* out_lens, float* out_scores,
+                          void* workspace, size_t workspace_bytes, int B, int T, int C, lr_stream_t stream);
+
 /* ---- A8 (BUILD-DEFINED, no reference symbol): 3-D conv frontend on bf16 MFMA -------------- */
 /* The reference has no conv frontend (src/models/lipreader/model.py:122,153-156 are comments, the
  * `ced` configs are empty); BASELINE.json's north_star asks for one ("im2col + MFMA GEMM for the 3D

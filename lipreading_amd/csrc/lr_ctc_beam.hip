@@ -1,4 +1,4 @@
-// lr_ctc_beam.hip — CTC prefix beam search without a language model for gfx950.
+// lr_ctc_beam.hip — CTC prefix beam search, with or without an ARPA n-gram word language model, for gfx950.
 //
 // Replaces src/models/lipreader/decoder.py:90-143 (BeamCTCDecoder), which hands the search to the external
 // `ctcdecode` C++ library (CTCBeamDecoder with lm_path=None) after a probs.cpu() copy.  ctcdecode is not part of this
@@ -47,6 +47,46 @@
 //      node with equal classes on the way (the rare case).  q then takes over that extension's mass.  The top-W of the W*(n+1) candidates is a radix select on 48-bit
 //      (score, tie-break) keys — 8-bit digits, LDS histograms, stopping at the first digit that closes the count —
 //      followed by a rank count among the W survivors.  At the end each beam walks its node chain backwards.
+//
+// With a word language model (lr_ctc_beam_lm_decode; the reference passes ctcdecode a KenLM model through lm_path,
+// alpha and beta).  Everything above holds; the following is added.
+//   Classes  class_roles[C] names each class's role.  The label that is exactly ' ' is the space class; it separates
+//            words.  Every other one-character label except the blank is a word character.  All other classes
+//            (the blank, multi-character labels such as <EOS>) are transparent: they stay in the output but never
+//            extend or complete a word.  A prefix's words are its maximal runs of word characters.  A word is
+//            completed by the space that follows it; a transparent class drops the run it follows, which is then
+//            neither scored nor part of any later context, and the next word character starts a new word.
+//   LM term  lm(w | ctx) = ln(10) * log10 P(w | ctx) by standard ARPA backoff.  ctx is the last order-1 completed
+//            words before w, padded on the left with <s>.  If (ctx, w) is listed, its probability; otherwise
+//            backoff(ctx) + P(w | ctx[1:]), an absent backoff counting as 0.  If w or any word of ctx is not an ARPA
+//            unigram the term is OOV = -1000 (no ln 10 factor; ctcdecode's Scorer::get_log_cond_prob).  </s> is
+//            never scored.
+//   Apply    each application adds alpha * lm + beta to the extension's log mass: an extension p+space (from
+//            score(p), and from p_blank(p) when p already ends in a space) applies it to the word p ends in, if
+//            that word is non-empty.  A leading space, a repeated space or a space right after a transparent class
+//            adds nothing.
+//   Dict     a word-character extension exists only if the current word stays a prefix of a vocabulary word (a
+//            trie of the vocabulary spelled in class ids, as ctcdecode's dictionary for a word LM); otherwise the
+//            candidate is not a hypothesis.  The vocabulary is the ARPA unigrams except <s>, </s> and <unk>; words
+//            with a character that has no class cannot be reached and are left out.  There is no switch to turn it
+//            off.
+//   End      after the last frame each hypothesis whose last word is non-empty gets alpha * lm + beta for that word
+//            (a vocabulary prefix that is not a word is OOV); then the beam is re-sorted by the final score, ties
+//            keeping the earlier rank.  out_scores = -(log mass + that term), ascending.
+//   Merging  the LM state (trie node, context word ids) is a function of the prefix, so merging by prefix holds.
+//   Deviations from ctcdecode: no character-based LM mode; no min_cutoff; empty words are not scored; ARPA only
+//            (the host reads the text, lipreading_amd/lm.py; KenLM's binary formats are not read).
+//   Limits   order <= 6 (KenLM's default maximum) and vocabulary < 2^24 (the packer's LR_ERR_UNSUPPORTED);
+//            non-finite alpha or beta is LR_ERR_INVALID_ARG.
+//   Layout   one packed read-only blob per model (lm_pack, below), uploaded once.  Lookups are open-addressing
+//            hash tables on exact 64-bit keys: (entry id of the n-gram's first k-1 words, last word id) and
+//            (trie node, class); a word or an n-gram is never identified by a hash of its string.  The loop keeps
+//            each hypothesis's trie node, its node's word id, its last order-1 completed word ids and the cached
+//            term alpha * lm + beta of its current word in LDS: phase 2 adds the cached term to the space
+//            extension and probes the trie for each word-character extension; phase 5 probes the trie again for
+//            the survivors and scores their new current word; the end term is the cached one.
+#include <string.h>
+
 #include "lr_common.h"
 
 namespace {
@@ -160,8 +200,142 @@ __global__ __launch_bounds__(kPruneWaves * LR_WAVE) void beam_prune_kernel(
 }
 
 // ---------------------------------------------------------------------------------------
+// the language-model blob: its layout is owned here (lm_pack writes it, the loop reads it)
+// ---------------------------------------------------------------------------------------
+// Little-endian, every section 16-byte aligned, offsets in bytes from the blob's start:
+//   LmHeader           kLmHeaderBytes
+//   uni[V]             float2 (ln p, ln backoff) of unigram w (word id w = its row in the ARPA \1-grams: section)
+//   ngram[ngram_slots] LmNgram, ngram_slots a power of two at load <= 1/2.  Entry ids: 0 is the empty context, 1+w
+//                      unigram w, V+1+slot the n-gram in that slot.  The n-gram (w1..wk), k >= 2, has key
+//                      (entry id of w1..w(k-1)) << 24 | wk; its (k-1)-gram prefix is always listed.
+//   trie[trie_slots]   LmTrie, trie_slots a power of two at load <= 1/2; key (node << 8) | class, root node 0;
+//                      child is the node reached, word the vocabulary word id it spells (-1: only a prefix).
+// Empty slots of both tables hold key kLmEmpty.  Values are natural logs (ln 10 * the ARPA's log10), fp32.
+constexpr uint32_t kLmMagic = 0x4d4c524cu;   // "LRLM"
+constexpr uint32_t kLmVersion = 1;
+constexpr int kLmMaxOrder = 6;
+constexpr int kLmMaxCtx = kLmMaxOrder - 1;
+constexpr int64_t kLmMaxVocab = (int64_t)1 << 24;
+constexpr uint64_t kLmEmpty = ~0ull;
+constexpr float kLmOov = -1000.f;
+constexpr size_t kLmHeaderBytes = 128;
+constexpr int kRoleTransparent = 0, kRoleWord = 1, kRoleSpace = 2;
+
+struct LmHeader {
+  uint32_t magic, version;
+  int32_t order, vocab, bos, pad_;   // bos: word id of <s>, -1 if the ARPA has none
+  int64_t ngram_slots, trie_slots;
+  int64_t uni_off, ngram_off, trie_off, bytes;
+};
+static_assert(sizeof(LmHeader) <= kLmHeaderBytes, "LmHeader");
+struct LmNgram {
+  uint64_t key;
+  float lp, lbow;
+};
+struct LmTrie {
+  uint64_t key;
+  int32_t child, word;
+};
+static_assert(sizeof(LmNgram) == 16 && sizeof(LmTrie) == 16, "16-byte slots");
+
+__host__ __device__ inline uint64_t lm_mix(uint64_t x) {   // splitmix64's finaliser
+  x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
+  x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
+  return x ^ (x >> 31);
+}
+__host__ __device__ inline uint64_t lm_ngram_key(int64_t entry, int word) {
+  return ((uint64_t)entry << 24) | (uint64_t)(uint32_t)word;
+}
+__host__ __device__ inline uint64_t lm_trie_key(int node, int cls) {
+  return ((uint64_t)(uint32_t)node << 8) | (uint64_t)(uint32_t)cls;
+}
+
+// The device view, read from the header once per workgroup.
+struct LmView {
+  const float2* uni;
+  const LmNgram* ngram;
+  const LmTrie* trie;
+  uint64_t nmask, tmask;
+  int vocab, m;   // m = order - 1 context words
+};
+
+__device__ __forceinline__ LmView lm_view(const uint8_t* blob) {
+  const LmHeader* h = reinterpret_cast<const LmHeader*>(blob);
+  LmView v;
+  v.uni = reinterpret_cast<const float2*>(blob + h->uni_off);
+  v.ngram = reinterpret_cast<const LmNgram*>(blob + h->ngram_off);
+  v.trie = reinterpret_cast<const LmTrie*>(blob + h->trie_off);
+  v.nmask = (uint64_t)h->ngram_slots - 1;
+  v.tmask = (uint64_t)h->trie_slots - 1;
+  v.vocab = h->vocab;
+  v.m = h->order - 1;
+  return v;
+}
+
+// entry id of the n-gram (entry's words, word), or -1 if it is not listed
+__device__ __forceinline__ int64_t lm_ngram_find(const LmView& L, int64_t entry, int word, float* lp, float* lbow) {
+  const uint64_t key = lm_ngram_key(entry, word);
+  for (uint64_t s = lm_mix(key) & L.nmask;; s = (s + 1) & L.nmask) {
+    const LmNgram g = L.ngram[s];
+    if (g.key == key) { *lp = g.lp; *lbow = g.lbow; return (int64_t)L.vocab + 1 + (int64_t)s; }
+    if (g.key == kLmEmpty) return -1;
+  }
+}
+
+// child of a trie node by class: .x = child node (-1 if the word leaves the vocabulary), .y = the word it spells
+__device__ __forceinline__ int2 lm_trie_find(const LmView& L, int node, int cls) {
+  const uint64_t key = lm_trie_key(node, cls);
+  for (uint64_t s = lm_mix(key) & L.tmask;; s = (s + 1) & L.tmask) {
+    const LmTrie e = L.trie[s];
+    if (e.key == key) return make_int2(e.child, e.word);
+    if (e.key == kLmEmpty) return make_int2(-1, -1);
+  }
+}
+
+// lm(w | ctx): ctx holds L.m word ids, oldest first (-1 = not a unigram)
+__device__ float lm_score(const LmView& L, const int* ctx, int w) {
+  if (w < 0) return kLmOov;
+  int c[kLmMaxCtx];
+  for (int j = 0; j < L.m; ++j) {
+    c[j] = ctx[j];
+    if (c[j] < 0) return kLmOov;
+  }
+  float acc = 0.f;
+  for (int j = 0; j < L.m; ++j) {   // context c[j..m-1], longest first
+    int64_t e = 1 + c[j];
+    float lp, lbow = L.uni[c[j]].y;
+    for (int q = j + 1; q < L.m && e >= 0; ++q) e = lm_ngram_find(L, e, c[q], &lp, &lbow);
+    if (e < 0) continue;   // the context is not listed: neither is (context, w), and its backoff is 0
+    float wbow;
+    if (lm_ngram_find(L, e, w, &lp, &wbow) >= 0) return acc + lp;
+    acc += lbow;
+  }
+  return acc + L.uni[w].x;
+}
+
+struct LmArgs {
+  const uint8_t* blob;     // nullptr: no language model
+  const int32_t* roles;    // [C] kRole*
+  float alpha, beta;
+};
+
+// ---------------------------------------------------------------------------------------
 // 2. the frame loop: one workgroup per utterance
 // ---------------------------------------------------------------------------------------
+// LM state of the beam (the LM instantiation only): trie node, the word id that node spells, the cached term
+// alpha * lm + beta of that word (0 at the root) and the last m completed word ids
+template <bool LM>
+struct BeamLmSmem {
+  int tnode[2][kBeamMaxW], tword[2][kBeamMaxW];
+  float tterm[2][kBeamMaxW];
+  int ctx[2][kBeamMaxW][kLmMaxCtx];
+  int role[kBeamMaxC];
+  float fin[kBeamMaxW];
+  int perm[kBeamMaxW];
+};
+template <>
+struct BeamLmSmem<false> {};
+
 struct BeamSmem {
   float score[kMaxCand];          // candidate s = i*(n+1) + j: j = 0 parent i's own continuation, j = 1+k extension by
                                   // kept class k; -inf = not a hypothesis
@@ -212,12 +386,16 @@ __device__ __forceinline__ uint64_t cand_key(float sc, int s, int n1, const int*
   return ((uint64_t)ord_f32(sc) << 16) | (uint64_t)(0xffffu - (uint32_t)tb);
 }
 
+// LM = false is the search without a language model; LM = true adds the terms and the dictionary of the header.
+template <bool LM>
 __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
     const int32_t* __restrict__ kcls, const float* __restrict__ klp, const int32_t* __restrict__ kcnt,
     const int32_t* __restrict__ sizes, int32_t* __restrict__ npar, int32_t* __restrict__ ncls,
     int32_t* __restrict__ nfrm, int32_t* __restrict__ out_ids, int32_t* __restrict__ out_off,
-    int32_t* __restrict__ out_lens, float* __restrict__ out_scores, int T, int W, int n, int blank) {
+    int32_t* __restrict__ out_lens, float* __restrict__ out_scores, int T, int W, int n, int blank, int C,
+    LmArgs lma) {
   __shared__ BeamSmem sm;
+  __shared__ BeamLmSmem<LM> lsm;
   const int b = blockIdx.x;
   const int tid = threadIdx.x;
   const int nt = blockDim.x;
@@ -234,6 +412,16 @@ __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
     sm.node[0][0] = 0; sm.par[0][0] = -1; sm.cls[0][0] = -1; sm.depth[0][0] = 0;
     sm.pb[0][0] = 0.f; sm.pnb[0][0] = LR_NEG_INF;
     sm.hpre[0][0] = 0; sm.hpar[0][0] = 0;
+  }
+  LmView L{};
+  if constexpr (LM) {
+    L = lm_view(lma.blob);
+    const int bos = reinterpret_cast<const LmHeader*>(lma.blob)->bos;
+    for (int c = tid; c < kBeamMaxC; c += nt) lsm.role[c] = c < C ? lma.roles[c] : kRoleTransparent;
+    if (tid == 0) {
+      lsm.tnode[0][0] = 0; lsm.tword[0][0] = -1; lsm.tterm[0][0] = 0.f;
+      for (int q = 0; q < kLmMaxCtx; ++q) lsm.ctx[0][0][q] = bos;
+    }
   }
   int cur = 0, nb = 1;
   // the kept list of the next frame is loaded one frame ahead
@@ -284,6 +472,13 @@ __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
         if (k < cnt) {
           const int c = sm.kc[k];
           if (c != blank) sc = (c == last ? pbi : lr_lse2(pbi, pnbi)) + sm.kl[k];
+          if constexpr (LM) {
+            if (sc > LR_NEG_INF) {
+              const int role = lsm.role[c];
+              if (role == kRoleSpace) sc += lsm.tterm[cur][i];   // 0 when the current word is empty
+              else if (role == kRoleWord && lm_trie_find(L, lsm.tnode[cur][i], c).x < 0) sc = LR_NEG_INF;
+            }
+          }
         }
         sm.score[s] = sc;
       }
@@ -393,6 +588,11 @@ __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
         sm.cls[nxt][r] = sm.cls[cur][i];   sm.depth[nxt][r] = sm.depth[cur][i];
         sm.pb[nxt][r] = sm.spb[i];         sm.pnb[nxt][r] = sm.spnb[i];
         sm.hpre[nxt][r] = sm.hpre[cur][i]; sm.hpar[nxt][r] = sm.hpar[cur][i];
+        if constexpr (LM) {
+          lsm.tnode[nxt][r] = lsm.tnode[cur][i]; lsm.tword[nxt][r] = lsm.tword[cur][i];
+          lsm.tterm[nxt][r] = lsm.tterm[cur][i];
+          for (int q = 0; q < kLmMaxCtx; ++q) lsm.ctx[nxt][r][q] = lsm.ctx[cur][i][q];
+        }
       } else {
         const int c = sm.kc[j - 1];
         const int id = 1 + t * W + r;
@@ -403,6 +603,23 @@ __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
         sm.node[nxt][r] = id; sm.par[nxt][r] = p; sm.cls[nxt][r] = c; sm.depth[nxt][r] = sm.depth[cur][i] + 1;
         sm.pb[nxt][r] = LR_NEG_INF;        sm.pnb[nxt][r] = sm.score[s];
         sm.hpre[nxt][r] = prefix_hash(sm.hpre[cur][i], c); sm.hpar[nxt][r] = sm.hpre[cur][i];
+        if constexpr (LM) {
+          const int role = lsm.role[c], node = lsm.tnode[cur][i];
+          int* ctx = lsm.ctx[nxt][r];
+          const int* pctx = lsm.ctx[cur][i];
+          if (role == kRoleWord) {
+            // the word stays in the dictionary (phase 2 dropped the others); score the new current word once
+            const int2 ch = lm_trie_find(L, node, c);
+            for (int q = 0; q < kLmMaxCtx; ++q) ctx[q] = pctx[q];
+            lsm.tnode[nxt][r] = ch.x; lsm.tword[nxt][r] = ch.y;
+            lsm.tterm[nxt][r] = lma.alpha * lm_score(L, ctx, ch.y) + lma.beta;
+          } else {
+            // a space completes a non-empty word: it joins the context; a transparent class drops the run
+            const bool push = role == kRoleSpace && node != 0;
+            for (int q = 0; q < L.m; ++q) ctx[q] = push ? (q + 1 < L.m ? pctx[q + 1] : lsm.tword[cur][i]) : pctx[q];
+            lsm.tnode[nxt][r] = 0; lsm.tword[nxt][r] = -1; lsm.tterm[nxt][r] = 0.f;
+          }
+        }
       }
     }
     if (tid < cnt) sm.c2k[sm.kc[tid]] = -1;
@@ -411,25 +628,45 @@ __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
     nb = nsel;
   }
 
+  // -- end of utterance (LM): the last word's term, then a stable re-sort by the final score
+  if constexpr (LM) {
+    if (tid < nb) lsm.fin[tid] = lr_lse2(sm.pb[cur][tid], sm.pnb[cur][tid]) + lsm.tterm[cur][tid];
+    __syncthreads();
+    if (tid < nb) {
+      const float f = lsm.fin[tid];
+      int r = 0;
+      for (int q = 0; q < nb; ++q) r += lsm.fin[q] > f || (lsm.fin[q] == f && q < tid);
+      lsm.perm[r] = tid;
+    }
+  }
+
   // -- output: every beam walks its node chain back to the root
   __threadfence();
   __syncthreads();
   const int64_t obase = (int64_t)b * W * T;
+  // output rank r holds beam entry src(r)
+  auto src = [&](int r) {
+    if constexpr (LM) return lsm.perm[r];
+    else return r;
+  };
   for (int64_t e = tid; e < (int64_t)W * T; e += nt) {
     const int r = (int)(e / T), d = (int)(e - (int64_t)r * T);
-    const int dep = r < nb ? sm.depth[cur][r] : 0;
+    const int dep = r < nb ? sm.depth[cur][src(r)] : 0;
     if (d >= dep) { out_ids[obase + e] = -1; out_off[obase + e] = -1; }
   }
   if (tid < W) {
-    out_lens[(int64_t)b * W + tid] = tid < nb ? sm.depth[cur][tid] : 0;
-    out_scores[(int64_t)b * W + tid] =
-        tid < nb ? -lr_lse2(sm.pb[cur][tid], sm.pnb[cur][tid]) : __builtin_inff();
+    out_lens[(int64_t)b * W + tid] = tid < nb ? sm.depth[cur][src(tid)] : 0;
+    if constexpr (LM)
+      out_scores[(int64_t)b * W + tid] = tid < nb ? -lsm.fin[src(tid)] : __builtin_inff();
+    else
+      out_scores[(int64_t)b * W + tid] =
+          tid < nb ? -lr_lse2(sm.pb[cur][tid], sm.pnb[cur][tid]) : __builtin_inff();
   }
   if (tid < nb) {
-    int id = sm.node[cur][tid];
+    int id = sm.node[cur][src(tid)];
     int32_t* ids = out_ids + obase + (int64_t)tid * T;
     int32_t* off = out_off + obase + (int64_t)tid * T;
-    for (int d = sm.depth[cur][tid] - 1; d >= 0; --d) {
+    for (int d = sm.depth[cur][src(tid)] - 1; d >= 0; --d) {
       ids[d] = gcls[id];
       off[d] = gfrm[id];
       id = gpar[id];
@@ -440,6 +677,47 @@ __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
 bool beam_supported(int T, int C, int W, int n) {
   return W <= kBeamMaxW && n <= kBeamMaxN && C <= kBeamMaxC && beam_nodes(T, W) < INT32_MAX;
 }
+
+uint64_t pow2_at_least(uint64_t x) {
+  uint64_t p = 16;
+  while (p < x) p <<= 1;
+  return p;
+}
+
+struct LmSizes {
+  int64_t higher;    // n-grams of order >= 2
+  uint64_t nslots, tslots;
+  size_t uni_off, ngram_off, trie_off, bytes;
+};
+
+// 0 for orders and vocabularies the blob does not hold (LR_ERR_UNSUPPORTED), -1 for bad arguments
+int lm_sizes(int order, const int64_t* counts, int64_t dict_chars, LmSizes* z) {
+  if (order < 1 || !counts || dict_chars < 0) return -1;
+  if (order > kLmMaxOrder) return 0;
+  if (counts[0] < 1) return -1;
+  if (counts[0] >= kLmMaxVocab) return 0;
+  z->higher = 0;
+  for (int k = 1; k < order; ++k) {
+    if (counts[k] < 0) return -1;
+    z->higher += counts[k];
+  }
+  if (z->higher > ((int64_t)1 << 36) || dict_chars >= ((int64_t)1 << 30)) return 0;
+  z->nslots = pow2_at_least(2 * (uint64_t)z->higher);
+  z->tslots = pow2_at_least(2 * (uint64_t)dict_chars);
+  z->uni_off = kLmHeaderBytes;
+  z->ngram_off = lr_align_up(z->uni_off + (size_t)counts[0] * sizeof(float2), 16);
+  z->trie_off = z->ngram_off + z->nslots * sizeof(LmNgram);
+  z->bytes = z->trie_off + z->tslots * sizeof(LmTrie);
+  return 1;
+}
+
+// host-side open addressing over the blob's tables (the device reads them with lm_ngram_find / lm_trie_find)
+template <class Slot>
+Slot* host_probe(Slot* tab, uint64_t mask, uint64_t key) {
+  for (uint64_t s = lm_mix(key) & mask;; s = (s + 1) & mask)
+    if (tab[s].key == key || tab[s].key == kLmEmpty) return tab + s;
+}
+
 
 }  // namespace
 
@@ -466,7 +744,107 @@ extern "C" int lr_ctc_beam_decode(const float* probs, int64_t stride_b, int64_t 
             w.kcls, w.klp, w.kcnt, B, T, C, n);
   int st = lr_launch_status();
   if (st != LR_OK) return st;
-  LR_LAUNCH(beam_loop_kernel, dim3(B), dim3(kLoopThreads), 0, stream, w.kcls, w.klp, w.kcnt, sizes, w.npar, w.ncls,
-            w.nfrm, out_ids, out_offsets, out_lens, out_scores, T, W, n, blank);
+  LR_LAUNCH(beam_loop_kernel<false>, dim3(B), dim3(kLoopThreads), 0, stream, w.kcls, w.klp, w.kcnt, sizes, w.npar,
+            w.ncls, w.nfrm, out_ids, out_offsets, out_lens, out_scores, T, W, n, blank, C, LmArgs{});
+  return lr_launch_status();
+}
+
+extern "C" size_t lr_ctc_beam_lm_pack_bytes(int order, const int64_t* counts, int64_t dict_chars) {
+  LmSizes z;
+  return lm_sizes(order, counts, dict_chars, &z) == 1 ? z.bytes : 0;
+}
+
+extern "C" int lr_ctc_beam_lm_pack(void* out, size_t out_bytes, int order, const int64_t* counts,
+                                   const int32_t* words, const double* log10_prob, const double* log10_backoff,
+                                   int bos, int64_t dict_n, const int32_t* dict_word, const int64_t* dict_off,
+                                   const int32_t* dict_cls, int n_classes) {
+  LR_CHECK_ARG(out && words && log10_prob && log10_backoff && dict_n >= 0 && dict_off);
+  LR_CHECK_ARG(dict_n == 0 || (dict_word && dict_cls));
+  LR_CHECK_ARG(n_classes > 0 && n_classes <= kBeamMaxC);
+  LmSizes z;
+  const int ok = lm_sizes(order, counts, dict_off[dict_n], &z);
+  if (ok == 0) return LR_ERR_UNSUPPORTED;
+  if (ok < 0) return LR_ERR_INVALID_ARG;
+  if (out_bytes < z.bytes) return LR_ERR_WORKSPACE;
+  const int64_t V = counts[0];
+  LR_CHECK_ARG(bos >= -1 && bos < V);
+  const double ln10 = 2.302585092994045684;
+  uint8_t* blob = static_cast<uint8_t*>(out);
+  memset(blob, 0, z.ngram_off);
+  memset(blob + z.ngram_off, 0xff, z.bytes - z.ngram_off);   // every key kLmEmpty
+  LmHeader* h = reinterpret_cast<LmHeader*>(blob);
+  h->magic = kLmMagic; h->version = kLmVersion; h->order = order; h->vocab = (int32_t)V; h->bos = bos; h->pad_ = 0;
+  h->ngram_slots = (int64_t)z.nslots; h->trie_slots = (int64_t)z.tslots;
+  h->uni_off = (int64_t)z.uni_off; h->ngram_off = (int64_t)z.ngram_off; h->trie_off = (int64_t)z.trie_off;
+  h->bytes = (int64_t)z.bytes;
+  float2* uni = reinterpret_cast<float2*>(blob + z.uni_off);
+  LmNgram* ng = reinterpret_cast<LmNgram*>(blob + z.ngram_off);
+  LmTrie* tr = reinterpret_cast<LmTrie*>(blob + z.trie_off);
+  // n-grams, lower orders first so that every prefix already has its entry id
+  int64_t row = 0;
+  const int32_t* w = words;
+  for (int k = 1; k <= order; ++k) {
+    for (int64_t i = 0; i < counts[k - 1]; ++i, ++row, w += k) {
+      for (int q = 0; q < k; ++q) LR_CHECK_ARG(w[q] >= 0 && w[q] < V);
+      const float lp = (float)(log10_prob[row] * ln10), lbow = (float)(log10_backoff[row] * ln10);
+      if (k == 1) {
+        LR_CHECK_ARG(w[0] == i);   // unigram i is word id i
+        uni[i] = make_float2(lp, lbow);
+        continue;
+      }
+      int64_t e = 1 + w[0];
+      for (int q = 1; q + 1 < k; ++q) {
+        const LmNgram* g = host_probe(ng, z.nslots - 1, lm_ngram_key(e, w[q]));
+        LR_CHECK_ARG(g->key != kLmEmpty);   // the (k-1)-gram prefix is not listed
+        e = V + 1 + (g - ng);
+      }
+      const uint64_t key = lm_ngram_key(e, w[k - 1]);
+      LmNgram* g = host_probe(ng, z.nslots - 1, key);
+      LR_CHECK_ARG(g->key == kLmEmpty);     // a duplicate n-gram
+      g->key = key; g->lp = lp; g->lbow = lbow;
+    }
+  }
+  // the vocabulary trie over class ids
+  int32_t nodes = 1;
+  for (int64_t d = 0; d < dict_n; ++d) {
+    const int64_t a = dict_off[d], b = dict_off[d + 1];
+    LR_CHECK_ARG(a < b && dict_word[d] >= 0 && dict_word[d] < V);
+    int32_t node = 0;
+    LmTrie* e = nullptr;
+    for (int64_t j = a; j < b; ++j) {
+      LR_CHECK_ARG(dict_cls[j] >= 0 && dict_cls[j] < n_classes);
+      const uint64_t key = lm_trie_key(node, dict_cls[j]);
+      e = host_probe(tr, z.tslots - 1, key);
+      if (e->key == kLmEmpty) { e->key = key; e->child = nodes++; e->word = -1; }
+      node = e->child;
+    }
+    LR_CHECK_ARG(e->word < 0);   // two words with one spelling
+    e->word = dict_word[d];
+  }
+  return LR_OK;
+}
+
+extern "C" int lr_ctc_beam_lm_decode(const float* probs, int64_t stride_b, int64_t stride_t, const int32_t* sizes,
+                                     int log_input, int cutoff_top_n, float cutoff_prob, int beam_width, int blank,
+                                     const void* lm, const int32_t* class_roles, float alpha, float beta,
+                                     int32_t* out_ids, int32_t* out_offsets, int32_t* out_lens, float* out_scores,
+                                     void* workspace, size_t workspace_bytes, int B, int T, int C, lr_stream_t stream) {
+  LR_CHECK_ARG(probs && out_ids && out_offsets && out_lens && out_scores && workspace && lm && class_roles);
+  LR_CHECK_ARG(B > 0 && T > 0 && C > 0 && beam_width > 0 && cutoff_top_n > 0);
+  LR_CHECK_ARG(blank >= 0 && blank < C && !(cutoff_prob != cutoff_prob));
+  LR_CHECK_ARG(isfinite(alpha) && isfinite(beta));
+  if (!beam_supported(T, C, beam_width, cutoff_top_n)) return LR_ERR_UNSUPPORTED;
+  const int W = beam_width, n = cutoff_top_n;
+  if (workspace_bytes < beam_ws_bytes(B, T, n, W)) return LR_ERR_WORKSPACE;
+  const BeamWs w = beam_ws_carve(workspace, B, T, n, W);
+  const int64_t frames = (int64_t)B * T;
+  LR_LAUNCH(beam_prune_kernel, dim3((unsigned)((frames + kPruneWaves - 1) / kPruneWaves)),
+            dim3(kPruneWaves * LR_WAVE), 0, stream, probs, stride_b, stride_t, sizes, log_input, cutoff_prob,
+            w.kcls, w.klp, w.kcnt, B, T, C, n);
+  int st = lr_launch_status();
+  if (st != LR_OK) return st;
+  const LmArgs lma{static_cast<const uint8_t*>(lm), class_roles, alpha, beta};
+  LR_LAUNCH(beam_loop_kernel<true>, dim3(B), dim3(kLoopThreads), 0, stream, w.kcls, w.klp, w.kcnt, sizes, w.npar,
+            w.ncls, w.nfrm, out_ids, out_offsets, out_lens, out_scores, T, W, n, blank, C, lma);
   return lr_launch_status();
 }

@@ -8,11 +8,15 @@ compaction) and a single device->host copy of the kept ids.
 
 BeamCTCDecoder keeps the reference's constructor and `(strings, offsets)` contract, but the
 search ctcdecode runs on CPU threads after `probs.cpu()` (decoder.py:139) runs on the GPU
-(lr_ctc_beam_decode: prefix beam search without a language model) with one device->host copy.
+(lr_ctc_beam_decode: prefix beam search) with one device->host copy.  An ARPA `lm_path` adds ctcdecode's word
+language model (lr_ctc_beam_lm_decode; the reader is lipreading_amd/lm.py).
 """
+import math
+
 import torch
 
 from . import _C
+from . import lm
 
 
 def _edit_distance(a, b):
@@ -59,14 +63,19 @@ class BeamCTCDecoder(Decoder):
   """decoder.py:90-143 on lr_ctc_beam_decode.  `log_probs_input` is ctcdecode's later keyword: True when
   `probs` holds log-probabilities (VideoEncoder's output).  Classes are compared by index, as ctcdecode does:
   no canonical-label mapping.  `num_processes`, and `alpha`/`beta` without a language model, are accepted and
-  ignored, as ctcdecode ignores them."""
+  ignored, as ctcdecode ignores them.
+
+  `lm_path` ending in '.arpa' or '.arpa.gz' loads an ARPA n-gram word model (lipreading_amd/lm.py); `alpha` weighs
+  its log-probabilities and `beta` is added per word, as in ctcdecode (the specification is lr_ctc_beam.hip's).
+  Any other path, or a KenLM binary file, raises NotImplementedError.  The labels then need a ' ' and distinct
+  one-character labels (ValueError otherwise)."""
 
   def __init__(self, labels, lm_path=None, alpha=0, beta=0, cutoff_top_n=40, cutoff_prob=1.0, beam_width=100,
                num_processes=4, blank_index=0, log_probs_input=False):
     super(BeamCTCDecoder, self).__init__(labels, blank_index)
-    if lm_path is not None:
-      raise NotImplementedError("BeamCTCDecoder: lm_path=%r needs a KenLM scorer, which this package does not "
-                                "have; only lm_path=None (no language model) is supported" % (lm_path,))
+    if lm_path is not None and not lm.is_arpa_path(lm_path):
+      # decided by the name, before the file is opened
+      raise lm.kenlm_binary_error(lm_path)
     if not 0 <= blank_index < len(labels):
       raise ValueError("blank_index %d outside the %d labels" % (blank_index, len(labels)))
     if beam_width < 1 or cutoff_top_n < 1:
@@ -75,6 +84,16 @@ class BeamCTCDecoder(Decoder):
     self.cutoff_prob = float(cutoff_prob)
     self.beam_width = int(beam_width)
     self.log_probs_input = bool(log_probs_input)
+    self.lm = None
+    if lm_path is not None:
+      alpha, beta = float(alpha), float(beta)
+      if not (math.isfinite(alpha) and math.isfinite(beta)):
+        raise ValueError("alpha and beta must be finite")
+      self.alpha, self.beta = alpha, beta
+      lm.class_roles(labels, blank_index)   # the label checks come before the file is read
+      self.lm = lm.read_arpa(lm_path)
+      self._lm_blob, self._lm_roles = lm.pack(self.lm, labels, blank_index)
+      self._lm_dev = {}   # device -> (blob, roles) tensors, uploaded once per device
 
   def decode_ids(self, probs, sizes=None):
     """Device part: probs (B,T,C) -> (ids (B,W,T) int32, offsets (B,W,T) int32, lens (B,W) int32,
@@ -100,12 +119,33 @@ class BeamCTCDecoder(Decoder):
       raise _C.LipReadingHipError("lr_ctc_beam_decode: unsupported shape B=%d T=%d C=%d beam_width=%d "
                                   "cutoff_top_n=%d" % (B, T, C, W, n))
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    if self.lm is not None:
+      if C > len(self._lm_roles):
+        raise KeyError("probs has %d classes but only %d labels" % (C, len(self._lm_roles)))
+      blob, roles = self._lm_tensors(dev)
+      _C.check(L.lr_ctc_beam_lm_decode(probs.data_ptr(), probs.stride(0), probs.stride(1), _C.ptr(sz),
+                                       int(self.log_probs_input), n, self.cutoff_prob, W, self.blank_index,
+                                       blob.data_ptr(), roles.data_ptr(), self.alpha, self.beta, ids.data_ptr(),
+                                       off.data_ptr(), lens.data_ptr(), scores.data_ptr(), ws.data_ptr(), nbytes,
+                                       B, T, C, _C.stream_handle()),
+               "lr_ctc_beam_lm_decode")
+      return ids, off, lens, scores
     _C.check(L.lr_ctc_beam_decode(probs.data_ptr(), probs.stride(0), probs.stride(1), _C.ptr(sz),
                                   int(self.log_probs_input), n, self.cutoff_prob, W, self.blank_index,
                                   ids.data_ptr(), off.data_ptr(), lens.data_ptr(), scores.data_ptr(),
                                   ws.data_ptr(), nbytes, B, T, C, _C.stream_handle()),
              "lr_ctc_beam_decode")
     return ids, off, lens, scores
+
+  def _lm_tensors(self, dev):
+    """The packed model and the class roles on `dev`: one host->device copy each, the first time."""
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    got = self._lm_dev.get(key)
+    if got is None:
+      blob = torch.from_numpy(self._lm_blob).to(dev)
+      roles = torch.tensor(self._lm_roles, dtype=torch.int32, device=dev)
+      got = self._lm_dev[key] = (blob, roles)
+    return got
 
   def decode(self, probs, sizes=None):
     """decoder.py:128-143: probs (B,T,C) -> (strings, offsets); strings[b] holds beam_width strings, best

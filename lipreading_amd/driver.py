@@ -39,8 +39,9 @@ DEFAULTS = dict(  # train.py:134-167
     # layers, --nhead heads).  Either one selects the encoder+CTC loop with greedy CER (no attention decoder).
     frontend="none", encoder="rnn", nhead=4, crop_size=96,
     # the CTC decoder behind the ctc_only loop's CER: greedy (the default) or beam (decoder.BeamCTCDecoder, no
-    # language model, ctcdecode's default cutoff_top_n=40) with --beam_width hypotheses
-    ctc_decoder="greedy", beam_width=100,
+    # language model, ctcdecode's default cutoff_top_n=40) with --beam_width hypotheses; --lm_path (an ARPA
+    # file, '' = none) adds a word language model weighted by --lm_alpha, plus --lm_beta per word
+    ctc_decoder="greedy", beam_width=100, lm_path="", lm_alpha=0.0, lm_beta=0.0,
 )
 
 
@@ -116,6 +117,8 @@ def parse_flags(argv, defaults=DEFAULTS):
     raise SystemExit("--encoder must be rnn or transformer")
   if out.get("ctc_decoder") not in ("greedy", "beam"):
     raise SystemExit("--ctc_decoder must be greedy or beam")
+  if out.get("lm_path") and out.get("ctc_decoder") != "beam":
+    raise SystemExit("--lm_path needs --ctc_decoder=beam")
   if out["frontend"] != "none" or out["encoder"] != "rnn":
     # the build-defined regimes are encoder + CTC (BASELINE configs[1], [4]); no attention decoder behind them
     for name in ("enable_ctc", "ctc_only"):
@@ -257,7 +260,8 @@ def run(**flags):
   ctc_decoder = None
   if ctc_only and f["ctc_decoder"] == "beam":
     from .decoder import BeamCTCDecoder, ctc_labels
-    ctc_decoder = BeamCTCDecoder(ctc_labels(char2idx), beam_width=f["beam_width"], blank_index=0,
+    ctc_decoder = BeamCTCDecoder(ctc_labels(char2idx), lm_path=f["lm_path"] or None, alpha=f["lm_alpha"],
+                                 beta=f["lm_beta"], beam_width=f["beam_width"], blank_index=0,
                                  log_probs_input=True)
 
   def error_of(loader):

@@ -2,10 +2,12 @@
 decode() end to end with its one device->host copy and the strings) next to the float64 CPU restatement of
 tests/test_beam_cpu.py spread over a process pool.
 
-  python tools/bench_beam.py [--iters 50] [--threads 16] [--cpu-batches 1]
+  python tools/bench_beam.py [--iters 50] [--threads 16] [--cpu-batches 1] [--lm model.arpa [--alpha A --beta B]]
 
 B = 32, T = 75, C = 65 (the fallback vocabulary), model-like peaked frames; (W, n) in
-{(1,1), (8,40), (100,40), (128,64)}.  One JSON line per row and a table at the end.
+{(1,1), (8,40), (100,40), (128,64)}.  With --lm the same rows follow again with the ARPA language model
+(lr_ctc_beam_lm_decode; ctc_labels() of the fallback vocabulary, whose ' ' separates words; GPU columns only).
+One JSON line per row and a table at the end.
 """
 import argparse
 import json
@@ -43,11 +45,33 @@ def _ref_one(args):
   return beam_ref(v, T, W, n)
 
 
+def time_gpu(dec, pd, iters):
+  """(decode_ids ms by events, decode() ms by wall clock), each per batch."""
+  import torch
+  for _ in range(5):
+    dec.decode_ids(pd)
+  torch.cuda.synchronize()
+  e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+  e0.record()
+  for _ in range(iters):
+    dec.decode_ids(pd)
+  e1.record()
+  torch.cuda.synchronize()
+  gpu_ms = e0.elapsed_time(e1) / iters
+  t0 = time.perf_counter()
+  for _ in range(iters):
+    dec.decode(pd)
+  return gpu_ms, (time.perf_counter() - t0) * 1e3 / iters
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument("--iters", type=int, default=50)
   ap.add_argument("--threads", type=int, default=16)
   ap.add_argument("--cpu-batches", type=int, default=1)
+  ap.add_argument("--lm", default=None, help="an ARPA file: add rows with the language model")
+  ap.add_argument("--alpha", type=float, default=0.5)
+  ap.add_argument("--beta", type=float, default=1.0)
   a = ap.parse_args()
   import torch
   from lipreading_amd import _build
@@ -85,11 +109,31 @@ def main():
                  cpu_ref_ms=round(cpu_ms, 2), cpu_threads=a.threads)
       rows.append(row)
       print(json.dumps(row), flush=True)
+  if a.lm:
+    from lipreading_amd.data import default_char2idx
+    from lipreading_amd.decoder import ctc_labels
+    lm_labels = ctc_labels(default_char2idx())
+    assert len(lm_labels) == C
+    for W, n in SHAPES:
+      dec = BeamCTCDecoder(lm_labels, lm_path=a.lm, alpha=a.alpha, beta=a.beta, beam_width=W, cutoff_top_n=n)
+      gpu_ms, e2e_ms = time_gpu(dec, pd, a.iters)
+      row = dict(W=W, n=n, B=B, T=T, C=C, lm=os.path.basename(a.lm), lm_order=dec.lm.order,
+                 lm_ngrams=int(sum(dec.lm.counts)), gpu_decode_ids_ms=round(gpu_ms, 4),
+                 gpu_decode_ms=round(e2e_ms, 4))
+      rows.append(row)
+      print(json.dumps(row), flush=True)
   print("\n| W | n | GPU decode_ids ms | GPU decode() ms | CPU restatement ms (%d procs) |" % a.threads)
   print("|---|---|---|---|---|")
   for r in rows:
+    if "lm" in r:
+      continue
     print("| %d | %d | %.3f | %.3f | %.1f |" % (r["W"], r["n"], r["gpu_decode_ids_ms"], r["gpu_decode_ms"],
                                                r["cpu_ref_ms"]))
+  if a.lm:
+    print("\nwith the language model %s:\n| W | n | GPU decode_ids ms | GPU decode() ms |\n|---|---|---|---|" % a.lm)
+    for r in rows:
+      if "lm" in r:
+        print("| %d | %d | %.3f | %.3f |" % (r["W"], r["n"], r["gpu_decode_ids_ms"], r["gpu_decode_ms"]))
 
 
 if __name__ == "__main__":
