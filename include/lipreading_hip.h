@@ -468,6 +468,28 @@ int lr_decoder_backward_parts(int mode, int attn_type, const lr_decoder_params* 
                               size_t workspace_bytes, int accumulate, int B, int L, int T, int Hd, int Cd, int V,
                               int A, int parts, lr_stream_t stream);
 
+/* ---- A5b: beam search through the attention decoder — src/models/lipreader/analysis.py:12-66 (inference) ---- */
+/* Deterministic, batched, entirely on the device; the search rule and its two departures from the reference
+ * (top-K candidates instead of multinomial draws; PAD and BOS never candidates) are stated in
+ * lipreading_amd/csrc/lr_attn_beam.hip.  Same params / upper (drop_mask must be NULL), enc
+ * [B][T][Hd], enc_lens [B] int32 and h0 / c0 [num_layers][B][Hd] as lr_decoder_forward.
+ *   bos / eos / pad      the vocabulary's marker ids; beam_width = K, max_label_len = Lmax
+ *   poll_every           the host reads the 4-byte finished counter every poll_every rounds to stop launching
+ *                        (the results do not depend on it)
+ *   out_ids [B][K][Lmax+1] int32 (pad past each length), out_lens [B][K] int32, out_scores [B][K] fp32: the
+ *                        final beam, best first (empty slots: length 0, score -inf)
+ *   rounds_host          HOST int (may be NULL): rounds the search needed (the call then synchronises the stream)
+ * Limits: K <= 32, Lmax <= 65535, 3 <= V <= 1024, B*K <= 65535 (else LR_ERR_UNSUPPORTED; the workspace query
+ * returns 0 for every request the search rejects). */
+size_t lr_decoder_beam_workspace_bytes(int mode, int attn_type, int num_layers, int B, int K, int Lmax, int T, int Hd,
+                                       int Cd, int V, int A);
+int lr_decoder_beam_search(int mode, int attn_type, const lr_decoder_params* params_host,
+                           const lr_decoder_upper* upper_host, const float* enc, const int32_t* enc_lens,
+                           const float* h0, const float* c0, int bos, int eos, int pad, int beam_width,
+                           int max_label_len, int poll_every, int32_t* out_ids, int32_t* out_lens, float* out_scores,
+                           int32_t* rounds_host, void* workspace, size_t workspace_bytes, int B, int T, int Hd, int Cd,
+                           int V, int A, lr_stream_t stream);
+
 /* The decoder loss of the train loop (train_better_model.py:62,65): over the R = B*L (sample, step) rows,
  * -sum_r log_probs[r][label_r] for label_r != ignore_index (F.nll_loss(ignore_index=PAD, reduction='sum') summed
  * over the steps) divided by the number of such rows ((labels != PAD).sum()).  labels: int64, row (b, i) at

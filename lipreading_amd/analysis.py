@@ -1,0 +1,43 @@
+"""Beam-search transcripts from the attention decoder — `src/models/lipreader/analysis.py:12-66` (inference).
+
+The reference decodes one utterance at a time on the host, drawing each hypothesis's candidates with a multinomial.
+Here the whole batch goes through one encoder pass and one `CharDecodingStep.beam_search` call on the device, with
+the deterministic rule of lipreading_amd/csrc/lr_attn_beam.hip (top-K candidates; PAD and BOS never candidates).
+The strings keep the reference's format.  The reference's confusion-matrix plots are not ported.
+"""
+import torch
+
+from .data import BOS
+
+
+def encode_for_beam(encoder, frames, frame_lens, device):
+  """One encoder pass over the batch -> (hidden (B, T, Hd), frame_lens on the device, final_state)."""
+  max_len = int(frame_lens.max()) if not frame_lens.is_cuda else None
+  frame_lens_d = frame_lens.to(device)
+  out = encoder(frames.to(device), frame_lens_d, max_len=max_len)
+  hidden, state = (out[1], out[2]) if encoder.enable_ctc else (out[0], out[1])
+  return hidden, frame_lens_d, state
+
+
+def best_ids(decoding_step, hidden, frame_lens, state, beam_width, max_label_len):
+  """The best hypothesis of every utterance as host lists of token ids (the final EOS included when reached)."""
+  ids, lens, _ = decoding_step.beam_search(hidden, frame_lens, state, beam_width=beam_width,
+                                           max_label_len=max_label_len)
+  ids, lens = ids[:, 0].cpu(), lens[:, 0].cpu()
+  return [ids[b, :int(lens[b])].tolist() for b in range(ids.shape[0])]
+
+
+def inference(encoder, decoding_step, frames, frame_lens, chars, char_lens, device, char2idx, beam_width=5,
+              max_label_len=100):
+  """analysis.py:12-66.  Returns (outputs, gt): outputs[i] = '<BOS>' + the best hypothesis's characters (with
+  '<EOS>' if it reached one), gt[i] = chars[i][:char_lens[i]] joined."""
+  idx2char = {val: key for key, val in char2idx.items()}
+  encoder.eval()
+  decoding_step.eval()
+  with torch.no_grad():
+    hidden, lens_d, state = encode_for_beam(encoder, frames, frame_lens, device)
+    best = best_ids(decoding_step, hidden, lens_d, state, beam_width, max_label_len)
+  outputs = [''.join(idx2char[int(i)] for i in [char2idx[BOS]] + h) for h in best]
+  chars, char_lens = chars.cpu(), char_lens.cpu()
+  gt = [''.join(idx2char[int(c)] for c in chars[i][:int(char_lens[i])]) for i in range(len(best))]
+  return outputs, gt

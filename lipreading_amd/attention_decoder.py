@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _C
-from .data import BOS, PAD
+from .data import BOS, EOS, PAD
 from .encoder import _RNNParams, _direct_grads, _notify
 
 _ALLOWED_ATTENTION_TYPES = {'none', 'dot', 'general', '1_layer_nn', 'concat'}   # better_model.py:11
@@ -318,6 +318,63 @@ class CharDecodingStep(nn.Module):
         *self._params())
     final_state = (h_n, c_n) if mode == 1 else h_n
     return lp, sampled, final_state
+
+  def beam_search(self, encoder_hidden_states, encoder_lens, previous_state, beam_width=10, max_label_len=100,
+                  poll_every=8):
+    """Deterministic beam search through this decoder for every utterance of the batch at once, entirely on the
+    device (lr_decoder_beam_search; the rule is in lipreading_amd/csrc/lr_attn_beam.hip and DESIGN.md §14; the
+    reference's analysis.py:12-66 inference() does it one utterance at a time with sampled candidates).
+
+    encoder_hidden_states (B, T, Hd), encoder_lens (B,), previous_state as for decode_sequence.  Returns device
+    tensors (ids (B, K, max_label_len + 1) int32, lens (B, K) int32, scores (B, K) float32): the final beam, best
+    first; ids past lens[b, k] are PAD, and each hypothesis ends with EOS unless it hit the cap.  `poll_every`
+    (how often the host checks whether every utterance has finished) changes nothing in the result.  The number of
+    rounds the search needed is left in `self.beam_rounds`."""
+    K, Lmax = beam_width, max_label_len
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= 32:
+      raise ValueError("beam_width must be an int in [1, 32], got %r" % (K,))
+    if isinstance(Lmax, bool) or not isinstance(Lmax, int) or not 1 <= Lmax <= 65535:
+      raise ValueError("max_label_len must be an int in [1, 65535], got %r" % (Lmax,))
+    if isinstance(poll_every, bool) or not isinstance(poll_every, int) or poll_every < 1:
+      raise ValueError("poll_every must be a positive int, got %r" % (poll_every,))
+    states = list(previous_state) if isinstance(previous_state, tuple) else [previous_state]
+    for t in [encoder_hidden_states] + states:
+      if not (torch.is_tensor(t) and t.is_cuda):
+        raise ValueError("beam_search runs on the GPU: encoder states and previous_state must be device tensors")
+    L_ = _C.lib()
+    mode = _MODES[self.rnn_type]
+    enc = encoder_hidden_states.detach().to(torch.float32).contiguous()
+    dev = enc.device
+    B, T, Hd = enc.shape
+    h0 = states[0].detach().contiguous()
+    c0 = states[1].detach().contiguous() if mode == 1 else None
+    if h0.shape != (self.num_layers, B, Hd):
+      raise ValueError("previous_state must be (num_layers, B, hidden), got %s" % (tuple(h0.shape),))
+    enc_lens = encoder_lens.to(device=dev, dtype=torch.int32).contiguous()
+    params = self._params()
+    pstruct = _C.DecoderParams(*[_C.ptr(p) for p in params[:13]], self.output_mask.data_ptr())
+    ustruct, NL = _upper_struct(params[13:], None)
+    V, Cd = self.vocab_size, self.char_dim
+    A = max(int(self.attn_hidden_size), 0)
+    at = _ATT_CODE[self.attention_type]
+    wbytes = L_.lr_decoder_beam_workspace_bytes(mode, at, NL, B, K, Lmax, T, Hd, Cd, V, A)
+    if wbytes == 0:
+      raise ValueError("beam search does not support this shape (B=%d, K=%d, max_label_len=%d, V=%d, Hd=%d)"
+                       % (B, K, Lmax, V, Hd))
+    ws = torch.empty(wbytes, dtype=torch.uint8, device=dev)
+    ids = torch.empty((B, K, Lmax + 1), dtype=torch.int32, device=dev)
+    lens = torch.empty((B, K), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, K), dtype=torch.float32, device=dev)
+    rounds = ctypes.c_int32(0)
+    c2i = self.char2idx
+    _C.check(L_.lr_decoder_beam_search(mode, at, ctypes.byref(pstruct),
+                                       ctypes.byref(ustruct) if ustruct is not None else None, enc.data_ptr(),
+                                       enc_lens.data_ptr(), h0.data_ptr(), _C.ptr(c0), c2i[BOS], c2i[EOS], c2i[PAD],
+                                       K, Lmax, poll_every, ids.data_ptr(), lens.data_ptr(), scores.data_ptr(),
+                                       ctypes.byref(rounds), ws.data_ptr(), wbytes, B, T, Hd, Cd, V, A,
+                                       _C.stream_handle()), "lr_decoder_beam_search")
+    self.beam_rounds = int(rounds.value)
+    return ids, lens, scores
 
   def forward(self, input_, previous_state, encoder_lens, encoder_hidden_states):
     """One step, reference contract (better_model.py:161-231): input_ (B,), previous_state

@@ -1,0 +1,529 @@
+// lr_attn_beam.hip — deterministic beam search through the attention decoder on gfx950.
+//
+// Reference capability replaced here (paths under the reference root):
+//   src/models/lipreader/analysis.py:12-66  inference(): a beam search through CharDecodingStep that stops
+//       at EOS, one utterance at a time on the host, one decoding_step call per candidate;
+//   src/scripts/train.py:323-331            its use ("student-forcing outputs with beam search", beam_width
+//       10, max_label_len 100).
+//
+// Specification (per utterance b, beam width K, cap Lmax = max_label_len):
+//   * A hypothesis is (history, state, score).  The start beam holds one: empty history, the encoder's final
+//     state for b (every decoder layer's h, plus c for the LSTM), score 0.
+//   * A hypothesis is finished when its last token is EOS, or when len(history) == Lmax + 1 (the reference's
+//     len(history) > max_label_len).
+//   * One round works through the beam in order, building a list:
+//       - an unfinished hypothesis runs one CharDecodingStep step on its last token (BOS if the history is
+//         empty) from its state, attending over b's encoder states masked by enc_lens[b].  That gives lp (the
+//         masked log-softmax, V entries) and a new state.  Its candidates are the min(K, V - 2) tokens with the
+//         largest lp, PAD and BOS excluded, listed by lp descending with ties to the lower id; each has score
+//         score + lp[v] and the new state;
+//       - a finished hypothesis contributes itself, unchanged, at its place in the list.
+//     The new beam is the first K entries of the list after a STABLE sort by score, descending.
+//     (Scores are carried in float64 on the device: a float32 running sum of ~100 log-probabilities loses ~1e-4.)
+//   * The search stops when every hypothesis of the beam is finished: at most Lmax + 1 rounds.
+//   * The result is the beam in order, best first: each entry's tokens (the final EOS included when it has
+//     one), their count and its score — a plain sum of log-probabilities, no length normalisation.  Slots past
+//     the beam's size (only when fewer than K complete hypotheses exist) have length 0 and score -inf.
+// Departures from the reference:
+//   1. The reference draws each hypothesis's beam_width candidates with multinomial(replacement=False); here
+//      they are the top K, which makes the result reproducible and testable.
+//   2. PAD and BOS are never candidates (the reference gives them weight ~1e-45 after masked_log_softmax).
+//
+// Structure.  Every beam row stays resident: R = B*K rows (row = b*K + k), dead or finished rows masked, so
+// every shape is static.  One round is
+//   * the step pieces of lr_decoder.hip at one step (lr_decoder_dev.h): the EW-table gather by each row's
+//     input token; per layer lr_rnn_step_fwd run as step 0 from the rows' current state (packed into the
+//     step kernel's slot by lr_rnn_pack_state), with the upper layers' W_ih GEMM; the attention as
+//     lr_sgemm_batched_impl over batch = B with M = K (the beams stand where the steps stand in training), so
+//     enc and the step-independent halves (GE, cE / se, PE) stay per utterance and are never copied K times;
+//     the concat GEMMs; the output head without the multinomial draw;
+//   * beam_select_kernel, one workgroup per utterance: the per-beam top-K over V, then the stable sort of the
+//     <= K*K list by rank counting in LDS; it writes each new slot's parent, token, score, length and finished
+//     flag, its history row (double-buffered, and the caller's out_ids row), the next round's input token,
+//     and counts the utterance into the finished counter once all its hypotheses are finished;
+//   * beam_reorder_kernel: every layer's h (and c) gathered by parent for the next round.
+// The search never waits for the host.  Both new kernels of an utterance whose hypotheses are all finished
+// return at once (a round of such an utterance changes nothing, by the rule), so the host may launch rounds
+// past the end: it reads the finished counter (4 bytes) every `poll_every` rounds and stops launching when all
+// B utterances are finished.  The results do not depend on poll_every.
+//
+// Limits (LR_ERR_UNSUPPORTED, workspace query 0): 1 <= K <= 32, 1 <= Lmax <= 65535, 3 <= V <= 1024,
+// B * K <= 65535, the head's and the concat attention's LDS as in lr_decoder_forward; every RNN mode, every
+// attention type, 1 .. LR_DEC_MAX_LAYERS layers.
+#include "lr_common.h"
+#include "lr_decoder_dev.h"
+
+namespace {
+
+constexpr int BEAM_MAX_K = 32;
+constexpr int BEAM_MAX_V = 1024;
+constexpr int BEAM_MAX_LMAX = 65535;
+constexpr int MAXL = LR_DEC_MAX_LAYERS;
+constexpr int SEL_THREADS = 256;
+constexpr int VPL = BEAM_MAX_V / 64;   // vocabulary entries per lane in the top-K scan
+
+// per-utterance words of the search: history buffer in use, all-finished flag, rounds run
+enum { U_CUR = 0, U_DONE = 1, U_ROUNDS = 2, U_WORDS = 4 };
+
+inline int gates_of(int mode) { return mode == LR_RNN_GRU ? 3 : (mode == LR_RNN_LSTM ? 4 : 1); }
+
+struct Sizes {
+  int B, K, LH, T, Hd, Cd, V, A, G, type, NL;   // LH = Lmax + 1: history capacity
+};
+
+// ---- workspace layout, in 4-byte words ------------------------------------------------------------------------
+struct Ws {
+  size_t EW, biasf[MAXL], wp[MAXL], hp[MAXL], gates[MAXL], extra[MAXL], y[MAXL], hcur[MAXL], ccur[MAXL];
+  size_t ones, ids_used, logits, wts, ctx, pre, aux1, aux2, ph, lp;
+  size_t score, len, fin, live, next_in, parent, hist, ustate, ctr, gemm, total;
+  size_t hp_slot, gemm_bytes;
+};
+
+Ws ws_layout(const Sizes& z) {
+  Ws w;
+  const size_t R = (size_t)z.B * z.K, GH = (size_t)z.G * z.Hd, BT = (size_t)z.B * z.T;
+  const bool attn = z.type != ATT_NONE;
+  size_t o = 0;
+  auto take = [&](size_t n) { size_t at = o; o += (n + 63) / 64 * 64; return at; };
+  w.EW = take((size_t)z.V * GH);
+  w.hp_slot = lr_rnn_packed_state_floats((int)R, z.Hd);
+  for (int k = 0; k < MAXL; ++k)
+    w.biasf[k] = w.wp[k] = w.hp[k] = w.gates[k] = w.extra[k] = w.y[k] = w.hcur[k] = w.ccur[k] = 0;
+  for (int k = 0; k < z.NL; ++k) {
+    w.biasf[k] = take(GH);
+    w.wp[k] = take(lr_rnn_packed_w_floats(z.G, z.Hd));
+    w.hp[k] = take(2 * w.hp_slot);
+    w.gates[k] = take(R * GH);
+    w.extra[k] = take(R * z.Hd);
+    w.y[k] = take(R * z.Hd);
+    w.hcur[k] = take(R * z.Hd);
+    w.ccur[k] = take(z.G == 4 ? R * z.Hd : 0);
+  }
+  w.ones = take(R);
+  w.ids_used = take(R);
+  w.logits = take(attn ? R * z.T : 0);
+  w.wts = take(attn ? R * z.T : 0);
+  w.ctx = take(attn ? R * z.Hd : 0);
+  w.pre = take(attn ? R * z.Hd : 0);
+  w.aux1 = take(z.type == ATT_GENERAL ? BT * z.Hd : (z.type == ATT_CONCAT ? BT * z.A : 0));   // GE | PE
+  w.aux2 = take((z.type == ATT_GENERAL || z.type == ATT_1LNN) ? BT : 0);                       // cE | se
+  w.ph = take(z.type == ATT_CONCAT ? R * z.A : 0);
+  w.lp = take(R * z.V);
+  w.score = take(2 * R);   // double
+  w.len = take(R);
+  w.fin = take(R);
+  w.live = take(R);
+  w.next_in = take(R);
+  w.parent = take(R);
+  w.hist = take(2 * R * z.LH);
+  w.ustate = take((size_t)z.B * U_WORDS);
+  w.ctr = take(2);   // {utterances finished, rounds run}
+  const int a = z.A > 0 ? z.A : 1;
+  const int dims[][3] = {{z.V, (int)GH, z.Cd}, {(int)BT, z.Hd, z.Hd}, {(int)BT, a, z.Hd}, {(int)R, z.Hd, z.Hd},
+                         {(int)R, a, z.Hd}, {(int)R, (int)GH, z.Hd}};
+  w.gemm_bytes = 0;
+  for (const auto& d : dims) {
+    const size_t g = lr_sgemm_workspace_bytes(d[0], d[1], d[2]);
+    if (g > w.gemm_bytes) w.gemm_bytes = g;
+  }
+  w.gemm = take((w.gemm_bytes + 3) / 4);
+  w.total = o;
+  return w;
+}
+
+// rows of the output head per workgroup (lr_decoder_forward's rule); 0 when even one row does not fit
+int head_rows(int Hd, int V) {
+  int rows = OUT_ROWS;
+  while (rows > 1 && (size_t)rows * (Hd + V) * sizeof(float) > 60 * 1024) rows >>= 1;
+  return (size_t)rows * (Hd + V) * sizeof(float) > 60 * 1024 ? 0 : rows;
+}
+
+bool sizes_ok(int mode, int type, int NL, int B, int K, int Lmax, int T, int Hd, int Cd, int V, int A) {
+  return (mode == LR_RNN_GRU || mode == LR_RNN_LSTM || mode == LR_RNN_TANH) && type >= ATT_NONE &&
+         type <= ATT_CONCAT && NL >= 1 && NL <= MAXL && B > 0 && K >= 1 && K <= BEAM_MAX_K &&
+         (int64_t)B * K <= 65535 && Lmax >= 1 && Lmax <= BEAM_MAX_LMAX && T > 0 && Hd > 0 && Hd % 4 == 0 &&
+         Cd > 0 && V >= 3 && V <= BEAM_MAX_V && (type != ATT_CONCAT || (A > 0 && (size_t)2 * A * 4 <= 60 * 1024)) &&
+         head_rows(Hd, V) > 0;
+}
+
+// dst[b*K + k][:] = src[b][:] for every k (the start state of every row of utterance b)
+__global__ void beam_bcast_kernel(const float* __restrict__ src, float* __restrict__ dst, int K, int Hd) {
+  const int r = blockIdx.x, b = r / K;
+  const float4* s = reinterpret_cast<const float4*>(src + (int64_t)b * Hd);
+  float4* d = reinterpret_cast<float4*>(dst + (int64_t)r * Hd);
+  for (int c = threadIdx.x; c < Hd / 4; c += blockDim.x) d[c] = s[c];
+}
+
+// the start beam: row b*K holds (empty history, score 0); rows b*K + 1 .. are empty slots
+__global__ void beam_init_kernel(double* score, int32_t* len, int32_t* fin, int32_t* live, int32_t* next_in,
+                                 int32_t* parent, int32_t* ones, int32_t* ustate, int32_t* ctr, int R, int K, int bos) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r == 0) ctr[0] = ctr[1] = 0;
+  if (r >= R) return;
+  const int k = r % K;
+  score[r] = 0.0;
+  len[r] = 0;
+  fin[r] = 0;
+  live[r] = k == 0;
+  next_in[r] = bos;
+  parent[r] = r;
+  ones[r] = 1;
+  if (k == 0) {
+    int32_t* u = ustate + (int64_t)(r / K) * U_WORDS;
+    u[U_CUR] = 0;
+    u[U_DONE] = 0;
+    u[U_ROUNDS] = 0;
+  }
+}
+
+template <typename S>
+__device__ __forceinline__ bool ranks_before(S sa, int ia, S sb, int ib) {
+  return sa > sb || (sa == sb && ia < ib);
+}
+
+// One workgroup per utterance: the rule's round after the step pieces left each row's lp [R][V].
+// Entry e = k*Kc + c of the round's list is candidate c of row k (c = 0 only for a finished row, which
+// contributes itself); e is also the entry's place in the list, so the stable sort is a sort by (score desc, e).
+__global__ __launch_bounds__(SEL_THREADS) void beam_select_kernel(
+    const float* __restrict__ lp, double* __restrict__ score, int32_t* __restrict__ len, int32_t* __restrict__ fin,
+    int32_t* __restrict__ live, int32_t* __restrict__ next_in, int32_t* __restrict__ parent,
+    int32_t* __restrict__ hist, int32_t* __restrict__ ustate, int32_t* __restrict__ ctr, int32_t* __restrict__ out_ids,
+    int32_t* __restrict__ out_lens, float* __restrict__ out_scores, int K, int Kc, int V, int LH, int bos, int eos,
+    int pad) {
+  __shared__ double e_score[BEAM_MAX_K * BEAM_MAX_K];
+  __shared__ int e_tok[BEAM_MAX_K * BEAM_MAX_K];   // token; -1 = a finished hypothesis carried over; -2 = no entry
+  __shared__ double o_score[BEAM_MAX_K];
+  __shared__ int o_len[BEAM_MAX_K], o_state[BEAM_MAX_K];   // o_state: 0 empty slot, 1 unfinished, 2 finished
+  __shared__ int sel[BEAM_MAX_K];
+  __shared__ int n_sel, all_fin;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int32_t* u = ustate + (int64_t)b * U_WORDS;
+  if (u[U_DONE]) return;   // (uniform) every hypothesis finished: a round changes nothing
+  const int r0 = b * K;
+  const int NE = K * Kc;
+  if (tid < K) {
+    o_score[tid] = score[r0 + tid];
+    o_len[tid] = len[r0 + tid];
+    o_state[tid] = live[r0 + tid] ? (fin[r0 + tid] ? 2 : 1) : 0;
+    sel[tid] = -1;
+  }
+  if (tid == 0) n_sel = 0;
+  for (int e = tid; e < NE; e += SEL_THREADS) e_tok[e] = -2;
+  __syncthreads();
+
+  // candidates: one wave per row, Kc rounds of a wave argmax over the row's unused entries
+  for (int k = wave; k < K; k += SEL_THREADS / 64) {
+    const int st = o_state[k];
+    if (st == 0) continue;
+    if (st == 2) {
+      if (lane == 0) { e_tok[k * Kc] = -1; e_score[k * Kc] = o_score[k]; }
+      continue;
+    }
+    const float* row = lp + (int64_t)(r0 + k) * V;
+    float val[VPL];
+    unsigned avail = 0;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      const int v = lane + 64 * i;
+      const bool ok = v < V && v != pad && v != bos;
+      val[i] = ok ? row[v] : LR_NEG_INF;
+      if (ok) avail |= 1u << i;
+    }
+    for (int c = 0; c < Kc; ++c) {
+      float bv = LR_NEG_INF;
+      int bi = 0x7fffffff;
+#pragma unroll
+      for (int i = 0; i < VPL; ++i)
+        if (((avail >> i) & 1u) && ranks_before(val[i], lane + 64 * i, bv, bi)) { bv = val[i]; bi = lane + 64 * i; }
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const float ov = __shfl_xor(bv, d, 64);
+        const int oi = __shfl_xor(bi, d, 64);
+        if (ranks_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+      }
+      if (bi == 0x7fffffff) break;   // (uniform) fewer than Kc tokens left: cannot happen with Kc <= V - 2
+      if ((bi & 63) == lane) avail &= ~(1u << (bi >> 6));
+      if (lane == 0) { e_tok[k * Kc + c] = bi; e_score[k * Kc + c] = o_score[k] + (double)bv; }
+    }
+  }
+  __syncthreads();
+
+  // stable sort, first K: an entry's rank is the count of entries before it in (score desc, place asc)
+  for (int e = tid; e < NE; e += SEL_THREADS) {
+    if (e_tok[e] == -2) continue;
+    const double s = e_score[e];
+    int rank = 0;
+    for (int f = 0; f < NE && rank < K; ++f)
+      if (e_tok[f] != -2 && ranks_before(e_score[f], f, s, e)) ++rank;
+    if (rank < K) { sel[rank] = e; atomicAdd(&n_sel, 1); }
+  }
+  __syncthreads();
+
+  // the new beam: slot s takes entry sel[s]
+  const int nsel = n_sel;
+  const int cur = u[U_CUR];
+  const int32_t* hin = hist + ((int64_t)cur * gridDim.x + b) * K * LH;
+  int32_t* hout = hist + ((int64_t)(cur ^ 1) * gridDim.x + b) * K * LH;
+  int32_t* oid = out_ids + (int64_t)b * K * LH;
+  for (int idx = tid; idx < K * LH; idx += SEL_THREADS) {
+    const int s = idx / LH, t = idx - s * LH;
+    int v = pad;
+    if (s < nsel) {
+      const int e = sel[s], k = e / Kc, tok = e_tok[e];
+      const int l0 = o_len[k];
+      if (t < l0) v = hin[k * LH + t];
+      else if (t == l0 && tok >= 0) v = tok;
+    }
+    hout[idx] = v;
+    oid[idx] = v;
+  }
+  if (tid == 0) all_fin = 1;
+  __syncthreads();
+  if (tid < K) {
+    const int s = tid, r = r0 + s;
+    if (s < nsel) {
+      const int e = sel[s], k = e / Kc, tok = e_tok[e];
+      const int nl = o_len[k] + (tok >= 0 ? 1 : 0);
+      const bool f = tok < 0 || tok == eos || nl == LH;
+      score[r] = e_score[e];
+      len[r] = nl;
+      fin[r] = f;
+      live[r] = 1;
+      next_in[r] = tok >= 0 ? tok : bos;
+      parent[r] = r0 + k;
+      out_lens[r] = nl;
+      out_scores[r] = (float)e_score[e];
+      if (!f) atomicAnd(&all_fin, 0);
+    } else {
+      score[r] = -__builtin_inf();
+      len[r] = 0;
+      fin[r] = 1;
+      live[r] = 0;
+      next_in[r] = bos;
+      parent[r] = r;
+      out_lens[r] = 0;
+      out_scores[r] = LR_NEG_INF;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    u[U_CUR] = cur ^ 1;
+    const int rounds = u[U_ROUNDS] + 1;
+    u[U_ROUNDS] = rounds;
+    atomicMax(&ctr[1], rounds);
+    if (all_fin) {
+      u[U_DONE] = 1;
+      atomicAdd(&ctr[0], 1);
+    }
+  }
+}
+
+struct StatePtrs {
+  const float* y[MAXL];    // each layer's new h [R][Hd] (the step's output)
+  const float* yc[MAXL];   // each layer's new c (LSTM) or NULL
+  float* h[MAXL];          // each layer's state for the next round
+  float* c[MAXL];
+};
+
+// next round's state of row r = the new state of its parent.  grid (R, NL)
+__global__ void beam_reorder_kernel(StatePtrs q, const int32_t* __restrict__ parent,
+                                    const int32_t* __restrict__ ustate, int K, int Hd) {
+  const int r = blockIdx.x, k = blockIdx.y;
+  if (ustate[(int64_t)(r / K) * U_WORDS + U_DONE]) return;
+  const int64_t src = (int64_t)parent[r] * Hd, dst = (int64_t)r * Hd;
+  for (int c = threadIdx.x; c < Hd / 4; c += blockDim.x) {
+    reinterpret_cast<float4*>(q.h[k] + dst)[c] = reinterpret_cast<const float4*>(q.y[k] + src)[c];
+    if (q.c[k]) reinterpret_cast<float4*>(q.c[k] + dst)[c] = reinterpret_cast<const float4*>(q.yc[k] + src)[c];
+  }
+}
+
+#define LR_TRY(expr)                \
+  do {                              \
+    const int st__ = (expr);        \
+    if (st__ != LR_OK) return st__; \
+  } while (0)
+
+}  // namespace
+
+extern "C" size_t lr_decoder_beam_workspace_bytes(int mode, int attn_type, int num_layers, int B, int K, int Lmax,
+                                                  int T, int Hd, int Cd, int V, int A) {
+  if (!sizes_ok(mode, attn_type, num_layers, B, K, Lmax, T, Hd, Cd, V, A)) return 0;
+  const Sizes z = {B, K, Lmax + 1, T, Hd, Cd, V, A, gates_of(mode), attn_type, num_layers};
+  return ws_layout(z).total * 4;
+}
+
+extern "C" int lr_decoder_beam_search(int mode, int attn_type, const lr_decoder_params* p, const lr_decoder_upper* up,
+                                      const float* enc, const int32_t* enc_lens, const float* h0, const float* c0,
+                                      int bos, int eos, int pad, int beam_width, int max_label_len, int poll_every,
+                                      int32_t* out_ids, int32_t* out_lens, float* out_scores, int32_t* rounds_host,
+                                      void* workspace, size_t workspace_bytes, int B, int T, int Hd, int Cd, int V,
+                                      int A, lr_stream_t stream_) {
+  const int NL = up ? up->num_layers : 1;
+  const int K = beam_width, Lmax = max_label_len;
+  if (!sizes_ok(mode, attn_type, NL, B, K, Lmax, T, Hd, Cd, V, A)) {
+    // a well-formed request the kernels do not cover is UNSUPPORTED; nonsense is INVALID_ARG
+    const bool sane = B > 0 && T > 0 && Hd > 0 && Cd > 0 && V > 0 && K > 0 && Lmax > 0 && NL >= 1;
+    return sane ? LR_ERR_UNSUPPORTED : LR_ERR_INVALID_ARG;
+  }
+  LR_CHECK_ARG(p && enc && enc_lens && h0 && out_ids && out_lens && out_scores && workspace && poll_every >= 1);
+  LR_CHECK_ARG(p->emb && p->w_ih && p->w_hh && p->b_ih && p->b_hh && p->w_o && p->b_o && p->out_mask);
+  LR_CHECK_ARG(attn_type == ATT_NONE || (p->w_c && p->b_c));
+  LR_CHECK_ARG(mode != LR_RNN_LSTM || c0);
+  LR_CHECK_ARG(!up || !up->drop_mask);   // inference: no inter-layer dropout
+  for (int k = 1; k < NL; ++k) LR_CHECK_ARG(up->w_ih[k - 1] && up->w_hh[k - 1] && up->b_ih[k - 1] && up->b_hh[k - 1]);
+  LR_CHECK_ARG(bos >= 0 && bos < V && eos >= 0 && eos < V && pad >= 0 && pad < V && bos != pad && eos != bos &&
+               eos != pad);
+  if (attn_type == ATT_GENERAL || attn_type == ATT_1LNN) LR_CHECK_ARG(p->attn_w1 && p->attn_b1);
+  if (attn_type == ATT_CONCAT) LR_CHECK_ARG(p->attn_w1 && p->attn_b1 && p->attn_w2 && p->attn_b2);
+  const Sizes z = {B, K, Lmax + 1, T, Hd, Cd, V, A, gates_of(mode), attn_type, NL};
+  const Ws w = ws_layout(z);
+  if (workspace_bytes < w.total * 4) return LR_ERR_WORKSPACE;
+  hipStream_t stream = (hipStream_t)stream_;
+  float* base = (float*)workspace;
+  auto I = [&](size_t off) { return (int32_t*)(base + off); };
+  const int G = z.G, GH = G * Hd, R = B * K, LH = Lmax + 1, Kc = K < V - 2 ? K : V - 2;
+  const bool attn = attn_type != ATT_NONE;
+  const size_t state = (size_t)B * Hd;
+  const float* w_hh[MAXL];
+  const float* w_ihu[MAXL];
+  const float* b_hhl[MAXL];
+  const float* b_ihl[MAXL];
+  for (int k = 0; k < NL; ++k) {
+    w_hh[k] = k == 0 ? p->w_hh : up->w_hh[k - 1];
+    w_ihu[k] = k == 0 ? nullptr : up->w_ih[k - 1];
+    b_ihl[k] = k == 0 ? p->b_ih : up->b_ih[k - 1];
+    b_hhl[k] = k == 0 ? p->b_hh : up->b_hh[k - 1];
+  }
+  void* gws = base + w.gemm;
+  float* top = base + w.y[NL - 1];   // the top layer's new states: what the attention and the head read
+  float* logits = base + w.logits;
+  float* wts = base + w.wts;
+  float* ctx = base + w.ctx;
+  float* pre = base + w.pre;
+  float* ph = base + w.ph;
+  float* lp = base + w.lp;
+  int32_t* ctr = I(w.ctr);
+  const int out_rows = head_rows(Hd, V);
+  const size_t out_lds = (size_t)out_rows * (Hd + V) * sizeof(float);
+
+  // ---- prologue: weights in the step kernels' forms, the start beam, the step-independent attention halves ----
+  for (int k = 0; k < NL; ++k) {
+    LR_TRY(lr_rnn_fold_bias(b_ihl[k], b_hhl[k], base + w.biasf[k], G, Hd, stream));
+    LR_TRY(lr_rnn_pack_w(w_hh[k], base + w.wp[k], G, Hd, 0, stream));
+    lr_clear_error();
+    if (hipMemsetAsync(base + w.hp[k], 0, 2 * w.hp_slot * sizeof(float), stream) != hipSuccess) return LR_ERR_LAUNCH;
+    LR_LAUNCH(beam_bcast_kernel, dim3(R), dim3(256), 0, stream, h0 + k * state, base + w.hcur[k], K, Hd);
+    LR_TRY(lr_launch_status());
+    if (G == 4) {
+      LR_LAUNCH(beam_bcast_kernel, dim3(R), dim3(256), 0, stream, c0 + k * state, base + w.ccur[k], K, Hd);
+      LR_TRY(lr_launch_status());
+    }
+  }
+  LR_LAUNCH(beam_init_kernel, dim3((R + 255) / 256), dim3(256), 0, stream, (double*)(base + w.score), I(w.len), I(w.fin),
+            I(w.live), I(w.next_in), I(w.parent), I(w.ones), I(w.ustate), ctr, R, K, bos);
+  LR_TRY(lr_launch_status());
+  LR_TRY(lr_sgemm_impl(0, 1, V, GH, Cd, 1.f, p->emb, Cd, p->w_ih, Cd, 0.f, base + w.EW, GH, base + w.biasf[0], 0, 0,
+                       gws, w.gemm_bytes, stream));
+  const int BT = B * T;
+  const float* src = nullptr;     // dot: enc; general: GE = enc W_g        [B][T][Hd]
+  const float* cterm = nullptr;   // general: cE = enc . b_g; 1_layer_nn: se = enc . w_e   [B][T]
+  if (attn_type == ATT_DOT) {
+    src = enc;
+  } else if (attn_type == ATT_GENERAL) {
+    LR_TRY(lr_sgemm_impl(0, 0, BT, Hd, Hd, 1.f, enc, Hd, p->attn_w1, Hd, 0.f, base + w.aux1, Hd, nullptr, 0, 0, gws,
+                         w.gemm_bytes, stream));
+    LR_TRY(lr_sgemm_impl(0, 1, BT, 1, Hd, 1.f, enc, Hd, p->attn_b1, Hd, 0.f, base + w.aux2, 1, nullptr, 0, 0, nullptr,
+                         0, stream));
+    src = base + w.aux1;
+    cterm = base + w.aux2;
+  } else if (attn_type == ATT_1LNN) {
+    LR_TRY(lr_sgemm_impl(0, 1, BT, 1, Hd, 1.f, enc, Hd, p->attn_w1, 2 * Hd, 0.f, base + w.aux2, 1, nullptr, 0, 0,
+                         nullptr, 0, stream));
+    cterm = base + w.aux2;
+  } else if (attn_type == ATT_CONCAT) {
+    LR_TRY(lr_sgemm_impl(0, 1, BT, A, Hd, 1.f, enc, Hd, p->attn_w1, 2 * Hd, 0.f, base + w.aux1, A, p->attn_b1, 0, 0,
+                         gws, w.gemm_bytes, stream));
+  }
+  StatePtrs sp;
+  for (int k = 0; k < MAXL; ++k) {
+    const bool on = k < NL;
+    sp.y[k] = on ? base + w.y[k] : nullptr;
+    sp.yc[k] = on && G == 4 ? base + w.extra[k] : nullptr;
+    sp.h[k] = on ? base + w.hcur[k] : nullptr;
+    sp.c[k] = on && G == 4 ? base + w.ccur[k] : nullptr;
+  }
+
+  // ---- one round ----
+  auto round = [&]() -> int {
+    LR_LAUNCH(dec_gather_kernel, dim3(1, R), dim3(256), 0, stream, (const float*)(base + w.EW),
+              (const int32_t*)I(w.next_in), (const int32_t*)I(w.next_in), I(w.ids_used), base + w.gates[0], 1, GH, V,
+              0, 1);
+    LR_TRY(lr_launch_status());
+    for (int k = 0; k < NL; ++k) {
+      if (k > 0)
+        LR_TRY(lr_sgemm_impl(0, 1, R, GH, Hd, 1.f, base + w.y[k - 1], Hd, w_ihu[k], Hd, 0.f, base + w.gates[k], GH,
+                             base + w.biasf[k], 0, 0, gws, w.gemm_bytes, stream));
+      // step 0 of a one-step sequence from the rows' current state: the kernel reads the state's packed copy
+      // from parity slot 1 and h0 / c0 = the unpacked state
+      LR_TRY(lr_rnn_pack_state(base + w.hcur[k], base + w.hp[k] + w.hp_slot, R, Hd, stream));
+      LR_TRY(lr_rnn_step_fwd(G, base + w.gates[k], base + w.extra[k], base + w.y[k], base + w.hp[k], I(w.ones),
+                             base + w.wp[k], b_hhl[k], base + w.hcur[k], G == 4 ? base + w.ccur[k] : nullptr, R, 1,
+                             Hd, 0, stream));
+    }
+    if (attn) {
+      if (attn_type == ATT_DOT || attn_type == ATT_GENERAL) {
+        // logits[b] (K x T) = top[b] (K x Hd) . src[b]^T
+        LR_TRY(lr_sgemm_batched_impl(0, 1, K, T, Hd, 1.f, top, Hd, (int64_t)K * Hd, src, Hd, (int64_t)T * Hd, 0.f,
+                                     logits, T, (int64_t)K * T, nullptr, B, stream));
+      } else if (attn_type == ATT_CONCAT) {
+        LR_TRY(lr_sgemm_impl(0, 1, R, A, Hd, 1.f, top, Hd, p->attn_w1 + Hd, 2 * Hd, 0.f, ph, A, nullptr, 0, 0, gws,
+                             w.gemm_bytes, stream));   // ph = W1h h
+        LR_LAUNCH(dec_concat_logits_kernel, dim3(K, B), dim3(256), (size_t)2 * A * sizeof(float), stream,
+                  (const float*)(base + w.aux1), (const float*)ph, p->attn_w2, p->attn_b2, logits, K, T, A, 0);
+        LR_TRY(lr_launch_status());
+      }
+      LR_LAUNCH(dec_attn_softmax_kernel, dim3(K, B), dim3(64), 0, stream, attn_type, (const float*)top, enc_lens,
+                cterm, attn_type == ATT_1LNN ? p->attn_w1 + Hd : (const float*)nullptr,
+                attn_type == ATT_1LNN ? p->attn_b1 : (const float*)nullptr, logits, wts, K, T, Hd, 0);
+      LR_TRY(lr_launch_status());
+      // ctx[b] (K x Hd) = wts[b] (K x T) . enc[b] (T x Hd)
+      LR_TRY(lr_sgemm_batched_impl(0, 0, K, Hd, T, 1.f, wts, T, (int64_t)K * T, enc, Hd, (int64_t)T * Hd, 0.f, ctx,
+                                   Hd, (int64_t)K * Hd, nullptr, B, stream));
+      LR_TRY(lr_sgemm_impl(0, 1, R, Hd, Hd, 1.f, ctx, Hd, p->w_c, 2 * Hd, 0.f, pre, Hd, p->b_c, 0, 0, gws,
+                           w.gemm_bytes, stream));
+      LR_TRY(lr_sgemm_impl(0, 1, R, Hd, Hd, 1.f, top, Hd, p->w_c + Hd, 2 * Hd, 1.f, pre, Hd, nullptr, 0, 0, gws,
+                           w.gemm_bytes, stream));
+    }
+    LR_LAUNCH(dec_out_fwd_kernel<false>, dim3((R + out_rows - 1) / out_rows), dim3(256), out_lds, stream,
+              attn ? pre : top, p->w_o, p->b_o, p->out_mask, lp, (int32_t*)nullptr, 1, Hd, V, 0, 1, R, out_rows,
+              attn ? 1 : 0, (uint64_t)0);
+    LR_TRY(lr_launch_status());
+    LR_LAUNCH(beam_select_kernel, dim3(B), dim3(SEL_THREADS), 0, stream, (const float*)lp, (double*)(base + w.score), I(w.len),
+              I(w.fin), I(w.live), I(w.next_in), I(w.parent), I(w.hist), I(w.ustate), ctr, out_ids, out_lens,
+              out_scores, K, Kc, V, LH, bos, eos, pad);
+    LR_TRY(lr_launch_status());
+    LR_LAUNCH(beam_reorder_kernel, dim3(R, NL), dim3(256), 0, stream, sp, (const int32_t*)I(w.parent),
+              (const int32_t*)I(w.ustate), K, Hd);
+    return lr_launch_status();
+  };
+
+  int32_t host[2] = {0, 0};
+  for (int rd = 1; rd <= LH; ++rd) {
+    LR_TRY(round());
+    if (rd % poll_every == 0 && rd < LH) {
+      lr_clear_error();
+      if (hipMemcpyAsync(host, ctr, sizeof(int32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+          hipStreamSynchronize(stream) != hipSuccess)
+        return LR_ERR_LAUNCH;
+      if (host[0] >= B) break;
+    }
+  }
+  if (rounds_host) {
+    lr_clear_error();
+    if (hipMemcpyAsync(host, ctr, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess)
+      return LR_ERR_LAUNCH;
+    *rounds_host = host[1];
+  }
+  return LR_OK;
+}

@@ -42,6 +42,10 @@ DEFAULTS = dict(  # train.py:134-167
     # language model, ctcdecode's default cutoff_top_n=40) with --beam_width hypotheses; --lm_path (an ARPA
     # file, '' = none) adds a word language model weighted by --lm_alpha, plus --lm_beta per word
     ctc_decoder="greedy", beam_width=100, lm_path="", lm_alpha=0.0, lm_beta=0.0,
+    # the error of a model WITH the attention decoder: teacher (the live loop's sampled-token mismatch rate under
+    # teacher forcing, train.eval) or beam (the edit-distance CER of the decoder's own beam-search transcript,
+    # train.attention_cer, --attn_beam_width hypotheses of up to --attn_max_label_len characters)
+    attn_decode="teacher", attn_beam_width=10, attn_max_label_len=100,
 )
 
 
@@ -119,6 +123,12 @@ def parse_flags(argv, defaults=DEFAULTS):
     raise SystemExit("--ctc_decoder must be greedy or beam")
   if out.get("lm_path") and out.get("ctc_decoder") != "beam":
     raise SystemExit("--lm_path needs --ctc_decoder=beam")
+  if out.get("attn_decode") not in ("teacher", "beam"):
+    raise SystemExit("--attn_decode must be teacher or beam")
+  if not 1 <= int(out.get("attn_beam_width", 10)) <= 32:
+    raise SystemExit("--attn_beam_width must be in [1, 32]")
+  if int(out.get("attn_max_label_len", 100)) < 1:
+    raise SystemExit("--attn_max_label_len must be positive")
   if out["frontend"] != "none" or out["encoder"] != "rnn":
     # the build-defined regimes are encoder + CTC (BASELINE configs[1], [4]); no attention decoder behind them
     for name in ("enable_ctc", "ctc_only"):
@@ -206,6 +216,27 @@ def _cer(correct, count):
   return float(count - correct) / count if count else 1.0
 
 
+def make_error_of(f, encoder, decoding_step, ctc_decoder, device, char2idx):
+  """The driver's error measure for a loader, by the flags `f`."""
+  from . import train as T
+
+  def error_of(loader):
+    """The live loop's "CER" is the sampled-token mismatch rate of the attention decoder (train.py:287-288
+    via eval's correct/count), or with --attn_decode=beam the edit-distance CER of its beam-search transcripts;
+    without a decoder it is the greedy-decoded CER of the CTC head (decoder.py:64-73 on :182-197, as
+    archive/train_model.py:351-357 composes them), or the beam-decoded one with --ctc_decoder=beam."""
+    if decoding_step is None:
+      if ctc_decoder is not None:
+        return T.ctc_cer(encoder, loader, device, char2idx, ctc_decoder)
+      return T.greedy_cer(encoder, loader, device, char2idx)
+    if f["attn_decode"] == "beam":
+      return T.attention_cer(encoder, decoding_step, loader, device, char2idx, beam_width=f["attn_beam_width"],
+                             max_label_len=f["attn_max_label_len"])
+    _, correct, count, _ = T.eval(encoder, decoding_step, loader, device, char2idx)
+    return _cer(correct, count)
+  return error_of
+
+
 def run(**flags):
   """The training loop of train.py:134-320 on one MI355X.  Returns a summary dict."""
   from . import train as T
@@ -264,17 +295,7 @@ def run(**flags):
                                  beta=f["lm_beta"], beam_width=f["beam_width"], blank_index=0,
                                  log_probs_input=True)
 
-  def error_of(loader):
-    """The live loop's "CER" is the sampled-token mismatch rate of the attention decoder (train.py:287-288
-    via eval's correct/count); without a decoder it is the greedy-decoded CER of the CTC head
-    (decoder.py:64-73 on :182-197, as archive/train_model.py:351-357 composes them), or the beam-decoded one
-    with --ctc_decoder=beam."""
-    if ctc_only:
-      if ctc_decoder is not None:
-        return T.ctc_cer(encoder, loader, device, char2idx, ctc_decoder)
-      return T.greedy_cer(encoder, loader, device, char2idx)
-    _, correct, count, _ = T.eval(encoder, decoding_step, loader, device, char2idx)
-    return _cer(correct, count)
+  error_of = make_error_of(f, encoder, decoding_step, ctc_decoder, device, char2idx)
 
   opt = tuple(FusedAdam(fl, lr=f["learning_rate"]) for fl in flats)
   if pixels and hasattr(encoder, "encoder"):

@@ -694,3 +694,40 @@ def ctc_cer(encoder, data_loader, device, char2idx, decoder):
         dist += decoder.cer(hyp, ref)
         total += len(ref.replace(' ', ''))
   return dist / max(total, 1)
+
+
+def attention_cer(encoder, decoding_step, data_loader, device, char2idx, beam_width=10, max_label_len=100):
+  """CER of the attention decoder's own transcripts: the best hypothesis of CharDecodingStep.beam_search (the
+  reference's analysis.inference, with this build's deterministic rule) with EOS stripped, scored as greedy_cer
+  scores the CTC head (sum of space-free edit distances / sum of space-free reference lengths).  A batch whose
+  encoder recurrence timed out is encoded again with recurrence='f32', as in greedy_cer."""
+  from .analysis import best_ids, encode_for_beam
+  from .decoder import _edit_distance
+  inv = {v: k for k, v in char2idx.items()}
+  eos = char2idx[EOS]
+  encoder.eval()
+  decoding_step.eval()
+  dist, total = 0, 0
+  on_gpu = torch.device(device).type == "cuda"
+  flag2 = torch.zeros(2, dtype=torch.int32, device=device) if on_gpu else None
+  with torch.no_grad():
+    for frames, frame_lens, chars, char_lens in data_loader:
+      if on_gpu:
+        _roll_faults(device)
+      hidden, lens_d, state = encode_for_beam(encoder, frames, frame_lens, device)
+      if on_gpu and not bool(_fault_keep(flag2)):
+        # the one-launch recurrence timed out (see greedy_cer): encode this batch again on the per-step kernels
+        inner = getattr(encoder, "encoder", encoder)
+        if hasattr(inner, "recurrence"):
+          saved, inner.recurrence = inner.recurrence, 'f32'
+          try:
+            hidden, lens_d, state = encode_for_beam(encoder, frames, frame_lens, device)
+          finally:
+            inner.recurrence = saved
+      best = best_ids(decoding_step, hidden, lens_d, state, beam_width, max_label_len)
+      for b, h in enumerate(best):
+        ref = ''.join(inv[int(c)] for c in chars[b, 1:int(char_lens[b]) - 1])  # strip BOS/EOS
+        hyp = ''.join(inv[int(i)] for i in h if i != eos)
+        dist += _edit_distance(hyp.replace(' ', ''), ref.replace(' ', ''))
+        total += len(ref.replace(' ', ''))
+  return dist / max(total, 1)
