@@ -76,10 +76,10 @@ typedef enum lr_rnn_mode {
    * _backward) takes the same cluster kernels, started from the encoder's final state, when every step is
    * teacher forced. */
   LR_RNN_RECUR_SPLIT = 0x1000,
-  /* with LR_RNN_PROJ_BF16X3: keep only the bf16 hi plane of EVERY operand of the input projection, its two
-   * gradients and dW_hh — one product each instead of two or three (weights and gate gradients rounded to bf16
-   * once per step, ~2^-9 relative).  An experiment of the build-defined pixel regime (encoder.input_projection =
-   * 'bf16x1'); measured against the oracle in bench.py's parity block, not a default. */
+  /* with LR_RNN_PROJ_BF16X3: keep only the bf16 hi plane of both operands of the input projection — one product
+   * instead of two or three (~2^-9 relative).  A FORWARD-ONLY experiment of the build-defined pixel regime
+   * (encoder.input_projection = 'bf16x1'), compared with the default in bench.py's parity block; the backward
+   * answers LR_ERR_UNSUPPORTED. */
   LR_RNN_PROJ_BF16X1 = 0x2000
 } lr_rnn_mode;
 
@@ -224,10 +224,9 @@ int lr_rnn_pass_launches(int mode, int B, int T, int I, int H, int D);
  * lr_rnn_debug_drop_member   TEST HOOK: member `m` (>= 0) of every pair / cluster returns at once, so its partners
  *                      time out (a few tenths of a second) and raise the fault; -1 (default) = off.
  * lr_rnn_debug_disable_cluster   TEST HOOK: bit 0 makes lr_rnn_pair_supported answer 0 for the cluster shapes
- *                      (and the decoder loop take its step kernels), bit 3 puts the first pixel-regime layer's dW_ih back on the
- *                      packed lr_xgemm path (round 5's A/B against lr_fgemm), bit 2 keeps the weight gradients of
- *                      LR_RNN_RECUR_SPLIT layers on the fp32 grouped GEMM, so the paths can be compared on one
- *                      model.  Size queries depend on it: set it BEFORE the forward whose backward it should cover.
+ *                      (and the decoder loop take its step kernels), so the one-launch and the per-step recurrences
+ *                      can be compared on one model; the other bits have no effect.  Size queries depend on it: set
+ *                      it BEFORE the forward whose backward it should cover.
  * lr_fault_export / lr_fault_import   data parallel (lipreading_amd/distributed.py): out2 = {status[0] (0 when
  *                      status is NULL), -(pending != 0)} for ONE MIN all-reduce over the ranks; import writes
  *                      in2[0] back to status[0] (skip the batch only if every rank skipped it) and raises the local
@@ -263,7 +262,7 @@ int lr_step_begin_ctc(float* grad, int64_t n, float* also_zero, const int64_t* c
                       const int64_t* frame_lens, const int64_t* char_lens, int32_t* labels_p1, int32_t* frame_lens32,
                       int32_t* label_lens32, int B, int L, lr_stream_t stream);
 void lr_rnn_debug_drop_member(int member);
-void lr_rnn_debug_disable_cluster(int off);   /* bit 0: no one-launch recurrence; 2: fp32 weight gradients + projection; 3: packed dW_ih; 4: always 8 samples per cluster */
+void lr_rnn_debug_disable_cluster(int off);   /* bit 0: no one-launch recurrence (the only bit read) */
 /* TUNING HOOK of the one-launch recurrences' exchange polling: which = 0 forward / 1 backward cluster kernels; 2 .. 5 the
  * four gathers of the grid recurrence (LSTM past 1152 units): forward h, forward partial sums, backward partial dh,
  * backward dG; first_poll_delay = 64-clock sleeps between a member's publish and its first poll of the others (default 0),

@@ -173,12 +173,9 @@ int lr_conv_wgrad_tr2(int layer, const void* X, const void* dZ, const void* code
 // include/lipreading_hip.h lr_fault_words_ptr).  NULL only when the allocation failed.
 int32_t* lr_fault_words();
 int lr_device_cus();                // compute units of the current device, 0 without one
-int lr_debug_drop_member_value();
+int lr_debug_drop_member_value();  // test hook (lr_rnn_debug_drop_member): that member of every cluster / pair exits at once
 int lr_debug_cluster_disabled();    // test hook (lr_rnn_debug_disable_cluster, bit 0): lr_rnn_cluster_supported answers 0
 int lr_debug_tune_value(int which);  // lr_rnn_debug_tune: exchange polling knobs of the cluster recurrence (0 forward, 1 backward)
-int lr_debug_ns8();                 // (bit 4): the cluster recurrence keeps 8 samples per cluster at every batch (round 6's A/B)
-int lr_debug_dwih_packed();         // (bit 3): the stored-bf16 first layer's dW_ih on the packed lr_xgemm path (round 5's A/B) instead of lr_fgemm
-int lr_debug_wgrad_f32();           // (bit 2): LR_RNN_RECUR_SPLIT layers keep their weight gradients on the fp32 grouped GEMM   // test hook (lr_rnn_debug_drop_member): that member of every cluster / pair exits at once
 
 // ---- recurrent layer pieces shared with lr_decoder.hip (implemented in lr_rnn.hip) --------------------
 size_t lr_rnn_packed_w_floats(int G, int H);
@@ -215,6 +212,17 @@ int lr_sgemm_grouped_tn_impl(int n, const int* M, const int* N, const int* K, co
                              hipStream_t stream, const LrRnnBiasJob* rider = nullptr);
 // lr_fgemm.hip: products straight from the tensors as they lie in memory (include/lipreading_hip.h lr_fgemm)
 int lr_fgemm_launch(int prec, int form, int a_bf16, int b_bf16, const lr_fgemm_job* jobs, int njobs, hipStream_t stream);
+// a job C = A . B with every optional field off (no bias, addend, mask, column sums or split-K; alpha 1, beta 0)
+inline lr_fgemm_job fgemm_job(const void* A, int lda, const void* Bm, int ldb, void* C, int ldc, int M, int N, int K) {
+  lr_fgemm_job j;
+  j.A = A; j.B = Bm; j.C = C;
+  j.bias = nullptr; j.addend = nullptr; j.mask = nullptr; j.colsum = nullptr; j.slabs = nullptr;
+  j.M = M; j.N = N; j.K = K; j.lda = lda; j.ldb = ldb; j.ldc = ldc;
+  j.ldadd = 0; j.add_period = 0; j.ldmask = 0; j.flags = 0; j.splits = 1;
+  j.alpha = 1.f; j.beta = 0.f;
+  j.b_shift = 0; j.b_period = 0;
+  return j;
+}
 int lr_fgemm_want_splits(int M, int N, int K);
 size_t lr_fgemm_slab_floats_impl(int M, int N, int splits);
 // lr_rnn_cluster.hip: the GRU / LSTM recurrence as one launch per layer pass, fp32-faithful (W_hh sliced over a
@@ -264,24 +272,13 @@ extern "C" size_t lr_xgemm_workspace_bytes(int transA, int transB, int M, int N,
 // the three products of a recurrent layer's input projection with all D directions in one
 // contraction each (gates / dG hold the directions side by side in a row; dstride = floats between
 // the directions' blocks of a dG row)
-size_t lr_xproj_workspace_bytes(int R, int I, int GH, int D, int H);
+size_t lr_xproj_workspace_bytes(int R, int I, int GH, int D);
 // (one_product: every operand as its bf16 hi plane only, LR_RNN_PROJ_BF16X1)
 int lr_xproj_forward(const float* x, int R, int I, const float* const* w_ih, int GH, int D, const float* bias,
                      float* gates, int x_exact, int x_bf16, void* workspace, size_t workspace_bytes,
                      hipStream_t stream, int one_product = 0);
-int lr_xproj_dw(const float* dG, int ldg, int dstride, const float* x, int R, int I, int GH, int D,
-                float* const* dw_ih, float beta, int x_exact, int x_bf16, void* workspace, size_t workspace_bytes,
-                hipStream_t stream, int one_product = 0);
 int lr_xproj_dx(const float* dG, int ldg, int dstride, const float* const* w_ih, int R, int I, int GH, int D,
                 float* dx, int hi_only, int dx_bf16, void* workspace, size_t workspace_bytes, hipStream_t stream);
-// dW_ih and dW_hh from ONE pack of dG (layers whose recurrent side reads dG slots 0..G-1: LSTM, tanh RNN)
-size_t lr_xproj_dw_both_workspace_bytes(int R, int I, int GH, int H, int D);
-int lr_xproj_dw_both(const float* dG, int ldg, int dstride, const float* x, const float* y, int ldy, int R, int T, int I,
-                     int H, int GH, int D, float* const* dw_ih, float* const* dw_hh, float beta, void* workspace,
-                     size_t workspace_bytes, hipStream_t stream);
-int lr_xproj_dwhh(const float* dG, int ldg, const float* y, int ldy, int R, int T, int H, int G, int D,
-                  float* const* dw_hh, float beta, void* workspace, size_t workspace_bytes, hipStream_t stream,
-                  int one_product = 0);
 
 // ---- lr_tfm_rowblock.hip: the row-wise half of an encoder layer as one launch per direction (LR_TFM_ROWBLOCK) ----
 int lr_tfm_rb_supported(int Dm, int F, int nlayers);

@@ -281,9 +281,9 @@ Res res_layout(const Sizes& z) {
 // A WIDE decoder's recurrent weight gradients (G * Hd >= 1536: the 1024-unit decoder of config/train/attn/attention_type,
 // the 1400 / 1536-unit ones of config/defaults.txt-style and ecd flag files, better_model.py:134-148) are split-bf16
 // products straight from dG and the states (lr_fgemm.hip, TN form, ~1e-5 relative — the encoder's rule for its own
-// wide layers, lr_rnn.hip wgrad_split) instead of the fp32-MFMA grouped GEMM: at LSTM-1536, B = 32 that GEMM was
-// 295 us of a 2.68 ms step at 40 % of the fp32 matrix peak.
-inline bool wide_wgrad(int G, int Hd) { return G * Hd >= 1536 && !lr_debug_wgrad_f32(); }
+// wide layers, lr_rnn.hip rnn_layer_backward_impl) instead of the fp32-MFMA grouped GEMM: at LSTM-1536, B = 32 that
+// GEMM was 295 us of a 2.68 ms step at 40 % of the fp32 matrix peak.
+inline bool wide_wgrad(int G, int Hd) { return G * Hd >= 1536; }
 
 struct Wsp {
   size_t wpT, dG, dcar, dgp, dy, dlogits, dpre, dctx, dlg, dsum, dEW, dsrc, dcterm, dPE, dph, dw2p, colsum, gemm,
@@ -817,12 +817,8 @@ extern "C" int lr_decoder_backward_parts(int mode, int attn_type, const lr_decod
       int n = 0;
       auto add = [&](int M, const float* A, const float* Bm, float* C) {
         lr_fgemm_job& j = jobs[n++];
-        j.A = A; j.B = Bm; j.C = C;
-        j.bias = nullptr; j.addend = nullptr; j.mask = nullptr; j.colsum = nullptr; j.slabs = nullptr;
-        j.M = M; j.N = Hd; j.K = BL; j.lda = ldg; j.ldb = Hd; j.ldc = Hd;
-        j.ldadd = 0; j.add_period = 0; j.ldmask = 0; j.flags = 0; j.splits = 1;
-        j.alpha = 1.f; j.beta = beta;
-        j.b_shift = 0; j.b_period = 0;
+        j = fgemm_job(A, ldg, Bm, Hd, C, Hd, M, Hd, BL);
+        j.beta = beta;
       };
       if (G == 3) {
         add(2 * Hd, dG, hprev, gw_hh);

@@ -619,7 +619,7 @@ namespace {
 constexpr int kMaxDevices = 64;
 int32_t* g_fault_words[kMaxDevices];
 int g_drop_member = -1;
-int g_cluster_off = 0;   // bit 0: no cluster recurrence; bit 2: weight gradients on the fp32 grouped GEMM
+int g_cluster_off = 0;   // lr_rnn_debug_disable_cluster; bit 0 (the only one read): no cluster recurrence
 __global__ void step_begin_kernel(float4* __restrict__ g, int64_t n4, float* __restrict__ tail, int ntail,
                                   int32_t* __restrict__ fault, float* __restrict__ also_zero) {
   const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -761,9 +761,6 @@ extern "C" int lr_debug_busy(int workgroups, int lds_bytes, int microseconds, lr
                      (long long)microseconds * 100, (int*)nullptr);
   return lr_launch_status();
 }
-int lr_debug_wgrad_f32() { return (g_cluster_off >> 2) & 1; }
-int lr_debug_dwih_packed() { return (g_cluster_off >> 3) & 1; }
-int lr_debug_ns8() { return (g_cluster_off >> 4) & 1; }
 // tuning knobs of the cluster recurrence's exchange (lr_rnn_debug_tune): [0] forward, [1] backward; bits 0-7 = 64-clock
 // sleeps before the first poll, bits 8-15 = sleeps between poll rounds
 // which = 2 .. 5: the grid recurrence's four gathers (lr_rnn_grid.hip): forward h, forward partial sums, backward partial dh,

@@ -522,7 +522,7 @@ Layout reserve_layout(int G, int B, int T, int I, int H, int D, bool x3 = false)
   l.hp = l.wp + (size_t)D * l.wp_per_dir;
   l.hp_floats = 2 * (size_t)D * nbt * nchunk * FRAG;
   l.gemm = l.hp + l.hp_floats;                               // split-K slabs of the input projection
-  l.gemm_bytes = x3 ? lr_xproj_workspace_bytes(B * T, I, G * H, D, H) : lr_sgemm_workspace_bytes(B * T, G * H, I);
+  l.gemm_bytes = x3 ? lr_xproj_workspace_bytes(B * T, I, G * H, D) : lr_sgemm_workspace_bytes(B * T, G * H, I);
   l.xch = (l.gemm + (l.gemm_bytes + 3) / 4 + 63) / 64 * 64;   // exchange words of the cluster recurrence
   l.xch_bytes = lr_rnn_cluster_supported(G, B, H) ? lr_rnn_cluster_xch_bytes(B, H, D, 0) : 0;
   // the cluster recurrence's BACKWARD fragments of W_hh and first exchange words: prepared by the forward's prologue
@@ -579,6 +579,53 @@ int wgrad_fgemm_plan(int G, int R, int I, int H, int D, size_t* slab_floats) {
   for (int j = 0; j < nj; ++j) f += (lr_fgemm_slab_floats_impl(Ms[j], Ns[j], (int)sp) + 63) / 64 * 64;
   *slab_floats = f * D;
   return (int)sp;
+}
+
+// A layer's weight half as split-bf16 lr_fgemm jobs straight from dG, x and y (TN form: ds_read_b64_tr_b16 delivers
+// both operands' K-major fragments, nothing is packed or transposed in memory; ~1e-5 relative):
+//   dW_ih[d] = dG[:, d, :GH]^T . x                        (x fp32, or stored as bf16 when x_bf16: its own hi plane)
+//   dW_hh[d] = dGh^T . h_prev, h_prev[b,t] = y[b,t-1] (forward) / y[b,t+1] (reverse), zero across sequence ends: B
+//              read through a row shift; the GRU's n-gate rows take slot 3 (d/d(W_hn h + b_hn)) instead of slot 2
+//   db_ih / db_hh = the column sums of those products' A operands, emitted by their first column tiles
+// ONE launch (two when x is stored as bf16: that operand form is its own instantiation); sp > 1 cuts K = R into sp
+// ranges whose partial sums go to `slab` (wgrad_fgemm_plan sizes it).
+int weight_half(const float* dG, int ldg, const float* x, int x_bf16, const float* y, int R, int T, int I, int H, int G,
+                int D, float* const* dw_ih, float* const* dw_hh, float* const* db_ih, float* const* db_hh, float beta,
+                int sp, float* slab, hipStream_t stream) {
+  const int GH = G * H;
+  lr_fgemm_job jobs[8];
+  int n = 0;
+  auto add = [&](const float* A, const void* Bm, int ldb, float* C, float* bias_out, int M, int N, int shift, int period) {
+    lr_fgemm_job& j = jobs[n++];
+    j = fgemm_job(A, ldg, Bm, ldb, C, N, M, N, R);
+    j.colsum = bias_out;
+    j.beta = beta;
+    j.b_shift = shift; j.b_period = period;
+    if (sp > 1) {
+      j.splits = sp;
+      j.slabs = slab;
+      slab += (lr_fgemm_slab_floats_impl(M, N, sp) + 63) / 64 * 64;
+    }
+  };
+  if (x_bf16) {
+    for (int d = 0; d < D; ++d) add(dG + (size_t)d * 4 * H, x, I, dw_ih[d], db_ih[d], GH, I, 0, 0);
+    int st = lr_fgemm_launch(LR_FGEMM_X3, LR_FGEMM_TN, 0, 1, jobs, n, stream);
+    if (st != LR_OK) return st;
+    n = 0;
+  }
+  for (int d = 0; d < D; ++d) {
+    const float* dGd = dG + (size_t)d * 4 * H;
+    const float* yd = y + (size_t)d * H;
+    const int shift = d == 0 ? -1 : 1;
+    if (!x_bf16) add(dGd, x, I, dw_ih[d], db_ih[d], GH, I, 0, 0);
+    if (G == 3) {
+      add(dGd, yd, D * H, dw_hh[d], db_hh[d], 2 * H, H, shift, T);
+      add(dGd + 3 * H, yd, D * H, dw_hh[d] + (size_t)2 * H * H, db_hh[d] + 2 * H, H, H, shift, T);
+    } else {
+      add(dGd, yd, D * H, dw_hh[d], db_hh[d], GH, H, shift, T);
+    }
+  }
+  return lr_fgemm_launch(LR_FGEMM_X3, LR_FGEMM_TN, 0, 0, jobs, n, stream);
 }
 
 struct WsLayout {
@@ -651,21 +698,10 @@ bool dims_ok(int mode, int B, int T, int I, int H, int D) {
          (!x_stored_bf16(mode) || (proj_x3(mode) && x_exact(mode) && I % 8 == 0)) &&
          B > 0 && T > 0 && I > 0 && H > 0 && (D == 1 || D == 2);
 }
-// extra workspace floats of the bf16x3 input projection's backward (operand planes + split-K slabs
-// of the larger of its products, all directions in one contraction)
+// extra workspace floats of the bf16x3 input projection's data gradient (operand planes + split-K slabs, all
+// directions in one contraction; sized as lr_xproj_workspace_bytes, for the forward as well)
 size_t x3_ws_floats(int G, int B, int T, int I, int H, int D) {
-  size_t b = lr_xproj_workspace_bytes(B * T, I, G * H, D, H);
-  const size_t b2 = lr_xproj_dw_both_workspace_bytes(B * T, I, G * H, H, D);
-  if (b2 > b) b = b2;
-  return (b / sizeof(float) + 63) / 64 * 64;
-}
-// Rounds 3-4: the weight gradients of a LARGE layer whose recurrence runs fp32-faithful on the bf16 matrix cores
-// (LR_RNN_RECUR_SPLIT, G * H >= 1536) as packed split-bf16 products (lr_xgemm.hip: one pack of dG, two contractions, a
-// combine) instead of the fp32-MFMA grouped GEMM (LSTM-768: 1.218 -> 1.155 ms per step then).  Round 5: EVERY such layer,
-// large or small, takes the one-launch lr_fgemm weight half (rnn_layer_backward_impl; BiLSTM-768 1.01 -> 0.87 ms); this
-// predicate now only sizes the workspace of the packed path, which test hook bit 3 still selects for the A/B.
-bool wgrad_split(int mode, int G, int H) {
-  return recur_split(mode) && !proj_x3(mode) && G * H >= 1536 && !lr_debug_wgrad_f32();
+  return (lr_xproj_workspace_bytes(B * T, I, G * H, D) / sizeof(float) + 63) / 64 * 64;
 }
 
 }  // namespace
@@ -706,7 +742,7 @@ extern "C" size_t lr_rnn_workspace_bytes(int mode, int B, int T, int I, int H, i
   if (!dims_ok(mode, B, T, I, H, D)) return 0;
   const int G = gates_of(mode);
   return ((ws_layout(G, B, T, I, H, D).total + 63) / 64 * 64 +
-          ((proj_x3(mode) || wgrad_split(mode, G, H)) ? x3_ws_floats(G, B, T, I, H, D) : 0)) *
+          (proj_x3(mode) ? x3_ws_floats(G, B, T, I, H, D) : 0)) *
          sizeof(float);
 }
 
@@ -746,48 +782,31 @@ extern "C" int lr_rnn_layer_forward(int mode, const float* x, const int32_t* len
     int st = lr_launch_status();
     if (st != LR_OK) return st;
   }
-  if (proj_x3(mode) && !x_stored_bf16(mode) && !x_exact(mode) && !proj_x1(mode) && I <= 1024 && !lr_debug_dwih_packed()) {
-    // an UPPER layer of the pixel regime (fp32 input, short K): gates[:, d, :] = x . W_ih[d]^T + folded bias straight from
-    // x and the weights (lr_fgemm.hip, NT form, bias in the epilogue), the directions as two jobs of one launch — no
-    // pack launch (round 5, bench shape: 37 us of pack + contraction -> one launch)
+  // lr_fgemm (NT form, bias in the epilogue, the directions as two jobs of one launch) straight from x and the weights:
+  // - an UPPER layer of the pixel regime (fp32 input, short K), as split-bf16 products — no pack launch (round 5, bench
+  //   shape: 37 us of pack + contraction -> one launch);
+  // - exact fp32 (regime R, recurrence 'f32') on the fp32 matrix cores (round 5: 128 x 128 tiles with double-buffered
+  //   stages in place of lr_gemm's 64 x 64 ones: 35.5 -> see profiles/r05_variants_ab.txt at B*T = 2400, I = 204,
+  //   G*H = 768).  Round 6: the LARGE layers of the one-launch recurrence (G * H >= 1536: the reference's own sizes —
+  //   LSTM-512 / 700 / 768, GRU-800 — whose weight gradients are split-bf16 products as well) take the projection as three
+  //   bf16 products too (~1e-5 relative; the recurrence it feeds contracts hi + lo planes itself): at M = 2400, N = 6144,
+  //   K = 204 the exact-fp32 MFMA form runs at 65-73 TF/s (93 us at B = 32, 329 us at the ecd family's own B = 128).
+  //   Small layers (BiGRU-256: 31 us) and recurrence = 'f32' stay exact.
+  const bool proj_fgemm = proj_x3(mode) ? !x_stored_bf16(mode) && !x_exact(mode) && !proj_x1(mode) && I <= 1024
+                                        : I % 4 == 0;
+  if (proj_fgemm) {
     lr_fgemm_job jobs[2];
     for (int d = 0; d < D; ++d) {
-      lr_fgemm_job& j = jobs[d];
-      j.A = x; j.B = w_ih[d]; j.C = gates + (size_t)d * GH;
-      j.bias = bias + (size_t)d * GH; j.addend = nullptr; j.mask = nullptr; j.colsum = nullptr; j.slabs = nullptr;
-      j.M = B * T; j.N = GH; j.K = I; j.lda = I; j.ldb = I; j.ldc = D * GH;
-      j.ldadd = 0; j.add_period = 0; j.ldmask = 0; j.flags = 0; j.splits = 1;
-      j.alpha = 1.f; j.beta = 0.f;
-      j.b_shift = 0; j.b_period = 0;
+      jobs[d] = fgemm_job(x, I, w_ih[d], I, gates + (size_t)d * GH, D * GH, B * T, GH, I);
+      jobs[d].bias = bias + (size_t)d * GH;
     }
-    int st = lr_fgemm_launch(LR_FGEMM_X3, LR_FGEMM_NT, 0, 0, jobs, D, stream);
+    const bool x3 = proj_x3(mode) || (cluster && GH >= 1536);
+    int st = lr_fgemm_launch(x3 ? LR_FGEMM_X3 : LR_FGEMM_F32, LR_FGEMM_NT, 0, 0, jobs, D, stream);
     if (st != LR_OK) return st;
   } else if (proj_x3(mode)) {
     // gates[b,t,:,:] = x[b,t,:] @ [W_ih[0]; W_ih[1]]^T + folded bias: both directions in one product
     int st = lr_xproj_forward(x, B * T, I, w_ih, GH, D, bias, gates, x_exact(mode) ? 1 : 0, x_stored_bf16(mode) ? 1 : 0,
                               l.gemm_bytes ? (void*)(base + l.gemm) : nullptr, l.gemm_bytes, stream, proj_x1(mode) ? 1 : 0);
-    if (st != LR_OK) return st;
-  } else if (I % 4 == 0 && D <= 2 && !lr_debug_dwih_packed()) {
-    // exact fp32 (regime R, recurrence 'f32'): gates[:, d, :] = x . W_ih[d]^T + folded bias as lr_fgemm jobs on the fp32
-    // matrix cores, the directions as two jobs of one launch (round 5: 128 x 128 tiles with double-buffered stages in
-    // place of lr_gemm's 64 x 64 ones: 35.5 -> see profiles/r05_variants_ab.txt at B*T = 2400, I = 204, G*H = 768)
-    lr_fgemm_job jobs[2];
-    for (int d = 0; d < D; ++d) {
-      lr_fgemm_job& j = jobs[d];
-      j.A = x; j.B = w_ih[d]; j.C = gates + (size_t)d * GH;
-      j.bias = bias + (size_t)d * GH; j.addend = nullptr; j.mask = nullptr; j.colsum = nullptr; j.slabs = nullptr;
-      j.M = B * T; j.N = GH; j.K = I; j.lda = I; j.ldb = I; j.ldc = D * GH;
-      j.ldadd = 0; j.add_period = 0; j.ldmask = 0; j.flags = 0; j.splits = 1;
-      j.alpha = 1.f; j.beta = 0.f;
-      j.b_shift = 0; j.b_period = 0;
-    }
-    // Round 6: the LARGE layers of the one-launch recurrence (G * H >= 1536: the reference's own sizes — LSTM-512 / 700 /
-    // 768, GRU-800 — whose weight gradients have been split-bf16 products since round 5) take the projection as three
-    // bf16 products too (~1e-5 relative; the recurrence it feeds contracts hi + lo planes itself): at M = 2400, N = 6144,
-    // K = 204 the exact-fp32 MFMA form runs at 65-73 TF/s (93 us at B = 32, 329 us at the ecd family's own B = 128).
-    // Small layers (BiGRU-256: 31 us) and recurrence = 'f32' stay exact.
-    const bool x3 = cluster && G * H >= 1536 && !lr_debug_wgrad_f32();
-    int st = lr_fgemm_launch(x3 ? LR_FGEMM_X3 : LR_FGEMM_F32, LR_FGEMM_NT, 0, 0, jobs, D, stream);
     if (st != LR_OK) return st;
   } else if (D == 2 && (((w_ih[1] - w_ih[0]) & 3) == 0)) {
     // gates[b,t,d,:] = x[b,t,:] @ W_ih[d]^T + folded bias: both directions as one batched launch (x shared,
@@ -881,6 +900,7 @@ static int rnn_layer_backward_impl(int mode, const float* x, const int32_t* lens
   LR_CHECK_ARG(dims_ok(mode, B, T, I, H, D));
   LR_CHECK_ARG((parts & ~3) == 0 && parts != 0);
   if (parts != 3 && !proj_x3(mode)) return LR_ERR_UNSUPPORTED;
+  if (proj_x1(mode)) return LR_ERR_UNSUPPORTED;   // (a forward-only experiment)
   LR_CHECK_ARG(x && lens && w_ih && w_hh && y && dy && reserve && workspace);
   const float wbeta = accumulate ? 1.f : 0.f;
   LR_CHECK_ARG(dw_ih && dw_hh && db_ih && db_hh);
@@ -894,9 +914,8 @@ static int rnn_layer_backward_impl(int mode, const float* x, const int32_t* lens
   if (reserve_bytes < rl.total * sizeof(float)) return LR_ERR_WORKSPACE;
   const WsLayout wl = ws_layout(G, B, T, I, H, D);
   const bool x3 = proj_x3(mode);
-  const bool wx = wgrad_split(mode, G, H);   // weight gradients as split-bf16 products (see wgrad_split)
   const size_t xws_off = (wl.total + 63) / 64 * 64;   // floats; keeps the bf16 planes 16-byte aligned
-  if (workspace_bytes < ((x3 || wx) ? xws_off + x3_ws_floats(G, B, T, I, H, D) : wl.total) * sizeof(float))
+  if (workspace_bytes < (x3 ? xws_off + x3_ws_floats(G, B, T, I, H, D) : wl.total) * sizeof(float))
     return LR_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   const float* rbase = (const float*)reserve;
@@ -958,136 +977,45 @@ static int rnn_layer_backward_impl(int mode, const float* x, const int32_t* lens
 
   const int R = B * T;
   const int ldg = D * 4 * H;
-  void* xws = wbase + xws_off;   // bf16x3 input projection: operand planes + split-K slabs
-  const size_t xws_bytes = (x3 || wx) ? x3_ws_floats(G, B, T, I, H, D) * sizeof(float) : 0;
   if (x3) {
     // input projection: all directions in one contraction per product (lr_xgemm.hip)
     if ((parts & 1) && dx) {
       // a bf16 input's gradient goes to a bf16 consumer (the conv frontend's backward): hi terms only
-      st = lr_xproj_dx(dG, ldg, 4 * H, w_ih, R, I, GH, D, dx, (x_exact(mode) || proj_x1(mode)) ? 1 : 0,
-                       x_stored_bf16(mode) ? 1 : 0, xws, xws_bytes, stream);
+      st = lr_xproj_dx(dG, ldg, 4 * H, w_ih, R, I, GH, D, dx, x_exact(mode) ? 1 : 0, x_stored_bf16(mode) ? 1 : 0,
+                       wbase + xws_off, x3_ws_floats(G, B, T, I, H, D) * sizeof(float), stream);
       if (st != LR_OK) return st;
     }
     if (!(parts & 2)) return LR_OK;
-    if (!proj_x1(mode) && !lr_debug_dwih_packed()) {
-      // The layer's whole weight half straight from dG, x and y (lr_fgemm.hip, TN form: ds_read_b64_tr_b16 delivers both
-      // operands' K-major fragments, nothing is packed or transposed in memory):
-      //   dW_ih[d] = dG[:, d, :GH]^T . x                        (x fp32, or the stored bf16 features: their own hi plane)
-      //   dW_hh[d] = dGh^T . h_prev, h_prev[b,t] = y[b,t-1] (forward) / y[b,t+1] (reverse), zero across sequence ends: B
-      //              read through a row shift; the GRU's n-gate rows take slot 3 (d/d(W_hn h + b_hn)) instead of slot 2
-      //   db_ih / db_hh = the column sums of those products' A operands, emitted by their first column tiles
-      // ONE launch (two when x is stored as bf16: that operand form is its own instantiation) of 24-350 workgroups in
-      // place of 2 pack launches + 2 contractions + 2 split-K combines + 2 bias-gradient launches that each swept the
-      // chip.  Round 5, same-visit A/B at the bench shape (profiles/r05_variants_ab.txt): dW_ih of the first layer alone
-      // (M 1536, N 3456, K 2400) took the pixel step from 2.517 / 2.477 ms to 2.397 / 2.393, the whole gradient
-      // BIT-identical (same products, same order).  lr_rnn_debug_disable_cluster bit 3 = the packed path, for that A/B.
-      lr_fgemm_job jobs[8];
-      int n = 0;
-      auto add = [&](const float* A, const void* Bm, int ldb, float* C, float* bias_out, int M, int N, int shift, int period) {
-        lr_fgemm_job& j = jobs[n++];
-        j.A = A; j.B = Bm; j.C = C;
-        j.bias = nullptr; j.addend = nullptr; j.mask = nullptr; j.colsum = bias_out; j.slabs = nullptr;
-        j.M = M; j.N = N; j.K = R; j.lda = ldg; j.ldb = ldb; j.ldc = N;
-        j.ldadd = 0; j.add_period = 0; j.ldmask = 0; j.flags = 0; j.splits = 1;
-        j.alpha = 1.f; j.beta = wbeta;
-        j.b_shift = shift; j.b_period = period;
-      };
-      const bool xbf = x_stored_bf16(mode);
-      if (xbf) {
-        for (int d = 0; d < D; ++d) add(dG + (size_t)d * 4 * H, x, I, dw_ih[d], db_ih[d], GH, I, 0, 0);
-        st = lr_fgemm_launch(LR_FGEMM_X3, LR_FGEMM_TN, 0, 1, jobs, n, stream);
-        if (st != LR_OK) return st;
-        n = 0;
-      }
-      for (int d = 0; d < D; ++d) {
-        const float* dGd = dG + (size_t)d * 4 * H;
-        const float* yd = y + (size_t)d * H;
-        const int shift = d == 0 ? -1 : 1;
-        if (!xbf) add(dGd, x, I, dw_ih[d], db_ih[d], GH, I, 0, 0);
-        if (G == 3) {
-          add(dGd, yd, D * H, dw_hh[d], db_hh[d], 2 * H, H, shift, T);
-          add(dGd + 3 * H, yd, D * H, dw_hh[d] + (size_t)2 * H * H, db_hh[d] + 2 * H, H, H, shift, T);
-        } else {
-          add(dGd, yd, D * H, dw_hh[d], db_hh[d], GH, H, shift, T);
-        }
-      }
-      return lr_fgemm_launch(LR_FGEMM_X3, LR_FGEMM_TN, 0, 0, jobs, n, stream);
-    }
-    st = lr_xproj_dw(dG, ldg, 4 * H, x, R, I, GH, D, dw_ih, wbeta, x_exact(mode) ? 1 : 0, x_stored_bf16(mode) ? 1 : 0,
-                     xws, xws_bytes, stream, proj_x1(mode) ? 1 : 0);
-    if (st != LR_OK) return st;
-    // recurrent weight gradient on the same split-bf16 path (one contraction per direction)
-    st = lr_xproj_dwhh(dG, ldg, y, D * H, R, T, H, G, D, dw_hh, wbeta, xws, xws_bytes, stream, proj_x1(mode) ? 1 : 0);
-    if (st != LR_OK) return st;
+    // (round 5, same-visit A/B at the bench shape, profiles/r05_variants_ab.txt: in place of 2 pack launches + 2
+    // contractions + 2 split-K combines + 2 bias-gradient launches, dW_ih of the first layer alone (M 1536, N 3456,
+    // K 2400) took the pixel step from 2.517 / 2.477 ms to 2.397 / 2.393, the whole gradient BIT-identical)
+    return weight_half(dG, ldg, x, x_stored_bf16(mode), y, R, T, I, H, G, D, dw_ih, dw_hh, db_ih, db_hh, wbeta, 1, nullptr,
+                       stream);
   }
-  // (round 5: the lr_fgemm weight half below serves the large layers too; test hook bit 3 keeps them on lr_xgemm's
-  // packed contractions, for the A/B)
-  const bool wx_packed = wx && lr_debug_dwih_packed();
-  if (wx_packed && G != 3) {
-    // fp32-faithful on the bf16 matrix cores, like the recurrence that produced dG (lr_xgemm.hip); both products
-    // read the same dG slots: ONE pack of dG
-    st = lr_xproj_dw_both(dG, ldg, 4 * H, x, y, D * H, R, T, I, H, GH, D, dw_ih, dw_hh, wbeta, xws, xws_bytes, stream);
-    if (st != LR_OK) return st;
-  } else if (wx_packed) {
-    // (GRU: the recurrent side reads slot 3 where the input side reads slot 2)
-    st = lr_xproj_dw(dG, ldg, 4 * H, x, R, I, GH, D, dw_ih, wbeta, 0, 0, xws, xws_bytes, stream);
-    if (st != LR_OK) return st;
-    st = lr_xproj_dwhh(dG, ldg, y, D * H, R, T, H, G, D, dw_hh, wbeta, xws, xws_bytes, stream);
-    if (st != LR_OK) return st;
-  }
-  LrRnnBiasJob bias_job;
-  bias_job.dG = dG; bias_job.partial = wbase + wl.colsum;
-  for (int d = 0; d < 2; ++d) {
-    bias_job.db_ih[d] = db_ih[d < D ? d : 0];
-    bias_job.db_hh[d] = db_hh[d < D ? d : 0];
-  }
-  bias_job.ld = ldg; bias_job.rows = R; bias_job.H = H; bias_job.D = D; bias_job.G = G; bias_job.accumulate = accumulate;
-  bool bias_done = false;
-  if (!x3 && !wx_packed && recur_split(mode) && !lr_debug_wgrad_f32()) {
-    // A layer on the one-launch recurrence, exact-fp32 projection (regime R; round 5): the weight half as split-bf16
-    // products straight from dG, x and y
-    // (lr_fgemm.hip, TN form, K cut into `sp` ranges; ~1e-5 relative, the recurrence that produced dG is itself a
-    // split-bf16 product) with the bias gradients as the products' column sums — one launch + one combine in place of
+  if (recur_split(mode)) {
+    // A layer on the one-launch recurrence, exact-fp32 projection (regime R; round 5): K cut into `sp` ranges (~1e-5
+    // relative, the recurrence that produced dG is itself a split-bf16 product) — one launch + one combine in place of
     // the exact-fp32 grouped GEMM (64 us at BiGRU-256, B = 32: the fp32 matrix cores' rate), its combine and two
-    // bias-gradient launches.  recurrence = 'f32' (the per-step kernels) keeps every product exact fp32.
+    // bias-gradient launches (BiLSTM-768: 1.01 -> 0.87 ms per step).  recurrence = 'f32' (the per-step kernels) keeps
+    // every product exact fp32.
     size_t sf = 0;
     const int sp = wgrad_fgemm_plan(G, R, I, H, D, &sf);
     if (wl.gemm_bytes < sf * sizeof(float)) return LR_ERR_WORKSPACE;
-    float* slab = (float*)gws;
-    lr_fgemm_job jobs[8];
-    int n = 0;
-    auto add = [&](const float* A, const float* Bm, int ldb, float* C, float* bias_out, int M, int N, int shift, int period) {
-      lr_fgemm_job& j = jobs[n++];
-      j.A = A; j.B = Bm; j.C = C;
-      j.bias = nullptr; j.addend = nullptr; j.mask = nullptr; j.colsum = bias_out;
-      j.slabs = sp > 1 ? slab : nullptr;
-      slab += (lr_fgemm_slab_floats_impl(M, N, sp) + 63) / 64 * 64;
-      j.M = M; j.N = N; j.K = R; j.lda = ldg; j.ldb = ldb; j.ldc = N;
-      j.ldadd = 0; j.add_period = 0; j.ldmask = 0; j.flags = 0; j.splits = sp;
-      j.alpha = 1.f; j.beta = wbeta;
-      j.b_shift = shift; j.b_period = period;
-    };
-    for (int d = 0; d < D; ++d) {
-      const float* dGd = dG + (size_t)d * 4 * H;
-      const float* yd = y + (size_t)d * H;
-      const int shift = d == 0 ? -1 : 1;
-      add(dGd, x, I, dw_ih[d], db_ih[d], GH, I, 0, 0);
-      if (G == 3) {
-        add(dGd, yd, D * H, dw_hh[d], db_hh[d], 2 * H, H, shift, T);
-        add(dGd + 3 * H, yd, D * H, dw_hh[d] + (size_t)2 * H * H, db_hh[d] + 2 * H, H, H, shift, T);
-      } else {
-        add(dGd, yd, D * H, dw_hh[d], db_hh[d], GH, H, shift, T);
-      }
-    }
-    st = lr_fgemm_launch(LR_FGEMM_X3, LR_FGEMM_TN, 0, 0, jobs, n, stream);
+    st = weight_half(dG, ldg, x, 0, y, R, T, I, H, G, D, dw_ih, dw_hh, db_ih, db_hh, wbeta, sp, (float*)gws, stream);
     if (st != LR_OK) return st;
-    bias_done = true;
-  } else if (!x3 && !wx_packed) {
+  } else {
     // every weight gradient of the layer in ONE grouped launch + one combine (lr_gemm.hip): each of these
     // small-M*N, K = B*T products fills a sixth of the chip on its own.
     //   dW_ih[d] (G*H x I) = dGx^T (slots 0..G-1 are contiguous rows) @ x
     //   dW_hh[d] = dGh^T @ h_prev, h_prev[b,t] = y[b,t-1] (forward dir) / y[b,t+1] (reverse dir); the GRU's
     //   n-gate rows take slot 3 (d/d(W_hn h + b_hn)) instead of slot 2
+    LrRnnBiasJob bias_job;
+    bias_job.dG = dG; bias_job.partial = wbase + wl.colsum;
+    for (int d = 0; d < 2; ++d) {
+      bias_job.db_ih[d] = db_ih[d < D ? d : 0];
+      bias_job.db_hh[d] = db_hh[d < D ? d : 0];
+    }
+    bias_job.ld = ldg; bias_job.rows = R; bias_job.H = H; bias_job.D = D; bias_job.G = G; bias_job.accumulate = accumulate;
     int Ms[8], Ns[8], Ks[8], ldas[8], ldbs[8], ldcs[8], shifts[8], periods[8], n = 0;
     const float* As[8];
     const float* Bs[8];
@@ -1114,21 +1042,13 @@ static int rnn_layer_backward_impl(int mode, const float* x, const int32_t* lens
     st = lr_sgemm_grouped_tn_impl(n, Ms, Ns, Ks, As, ldas, Bs, ldbs, Cs, ldcs, wbeta, shifts, periods, gws,
                                   wl.gemm_bytes, stream, &bias_job);
     if (st != LR_OK) return st;
-    bias_done = true;
   }
-  for (int d = 0; d < D && !x3; ++d) {
-    const float* dGd = dG + (size_t)d * 4 * H;
-    if (dx && !x3) {
-      st = lr_sgemm_impl(0, 0, R, I, GH, 1.f, dGd, ldg, w_ih[d], I, d == 0 ? 0.f : 1.f, dx, I,
-                         nullptr, 0, 0, gws, wl.gemm_bytes, stream);
-      if (st != LR_OK) return st;
-    }
+  for (int d = 0; d < D && dx; ++d) {
+    st = lr_sgemm_impl(0, 0, R, I, GH, 1.f, dG + (size_t)d * 4 * H, ldg, w_ih[d], I, d == 0 ? 0.f : 1.f, dx, I, nullptr,
+                       0, 0, gws, wl.gemm_bytes, stream);
+    if (st != LR_OK) return st;
   }
-  if (bias_done) return LR_OK;
-  st = lr_colsum_partial(dG, ldg, R, ldg, bias_job.partial, stream);
-  if (st != LR_OK) return st;
-  LR_LAUNCH(bias_grad_final_kernel, dim3((ldg + 255) / 256), dim3(256), 0, stream, bias_job);
-  return lr_launch_status();
+  return LR_OK;
 }
 
 extern "C" int lr_rnn_layer_backward(int mode, const float* x, const int32_t* lens,

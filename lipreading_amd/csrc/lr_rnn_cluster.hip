@@ -1060,11 +1060,10 @@ inline int max_clusters(int CC, int U) {   // Cfg::MAXCL without the template
   return (U == 32 && CC <= 16) ? xs * (32 / CC) : xs;
 }
 // samples per cluster of a pass: 16 where the shape has the form (32-unit members, CC >= 17: one cluster per XCD) AND the
-// batch would take more than one launch of 8-sample clusters; 8 otherwise (and under the test hook, bit 4 of
-// lr_rnn_debug_disable_cluster, for the A/B)
+// batch would take more than one launch of 8-sample clusters; 8 otherwise
 constexpr bool has_ns16(int CC, int U) { return U == 32 && CC >= 17 && CC <= 24; }   // (25 .. 27 GRU members: the state of 16 samples does not fit the LDS beside the fragments)
 inline int pick_ns(int CC, int U, int B, int D) {
-  return has_ns16(CC, U) && !lr_debug_ns8() && (B + 7) / 8 * D > max_clusters(CC, U) ? 16 : 8;
+  return has_ns16(CC, U) && (B + 7) / 8 * D > max_clusters(CC, U) ? 16 : 8;
 }
 
 // words of the first launch's exchange area
@@ -1298,18 +1297,11 @@ size_t lr_rnn_cluster_xch_bytes(int B, int H, int D, int backward) {
   if (lr_rnn_grid_shape(4, H)) return lr_rnn_grid_xch_bytes(B, backward);   // (a GRU of this size has no one-launch kernel)
   // (the exchange area does not depend on the gate count: resolve as the LSTM, whose 32-unit range is the smaller)
   if (!resolve_shape(4, H, &cc, &u) && !resolve_shape(3, H, &cc, &u)) return 0;
-  // (the largest of: 8-sample clusters, and 16-sample ones where the shape and the batch take them — the test hook may
-  // switch between the two after the buffers were sized)
-  auto words = [&](int c_, int u_) {
-    size_t best = 0;
-    for (int ns = 8; ns <= (has_ns16(c_, u_) && (B + 7) / 8 * D > max_clusters(c_, u_) ? 16 : 8); ns += 8) {
-      const int maxcl = max_clusters(c_, u_);
-      int clusters = (B + ns - 1) / ns * D;
-      if (clusters > maxcl) clusters = maxcl;
-      const size_t w_ = xch_words(c_, u_, ns, clusters, backward);
-      if (w_ > best) best = w_;
-    }
-    return best;
+  auto words = [&](int c_, int u_) {   // (for the samples per cluster that the pass takes)
+    const int ns = pick_ns(c_, u_, B, D), maxcl = max_clusters(c_, u_);
+    int clusters = (B + ns - 1) / ns * D;
+    if (clusters > maxcl) clusters = maxcl;
+    return xch_words(c_, u_, ns, clusters, backward);
   };
   size_t w = words(cc, u);
   int cc3, u3;

@@ -270,17 +270,6 @@ bool tfm_dims_ok(int mode, int B, int T, int I, int Dm, int nh, int F, int nl) {
          (!(mode & LR_TFM_ROWBLOCK) || ((mode & LR_TFM_X3) && lr_tfm_rb_supported(Dm, F, nl)));
 }
 
-lr_fgemm_job job(const void* A, int lda, const void* Bm, int ldb, void* C, int ldc, int M, int N, int K) {
-  lr_fgemm_job j;
-  j.A = A; j.B = Bm; j.C = C;
-  j.bias = nullptr; j.addend = nullptr; j.mask = nullptr; j.colsum = nullptr; j.slabs = nullptr;
-  j.M = M; j.N = N; j.K = K; j.lda = lda; j.ldb = ldb; j.ldc = ldc;
-  j.ldadd = 0; j.add_period = 0; j.ldmask = 0; j.flags = 0; j.splits = 1;
-  j.alpha = 1.f; j.beta = 0.f;
-  j.b_shift = 0; j.b_period = 0;
-  return j;
-}
-
 #define LR_TRY_(expr)              \
   do {                             \
     const int lr_st_ = (expr);     \
@@ -354,7 +343,7 @@ extern "C" int lr_tfm_forward(int mode, const void* x, const int32_t* key_lens, 
   // h0 = x W_p^T + b_p + pe[t]   (K = I may be long and the product has few tiles: split K)
   float* h = base + r.h0;
   {
-    lr_fgemm_job j = job(x, I, weights[0], I, h, Dm, R, Dm, I);
+    lr_fgemm_job j = fgemm_job(x, I, weights[0], I, h, Dm, R, Dm, I);
     j.bias = weights[1];
     j.addend = pe; j.ldadd = Dm; j.add_period = T;
     j.splits = lr_fgemm_want_splits(R, Dm, I);
@@ -367,7 +356,7 @@ extern "C" int lr_tfm_forward(int mode, const void* x, const int32_t* key_lens, 
     const float* const* W = weights + 2 + 12 * l;
     float* L = base + r.layer0 + (size_t)l * r.per_layer;
     float* h2 = l == nlayers - 1 ? h_out : L + r.h2;
-    lr_fgemm_job j = job(h, Dm, W[0], Dm, L + r.qkv, 3 * Dm, R, 3 * Dm, Dm);
+    lr_fgemm_job j = fgemm_job(h, Dm, W[0], Dm, L + r.qkv, 3 * Dm, R, 3 * Dm, Dm);
     j.bias = W[1];
     if (!(rowblock && l > 0))   // (row blocks: layer l - 1's launch wrote this layer's qkv on its way out)
       LR_TRY_(lr_fgemm_launch(prec, LR_FGEMM_NT, 0, 0, &j, 1, st));
@@ -383,16 +372,16 @@ extern "C" int lr_tfm_forward(int mode, const void* x, const int32_t* key_lens, 
       h = h2;
       continue;
     }
-    j = job(L + r.a, Dm, W[2], Dm, L + r.s1, Dm, R, Dm, Dm);      // s1 = a W_o^T + b_o + h
+    j = fgemm_job(L + r.a, Dm, W[2], Dm, L + r.s1, Dm, R, Dm, Dm);      // s1 = a W_o^T + b_o + h
     j.bias = W[3];
     j.addend = h; j.ldadd = Dm; j.add_period = R;
     LR_TRY_(lr_fgemm_launch(prec, LR_FGEMM_NT, 0, 0, &j, 1, st));
     LR_TRY_(ln_forward(L + r.s1, W[8], W[9], L + r.h1, L + r.st1, R, Dm, eps, st));
-    j = job(L + r.h1, Dm, W[4], Dm, L + r.f1, F, R, F, Dm);        // f1 = relu(h1 W_1^T + b_1)
+    j = fgemm_job(L + r.h1, Dm, W[4], Dm, L + r.f1, F, R, F, Dm);        // f1 = relu(h1 W_1^T + b_1)
     j.bias = W[5];
     j.flags = LR_FGEMM_RELU;
     LR_TRY_(lr_fgemm_launch(prec, LR_FGEMM_NT, 0, 0, &j, 1, st));
-    j = job(L + r.f1, F, W[6], F, L + r.s2, Dm, R, Dm, F);         // s2 = f1 W_2^T + b_2 + h1
+    j = fgemm_job(L + r.f1, F, W[6], F, L + r.s2, Dm, R, Dm, F);         // s2 = f1 W_2^T + b_2 + h1
     j.bias = W[7];
     j.addend = L + r.h1; j.ldadd = Dm; j.add_period = R;
     LR_TRY_(lr_fgemm_launch(prec, LR_FGEMM_NT, 0, 0, &j, 1, st));
@@ -432,28 +421,28 @@ extern "C" int lr_tfm_backward_data(int mode, const int32_t* key_lens, const flo
                                  F, st));
     } else {
       LR_TRY_(ln_backward(L + r.s2, W[10], L + r.st2, dh_cur, G + w.ds2, G + w.lnp2, R, Dm, st));
-      j = job(G + w.ds2, Dm, W[6], F, G + w.df1, F, R, F, Dm);      // df1 = (ds2 W_2) where f1 > 0
+      j = fgemm_job(G + w.ds2, Dm, W[6], F, G + w.df1, F, R, F, Dm);      // df1 = (ds2 W_2) where f1 > 0
       j.mask = L + r.f1; j.ldmask = F;
       LR_TRY_(lr_fgemm_launch(prec, LR_FGEMM_NN, 0, 0, &j, 1, st));
-      j = job(G + w.df1, F, W[4], Dm, wsb + w.dh1, Dm, R, Dm, F);                // dh1 = df1 W_1 + ds2
+      j = fgemm_job(G + w.df1, F, W[4], Dm, wsb + w.dh1, Dm, R, Dm, F);                // dh1 = df1 W_1 + ds2
       j.addend = G + w.ds2; j.ldadd = Dm; j.add_period = R;
       LR_TRY_(lr_fgemm_launch(prec, LR_FGEMM_NN, 0, 0, &j, 1, st));
       LR_TRY_(ln_backward(L + r.s1, W[8], L + r.st1, wsb + w.dh1, G + w.ds1, G + w.lnp1, R, Dm, st));
-      j = job(G + w.ds1, Dm, W[2], Dm, wsb + w.da, Dm, R, Dm, Dm);               // da = ds1 W_o
+      j = fgemm_job(G + w.ds1, Dm, W[2], Dm, wsb + w.da, Dm, R, Dm, Dm);               // da = ds1 W_o
       LR_TRY_(lr_fgemm_launch(prec, LR_FGEMM_NN, 0, 0, &j, 1, st));
     }
     if (mode & LR_TFM_ATTN_FUSED)
       LR_TRY_(lr_attn_fused_backward(L + r.qkv, key_lens, wsb + w.da, G + w.dqkv, 1.f / sqrtf((float)dh), B, T, nhead, dh, st));
     else
       LR_TRY_(attention_f32_backward(L + r.qkv, L + r.probs, wsb + w.da, wsb + w.dP, G + w.dqkv, B, T, nhead, dh, st));
-    j = job(G + w.dqkv, 3 * Dm, W[0], Dm, dh_prev, Dm, R, Dm, 3 * Dm);         // dh = dqkv W_qkv + ds1
+    j = fgemm_job(G + w.dqkv, 3 * Dm, W[0], Dm, dh_prev, Dm, R, Dm, 3 * Dm);         // dh = dqkv W_qkv + ds1
     j.addend = G + w.ds1; j.ldadd = Dm; j.add_period = R;
     if (!((mode & LR_TFM_ROWBLOCK) && l > 0))   // (row blocks: the layer below takes it in at the start of its chain)
       LR_TRY_(lr_fgemm_launch(prec, LR_FGEMM_NN, 0, 0, &j, 1, st));
     dh_cur = dh_prev;
   }
   if (dx) {   // dx = dh0 W_p
-    lr_fgemm_job j = job(dh_cur, Dm, weights[0], I, dx, I, R, I, Dm);
+    lr_fgemm_job j = fgemm_job(dh_cur, Dm, weights[0], I, dx, I, R, I, Dm);
     if (mode & LR_TFM_DX_BF16) j.flags = LR_FGEMM_C_BF16;
     LR_TRY_(lr_fgemm_launch(prec, LR_FGEMM_NN, 0, 0, &j, 1, st));
   }
@@ -486,7 +475,7 @@ extern "C" int lr_tfm_backward_weights(int mode, const void* x, float* const* gr
     return st_;
   };
   auto add = [&](const float* dy, int ldy, const void* xin, int ldx, float* dW, float* db, int M, int N) {
-    lr_fgemm_job j = job(dy, ldy, xin, ldx, dW, N, M, N, R);
+    lr_fgemm_job j = fgemm_job(dy, ldy, xin, ldx, dW, N, M, N, R);
     j.colsum = db;
     j.beta = beta;
     jobs[n++] = j;

@@ -66,19 +66,13 @@ struct XArgs {
   const bf16_t* Bh;   // [N][K]
   const bf16_t* Bl;
   float* C;
-  float* C1;          // rows >= split_row go to C1 + (row - split_row) * ldc (two stacked outputs)
-  int split_row;
   const float* bias;
   int M, N, K, ldp, ldc;
   float alpha, beta;
   int k_chunk;     // K range per split (multiple of XBK)
   float* slabs;    // split-K partial sums [splits][M][N], or nullptr
   int nx, ny, splits, per_xcd;   // tile grid and the number of tiles each XCD takes
-  // batch (blockIdx.y): independent products of one shape sharing a launch
-  int64_t a_bstride, b_bstride;  // bf16 elements between the batches' planes (hi and lo alike)
-  int64_t slab_bstride;          // floats between the batches' split-K slabs
-  float* Cb;                     // C of batch 1 (batch 0 writes C); no C1 split when batched
-  int c_bf16;                    // C is a bf16 matrix (ldc in elements; beta must be 0, no C1 split)
+  int c_bf16;                    // C is a bf16 matrix (ldc in elements; beta must be 0)
 };
 
 // ---- pass 1: fp32 [rows][cols] (or its transpose) -> bf16 hi (+ lo) planes [rows'][ldp] -------------
@@ -86,12 +80,9 @@ struct XArgs {
 // Output columns [0, owidth) are written, zero beyond the logical width (the contraction reads whole
 // 16-byte units up to ldp); hi / lo may point into the middle of a larger plane (an operand assembled
 // from several blocks).  32x32 tiles, 256 threads; the grid covers the OUTPUT extent.
-// shift / period: input row r is read from row r + shift, or as zero when (r % period) + shift leaves
-// [0, period) — the previous / next time step of a [B*T][cols] sequence tensor (period = T).
 __global__ __launch_bounds__(256) void xpack_kernel(const float* __restrict__ in, int ld_in, int rows, int cols,
                                                     int transpose, bf16_t* __restrict__ hi,
-                                                    bf16_t* __restrict__ lo, int ldp, int owidth, int shift,
-                                                    int period) {
+                                                    bf16_t* __restrict__ lo, int ldp, int owidth) {
   __shared__ float tile[32][33];
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
   // tile origin in OUTPUT coordinates (orow, ocol); input origin is the same or swapped
@@ -100,12 +91,7 @@ __global__ __launch_bounds__(256) void xpack_kernel(const float* __restrict__ in
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int r = ir0 + ty + 8 * i, c = ic0 + tx;
-    bool ok = r < rows && c < cols;
-    if (ok && shift != 0) {
-      const int tt = r % period + shift;
-      ok = tt >= 0 && tt < period;
-    }
-    tile[ty + 8 * i][tx] = ok ? in[(int64_t)(r + shift) * ld_in + c] : 0.f;
+    tile[ty + 8 * i][tx] = r < rows && c < cols ? in[(int64_t)r * ld_in + c] : 0.f;
   }
   __syncthreads();
   const int orows = transpose ? cols : rows;
@@ -129,7 +115,7 @@ struct XPackBlock {
   const float* in;
   bf16_t* hi;
   bf16_t* lo;
-  int ld_in, rows, cols, transpose, ldp, owidth, shift, period;
+  int ld_in, rows, cols, transpose, ldp, owidth;
   int in_bf16;   // the source is a bf16 matrix (ld_in in elements), e.g. the conv frontend's features
 };
 constexpr int XPACK_MAX = 8;
@@ -156,14 +142,9 @@ __global__ __launch_bounds__(256) void xpack_multi_kernel(XPackArgs a) {
   for (int i = 0; i < 4; ++i) {
     const int rl = (t >> 4) + 16 * i, cl = 4 * (t & 15);
     const int r = ir0 + rl, c = ic0 + cl;
-    bool ok = r < k.rows;
-    if (ok && k.shift != 0) {
-      const int tt = r % k.period + k.shift;
-      ok = tt >= 0 && tt < k.period;
-    }
     float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (ok) {
-      const int64_t idx = (int64_t)(r + k.shift) * k.ld_in + c;
+    if (r < k.rows) {
+      const int64_t idx = (int64_t)r * k.ld_in + c;
       if (in_vec && c + 3 < k.cols) {
         if (k.in_bf16) {
           const uint2 u = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(k.in) + idx);
@@ -238,16 +219,6 @@ __global__ __launch_bounds__(256) void xgemm_kernel(XArgs g) {
   const int in_grp = tt - grp * XGROUP_M * g.nx;
   const int m0 = (first_m + in_grp % gm) * XBM, n0 = (in_grp / gm) * XBN;
   const int kbeg = zs * g.k_chunk, kend = min(g.K, kbeg + g.k_chunk);
-  const int bz = blockIdx.y;
-  if (bz) {   // workgroup-uniform
-    g.Ah += (int64_t)bz * g.a_bstride;
-    if (!AX) g.Al += (int64_t)bz * g.a_bstride;
-    g.Bh += (int64_t)bz * g.b_bstride;
-    if (!BX) g.Bl += (int64_t)bz * g.b_bstride;
-    if (g.slabs) g.slabs += (int64_t)bz * g.slab_bstride;
-    g.C = g.Cb;
-    g.C1 = g.Cb;
-  }
 
   // a plane tile is 128 rows x 64 k = 1024 16-byte units: four per thread (row = e / 8, unit = e % 8).  Rows past
   // the matrix edge are CLAMPED, not zeroed (their products land in accumulator rows / columns that are never
@@ -406,7 +377,7 @@ __global__ __launch_bounds__(256) void xgemm_kernel(XArgs g) {
           reinterpret_cast<bf16_t*>(g.C)[(int64_t)row * g.ldc + col] = __builtin_bit_cast(bf16_t, hb);
           continue;
         }
-        float* c = (row < g.split_row ? g.C + (int64_t)row * g.ldc : g.C1 + (int64_t)(row - g.split_row) * g.ldc) + col;
+        float* c = g.C + (int64_t)row * g.ldc + col;
         if (g.beta != 0.f) out += g.beta * *c;
         *c = out;
       }
@@ -417,16 +388,9 @@ __global__ __launch_bounds__(256) void xgemm_kernel(XArgs g) {
 // elements per thread (16-byte loads of every slab in flight together) when N % 4 == 0; this pass is pure HBM
 // streaming of (splits + 1) * M * N floats.
 __global__ __launch_bounds__(256) void xsplitk_reduce_kernel(const float* __restrict__ slabs, int splits,
-                                                             float* __restrict__ C, float* __restrict__ C1,
-                                                             int split_row, int ldc, const float* __restrict__ bias,
-                                                             int M, int N, float alpha, float beta,
-                                                             float* __restrict__ Cb, int64_t slab_bstride, int c_bf16) {
+                                                             float* __restrict__ C, int ldc, const float* __restrict__ bias,
+                                                             int M, int N, float alpha, float beta, int c_bf16) {
   const int64_t total = (int64_t)M * N;
-  if (blockIdx.y) {   // batch 1
-    slabs += slab_bstride;
-    C = Cb;
-    C1 = Cb;
-  }
   auto finish = [&](int64_t i, float s) {
     const int row = (int)(i / N), col = (int)(i - (int64_t)row * N);
     float out = alpha * s;
@@ -436,15 +400,14 @@ __global__ __launch_bounds__(256) void xsplitk_reduce_kernel(const float* __rest
       reinterpret_cast<bf16_t*>(C)[(int64_t)row * ldc + col] = __builtin_bit_cast(bf16_t, hb);
       return;
     }
-    float* c = (row < split_row ? C + (int64_t)row * ldc : C1 + (int64_t)(row - split_row) * ldc) + col;
+    float* c = C + (int64_t)row * ldc + col;
     if (beta != 0.f) out += beta * *c;
     *c = out;
   };
   if ((N & 3) == 0) {
     const int64_t quads = total >> 2;
     const bool vec_out = !c_bf16 && (ldc & 3) == 0 &&
-                         ((reinterpret_cast<uintptr_t>(C) | reinterpret_cast<uintptr_t>(C1) |
-                           (bias ? reinterpret_cast<uintptr_t>(bias) : 0)) & 15) == 0;
+                         ((reinterpret_cast<uintptr_t>(C) | (bias ? reinterpret_cast<uintptr_t>(bias) : 0)) & 15) == 0;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (int64_t)gridDim.x * blockDim.x) {
       const float4* src = reinterpret_cast<const float4*>(slabs) + q;
       float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -464,7 +427,7 @@ __global__ __launch_bounds__(256) void xsplitk_reduce_kernel(const float* __rest
       const int64_t i = q << 2;
       if (vec_out) {   // plain fp32 output with 16-byte aligned rows: one store (and one read for beta) per quad
         const int row = (int)(i / N), col = (int)(i - (int64_t)row * N);
-        float4* c = reinterpret_cast<float4*>((row < split_row ? C + (int64_t)row * ldc : C1 + (int64_t)(row - split_row) * ldc) + col);
+        float4* c = reinterpret_cast<float4*>(C + (int64_t)row * ldc + col);
         float4 o = make_float4(alpha * s.x, alpha * s.y, alpha * s.z, alpha * s.w);
         if (bias) {
           const float4 b = *reinterpret_cast<const float4*>(bias + col);
@@ -521,10 +484,10 @@ int want_splits(int M, int N, int K) {
 // planes [orows][owidth of ldp] of an operand block stored [rows][cols] (transpose: planes are
 // [cols][rows]); hi / lo may be offset into a larger plane
 int pack_operand(const float* in, int ld_in, int rows, int cols, int transpose, bf16_t* hi, bf16_t* lo, int ldp,
-                 int owidth, hipStream_t stream, int shift = 0, int period = 1) {
+                 int owidth, hipStream_t stream) {
   const int orows = transpose ? cols : rows;
   LR_LAUNCH(xpack_kernel, dim3((owidth + 31) / 32, (orows + 31) / 32), dim3(256), 0, stream, in, ld_in, rows, cols,
-            transpose, hi, lo, ldp, owidth, shift, period);
+            transpose, hi, lo, ldp, owidth);
   return lr_launch_status();
 }
 
@@ -533,11 +496,11 @@ struct PackList {
   XPackArgs a;
   int n = 0, gx = 0, gy = 0;
   void add(const float* in, int ld_in, int rows, int cols, int transpose, bf16_t* hi, bf16_t* lo, int ldp, int owidth,
-           int shift = 0, int period = 1, int in_bf16 = 0) {
+           int in_bf16 = 0) {
     XPackBlock& k = a.b[n++];
     k.in = in; k.hi = hi; k.lo = lo;
     k.ld_in = ld_in; k.rows = rows; k.cols = cols; k.transpose = transpose; k.ldp = ldp; k.owidth = owidth;
-    k.shift = shift; k.period = period; k.in_bf16 = in_bf16;
+    k.in_bf16 = in_bf16;
     const int orows = transpose ? cols : rows;
     if ((owidth + 63) / 64 > gx) gx = (owidth + 63) / 64;
     if ((orows + 63) / 64 > gy) gy = (orows + 63) / 64;
@@ -548,23 +511,20 @@ struct PackList {
   }
 };
 
-// C (+ C1 below split_row) = alpha * A_planes . B_planes^T + beta * C + bias; slabs: split-K workspace.
-// nbatch = 2: a second product of the same shape in the same launch (planes a_bstride / b_bstride
-// bf16 elements further, output Cb, its slabs behind the first batch's).
+// C = alpha * A_planes . B_planes^T + beta * C + bias; slabs: split-K workspace.
 int contract(const bf16_t* Ahp, const bf16_t* Alp, const bf16_t* Bhp, const bf16_t* Blp, int M, int N, int K,
-             float alpha, float beta, float* C, float* C1, int split_row, int ldc, const float* bias, float* slabs,
-             size_t slab_floats, hipStream_t stream, int nbatch = 1, int64_t a_bstride = 0, int64_t b_bstride = 0,
-             float* Cb = nullptr, int c_bf16 = 0) {
+             float alpha, float beta, float* C, int ldc, const float* bias, float* slabs, size_t slab_floats,
+             hipStream_t stream, int c_bf16 = 0) {
   const int ldp = ldp_of(K);
   // split-K as far as the remaining workspace allows (none: a single pass, just slower)
-  int splits = want_splits(M, N * nbatch, K);
-  while (splits > 1 && (size_t)splits * M * N * nbatch > slab_floats) --splits;
+  int splits = want_splits(M, N, K);
+  while (splits > 1 && (size_t)splits * M * N > slab_floats) --splits;
   int chunk = (K + splits - 1) / splits;
   chunk = (chunk + XBK - 1) / XBK * XBK;
   splits = (K + chunk - 1) / chunk;
   XArgs g;
   g.Ah = Ahp; g.Al = Alp; g.Bh = Bhp; g.Bl = Blp;
-  g.C = C; g.C1 = C1 ? C1 : C; g.split_row = C1 ? split_row : M; g.bias = bias;
+  g.C = C; g.bias = bias;
   g.M = M; g.N = N; g.K = K; g.ldp = ldp; g.ldc = ldc;
   g.alpha = alpha; g.beta = beta;
   g.k_chunk = chunk;
@@ -572,13 +532,10 @@ int contract(const bf16_t* Ahp, const bf16_t* Alp, const bf16_t* Bhp, const bf16
   g.nx = (N + XBN - 1) / XBN;
   g.ny = (M + XBM - 1) / XBM;
   g.splits = splits;
-  g.a_bstride = a_bstride; g.b_bstride = b_bstride;
-  g.slab_bstride = (int64_t)splits * M * N;
-  g.Cb = Cb ? Cb : C;
   g.c_bf16 = c_bf16;
   const int ntile = g.nx * g.ny * splits;
   g.per_xcd = (ntile + 7) / 8;
-  dim3 grid(8 * g.per_xcd, nbatch);
+  const dim3 grid(8 * g.per_xcd);
   lr_clear_error();
   const bool ax = Alp == nullptr, bx = Blp == nullptr;
   if (ax && bx) hipLaunchKernelGGL((xgemm_kernel<true, true>), grid, dim3(256), 0, stream, g);
@@ -591,8 +548,8 @@ int contract(const bf16_t* Ahp, const bf16_t* Alp, const bf16_t* Bhp, const bf16
   int blocks = (int)(((N & 3) == 0 ? total / 4 : total) + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
-  LR_LAUNCH(xsplitk_reduce_kernel, dim3(blocks, nbatch), dim3(256), 0, stream, (const float*)g.slabs, splits, C, g.C1,
-            g.split_row, ldc, bias, M, N, alpha, beta, g.Cb, g.slab_bstride, c_bf16);
+  LR_LAUNCH(xsplitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)g.slabs, splits, C, ldc, bias, M,
+            N, alpha, beta, c_bf16);
   return lr_launch_status();
 }
 
@@ -648,26 +605,19 @@ int lr_xgemm_impl(int transA, int transB, int M, int N, int K, float alpha, cons
   st = transB ? pack_operand(B, ldb, N, K, 0, pl.Bh, pl.Bl, ldp, ldp, stream)
               : pack_operand(B, ldb, K, N, 1, pl.Bh, pl.Bl, ldp, ldp, stream);
   if (st != LR_OK) return st;
-  return contract(pl.Ah, pl.Al, pl.Bh, pl.Bl, M, N, K, alpha, beta, C, nullptr, M, ldc, bias, pl.slabs,
-                  pl.slab_floats, stream);
+  return contract(pl.Ah, pl.Al, pl.Bh, pl.Bl, M, N, K, alpha, beta, C, ldc, bias, pl.slabs, pl.slab_floats, stream);
 }
 
-// ---- the products of a recurrent layer around its recurrence, all directions in ONE contraction -------
+// ---- the products of a recurrent layer's input projection, all directions in ONE contraction -------
 // (lr_rnn.hip, LR_RNN_PROJ_BF16X3).  R = B*T rows, I input features, GH gate rows per direction, D
 // directions; gates / dG keep the directions side by side in a row (leading dimensions ldgates, ldg).
-// Every product packs all of its operand blocks in one launch (PackList).
-size_t lr_xproj_workspace_bytes(int R, int I, int GH, int D, int H) {
-  if (R <= 0 || I <= 0 || GH <= 0 || D <= 0 || H <= 0) return 0;
-  size_t a = lr_xgemm_workspace_bytes(0, 1, R, D * GH, I);
-  size_t b = lr_xgemm_workspace_bytes(1, 0, D * GH, I, R);
-  if (b > a) a = b;
-  b = lr_xgemm_workspace_bytes(0, 0, R, I, D * GH);
-  if (b > a) a = b;
-  // recurrent weight gradient: D batched products GH x H over K = R (lr_xproj_dwhh) and their split-K slabs
-  b = ((size_t)D * (plane_floats(GH, R, false) + plane_floats(H, R, false)) +
-       pad64((size_t)want_splits(GH, H * D, R) * GH * H * D)) * sizeof(float);
-  if (b > a) a = b;
-  return a;
+// Every product packs all of its operand blocks in one launch (PackList).  (The weight gradients are lr_fgemm
+// jobs straight from dG, x and y: lr_rnn.hip rnn_layer_backward_impl.)
+size_t lr_xproj_workspace_bytes(int R, int I, int GH, int D) {
+  if (R <= 0 || I <= 0 || GH <= 0 || D <= 0) return 0;
+  const size_t a = lr_xgemm_workspace_bytes(0, 1, R, D * GH, I);   // the forward
+  const size_t b = lr_xgemm_workspace_bytes(0, 0, R, I, D * GH);   // dx
+  return a > b ? a : b;
 }
 
 // gates[R][D*GH] = x[R][I] . [W_ih[0]; W_ih[1]]^T + bias[D*GH]
@@ -684,32 +634,12 @@ int lr_xproj_forward(const float* x, int R, int I, const float* const* w_ih, int
   PackList pk;
   const bool direct = x_bf16 && ldp == I;
   if (direct) pl.Ah = (bf16_t*)x;
-  else pk.add(x, I, R, I, 0, pl.Ah, pl.Al, ldp, ldp, 0, 1, x_bf16);
+  else pk.add(x, I, R, I, 0, pl.Ah, pl.Al, ldp, ldp, x_bf16);
   for (int d = 0; d < D; ++d)
     pk.add(w_ih[d], I, GH, I, 0, pl.Bh + (size_t)d * GH * ldp, pl.Bl ? pl.Bl + (size_t)d * GH * ldp : nullptr, ldp, ldp);
   int st = pk.launch(stream);
   if (st != LR_OK) return st;
-  return contract(pl.Ah, pl.Al, pl.Bh, pl.Bl, R, N, I, 1.f, 0.f, gates, nullptr, R, N, bias, pl.slabs, pl.slab_floats,
-                  stream);
-}
-
-// dW_ih[d][GH][I] (beta) = dG[:, d, :GH]^T . x   — rows d*GH.. of one (D*GH) x I product over K = R
-int lr_xproj_dw(const float* dG, int ldg, int dstride, const float* x, int R, int I, int GH, int D,
-                float* const* dw_ih, float beta, int x_exact, int x_bf16, void* workspace, size_t workspace_bytes,
-                hipStream_t stream, int one_product) {
-  const int M = D * GH, ldp = ldp_of(R);
-  if (1 + D > XPACK_MAX) return LR_ERR_UNSUPPORTED;
-  Planes pl;
-  if (!carve(workspace, workspace_bytes, M, I, R, one_product != 0, x_exact != 0 || one_product, &pl)) return LR_ERR_WORKSPACE;
-  PackList pk;
-  for (int d = 0; d < D; ++d)
-    pk.add(dG + (size_t)d * dstride, ldg, R, GH, 1, pl.Ah + (size_t)d * GH * ldp,
-           pl.Al ? pl.Al + (size_t)d * GH * ldp : nullptr, ldp, ldp);
-  pk.add(x, I, R, I, 1, pl.Bh, pl.Bl, ldp, ldp, 0, 1, x_bf16);
-  int st = pk.launch(stream);
-  if (st != LR_OK) return st;
-  return contract(pl.Ah, pl.Al, pl.Bh, pl.Bl, M, I, R, 1.f, beta, dw_ih[0], D > 1 ? dw_ih[1] : nullptr, GH, I, nullptr,
-                  pl.slabs, pl.slab_floats, stream);
+  return contract(pl.Ah, pl.Al, pl.Bh, pl.Bl, R, N, I, 1.f, 0.f, gates, N, bias, pl.slabs, pl.slab_floats, stream);
 }
 
 // dx[R][I] = sum_d dG[:, d, :GH] . W_ih[d]   — one product over K = D*GH
@@ -727,91 +657,8 @@ int lr_xproj_dx(const float* dG, int ldg, int dstride, const float* const* w_ih,
   }
   int st = pk.launch(stream);
   if (st != LR_OK) return st;
-  return contract(pl.Ah, pl.Al, pl.Bh, pl.Bl, R, I, K, 1.f, 0.f, dx, nullptr, R, I, nullptr, pl.slabs, pl.slab_floats,
-                  stream, 1, 0, 0, nullptr, dx_bf16);
-}
-
-// dW_hh[d][G*H][H] (beta) = dGh[:, d]^T . h_prev[:, d], h_prev[b,t] = y[b,t-1] (d = 0) / y[b,t+1] (d = 1), zero
-// across sequence ends.  dG rows hold 4 slots of H per direction; the recurrent side reads slots
-// (0, 1, 3) for the GRU (dr, dz, d(W_hn h + b_hn)) and (0..3) for the LSTM.  The directions are two
-// batches of one launch (operands packed together, one contraction, one split-K combine).
-int lr_xproj_dwhh(const float* dG, int ldg, const float* y, int ldy, int R, int T, int H, int G, int D,
-                  float* const* dw_hh, float beta, void* workspace, size_t workspace_bytes, hipStream_t stream,
-                  int one_product) {
-  const int GH = G * H, ldp = ldp_of(R);
-  if (D > 2 || 3 * D > XPACK_MAX) return LR_ERR_UNSUPPORTED;
-  const size_t fa = plane_floats(GH, R, false), fb = plane_floats(H, R, false);
-  const size_t avail = workspace_bytes / sizeof(float);
-  if (avail < D * (fa + fb)) return LR_ERR_WORKSPACE;
-  float* ws = (float*)workspace;
-  bf16_t* A0 = (bf16_t*)ws;
-  bf16_t* B0 = (bf16_t*)(ws + D * fa);
-  float* slabs = ws + D * (fa + fb);
-  const size_t slab_floats = avail - D * (fa + fb);
-  PackList pk;
-  for (int d = 0; d < D; ++d) {
-    const float* g = dG + (size_t)d * 4 * H;
-    bf16_t* Ah = A0 + (size_t)d * fa * 2;           // fa floats = 2 fa bf16 per batch
-    bf16_t* Al = one_product ? nullptr : Ah + (size_t)GH * ldp;
-    bf16_t* Bh = B0 + (size_t)d * fb * 2;
-    bf16_t* Bl = one_product ? nullptr : Bh + (size_t)H * ldp;
-    if (G == 3) {
-      pk.add(g, ldg, R, 2 * H, 1, Ah, Al, ldp, ldp);
-      pk.add(g + 3 * H, ldg, R, H, 1, Ah + (size_t)2 * H * ldp, Al ? Al + (size_t)2 * H * ldp : nullptr, ldp, ldp);
-    } else {
-      pk.add(g, ldg, R, GH, 1, Ah, Al, ldp, ldp);
-    }
-    pk.add(y + (size_t)d * H, ldy, R, H, 1, Bh, Bl, ldp, ldp, d == 0 ? -1 : 1, T);
-  }
-  int st = pk.launch(stream);
-  if (st != LR_OK) return st;
-  return contract(A0, one_product ? nullptr : A0 + (size_t)GH * ldp, B0, one_product ? nullptr : B0 + (size_t)H * ldp, GH, H,
-                  R, 1.f, beta, dw_hh[0], nullptr, GH, H, nullptr, slabs, slab_floats, stream, D, (int64_t)fa * 2,
-                  (int64_t)fb * 2, D > 1 ? dw_hh[1] : nullptr);
-}
-
-// dW_ih AND dW_hh of a layer whose recurrent side reads the same dG slots as its input side (LSTM: i, f, g, o; the
-// tanh RNN) from ONE pack of dG: the transposed hi / lo planes of dG [D*GH][R] are the A operand of both products
-// (lr_xproj_dw + lr_xproj_dwhh pack them twice: 37 us each at BiLSTM-768).  One pack launch (dG blocks, x, the
-// time-shifted y blocks), two contractions.
-size_t lr_xproj_dw_both_workspace_bytes(int R, int I, int GH, int H, int D) {
-  if (R <= 0 || I <= 0 || GH <= 0 || H <= 0 || D <= 0) return 0;
-  size_t slab = (size_t)want_splits(D * GH, I, R) * D * GH * I;
-  const size_t s2 = (size_t)want_splits(GH, H * D, R) * GH * H * D;
-  if (s2 > slab) slab = s2;
-  return (plane_floats(D * GH, R, false) + plane_floats(I, R, false) + (size_t)D * plane_floats(H, R, false) + pad64(slab)) *
-         sizeof(float);
-}
-int lr_xproj_dw_both(const float* dG, int ldg, int dstride, const float* x, const float* y, int ldy, int R, int T, int I,
-                     int H, int GH, int D, float* const* dw_ih, float* const* dw_hh, float beta, void* workspace,
-                     size_t workspace_bytes, hipStream_t stream) {
-  const int M = D * GH, ldp = ldp_of(R);
-  if (D > 2 || 2 * D + 1 > XPACK_MAX) return LR_ERR_UNSUPPORTED;
-  const size_t fa = plane_floats(M, R, false), fx = plane_floats(I, R, false), fy = plane_floats(H, R, false);
-  const size_t avail = workspace_bytes / sizeof(float);
-  if (avail < fa + fx + D * fy) return LR_ERR_WORKSPACE;
-  float* ws = (float*)workspace;
-  bf16_t* Ah = (bf16_t*)ws;
-  bf16_t* Al = Ah + (size_t)M * ldp;
-  bf16_t* Xh = (bf16_t*)(ws + fa);
-  bf16_t* Xl = Xh + (size_t)I * ldp;
-  bf16_t* Y0 = (bf16_t*)(ws + fa + fx);
-  float* slabs = ws + fa + fx + D * fy;
-  const size_t slab_floats = avail - fa - fx - D * fy;
-  PackList pk;
-  for (int d = 0; d < D; ++d) {
-    pk.add(dG + (size_t)d * dstride, ldg, R, GH, 1, Ah + (size_t)d * GH * ldp, Al + (size_t)d * GH * ldp, ldp, ldp);
-    bf16_t* Yh = Y0 + (size_t)d * fy * 2;
-    pk.add(y + (size_t)d * H, ldy, R, H, 1, Yh, Yh + (size_t)H * ldp, ldp, ldp, d == 0 ? -1 : 1, T);
-  }
-  pk.add(x, I, R, I, 1, Xh, Xl, ldp, ldp);
-  int st = pk.launch(stream);
-  if (st != LR_OK) return st;
-  st = contract(Ah, Al, Xh, Xl, M, I, R, 1.f, beta, dw_ih[0], D > 1 ? dw_ih[1] : nullptr, GH, I, nullptr, slabs, slab_floats,
-                stream);
-  if (st != LR_OK) return st;
-  return contract(Ah, Al, Y0, Y0 + (size_t)H * ldp, GH, H, R, 1.f, beta, dw_hh[0], nullptr, GH, H, nullptr, slabs, slab_floats,
-                  stream, D, (int64_t)GH * ldp, (int64_t)fy * 2, D > 1 ? dw_hh[1] : nullptr);
+  return contract(pl.Ah, pl.Al, pl.Bh, pl.Bl, R, I, K, 1.f, 0.f, dx, I, nullptr, pl.slabs, pl.slab_floats, stream,
+                  dx_bf16);
 }
 
 extern "C" int lr_xgemm(int transA, int transB, int M, int N, int K, float alpha, const float* A, int lda,

@@ -419,6 +419,7 @@ class VideoEncoder(nn.Module):
     if max_len is None:
       max_len = int(frame_lens.max())          # host read iff frame_lens lives on the device
     assert 1 <= max_len <= T
+    assert self.input_projection in ('f32', 'bf16x3', 'bf16x1'), self.input_projection
     # the pixel regime hands the frontend's bf16 features over as they are (LR_RNN_INPUT_STORED_BF16)
     stored_bf16 = (frames.dtype == torch.bfloat16 and self.input_projection in ('bf16x3', 'bf16x1') and self.input_is_bf16
                    and I % 8 == 0)
@@ -436,7 +437,7 @@ class VideoEncoder(nn.Module):
         # operands (include/lipreading_hip.h LR_RNN_PROJ_BF16X3); layer 0's input is bf16-exact
         # when it comes from the bf16 conv frontend
         lmode |= _PROJ_BF16X3 | (_INPUT_BF16_EXACT if (layer == 0 and self.input_is_bf16) else 0)
-        if self.input_projection == 'bf16x1':   # experiment: one bf16 product per GEMM (LR_RNN_PROJ_BF16X1)
+        if self.input_projection == 'bf16x1':   # forward-only experiment: one bf16 product (LR_RNN_PROJ_BF16X1)
           lmode |= _PROJ_BF16X1
         if layer == 0 and stored_bf16:
           lmode |= _INPUT_STORED_BF16
