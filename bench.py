@@ -2,7 +2,7 @@
 """Benchmark of the video->characters hot path on MI355X.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--regime pixels|landmarks|landmarks_attn|all]
-                  [--model gru256|lstm768|lstm700|lstm512|gru800] [--batch B] [--dump-outputs DIR]
+                  [--model gru256|lstm768|lstm700|lstm512|gru800] [--batch B] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic input already resident in HBM:
 (frontend ->) VideoEncoder forward -> CTC 'mean' loss -> backward -> clip_grad_norm_(50) ->
@@ -22,11 +22,15 @@ Two input regimes (SURVEY.md section 8d says they must be reported separately):
              regime plus the CharDecodingStep loop (char_dim 300, '1_layer_nn' attention,
              teacher_forcing_ratio 1, L=31 steps), decoder NLL + CTC, per-module clip, Adam.
 
-Extra objects: `roofline` for the regime's dominant kernel (average launch duration measured live
-with hipEvent pairs that stamp the dispatch on its own stream, in an eager pass right after the
-timed region — hipGraph replays do not re-run the host code that records events) and
-`cpu_baseline` (the oracle, i.e. the reference's op sequence on stock torch CPU ops, timed on this
-host on a bounded sample of the same workload).
+A plain run times the headline regime (pixels, or the one --regime names) and prints its line; with
+--dump-outputs it times every regime whose outputs it writes (all of them by default).  --full runs
+every regime of --regime (default: all, plus the landmarks regime once more on the f32 recurrence)
+and adds what takes runs of its own: `roofline` for each regime's dominant kernel (average launch
+duration measured live with hipEvent pairs that stamp the dispatch on its own stream, in an eager
+pass right after the timed region — hipGraph replays do not re-run the host code that records
+events), each all-reduce bucket timed on its own, the `parity` blocks (HIP path against the
+oracle) and `cpu_baseline` (the oracle, i.e. the reference's op sequence on stock torch CPU ops,
+timed on this host on a bounded sample of the same workload); --model-scaling needs it.
 """
 import argparse
 import ctypes
@@ -569,8 +573,8 @@ def write_outputs(directory, results):
 
 
 def run_regime(args, regime, world, rank, dev, recurrence=None, dump=False):
-  """Builds the model, times `args.steps` steps, measures the dominant kernels.  Returns a dict; with `dump`, its
-  "outputs" hold what the last timed step returned (dump_sample)."""
+  """Builds the model, times `args.steps` steps and, with --full, measures the dominant kernels.  Returns a dict;
+  with `dump`, its "outputs" hold what the last timed step returned (dump_sample)."""
   import torch
   import torch.distributed as dist
   from lipreading_amd import _C
@@ -759,34 +763,36 @@ def run_regime(args, regime, world, rank, dev, recurrence=None, dump=False):
       outputs["decoder_params"] = dec_flat.data[dec_flat.first:]
     outputs = {k: dump_sample(v) for k, v in outputs.items()}
 
-  # roofline leg (after the timed region, same process, same tensors).  Per-kernel durations are taken with the conv
-  # backward on ONE stream: in the timed step a layer's weight gradient runs on a side stream beside its data
-  # gradient (frontend._WGRAD_SIDE_STREAM) — the two then share the chip and each one's duration says nothing about
-  # the kernel itself.
+  # roofline leg, --full only (after the timed region, same process, same tensors).  Per-kernel durations are taken
+  # with the conv backward on ONE stream: in the timed step a layer's weight gradient runs on a side stream beside its
+  # data gradient (frontend._WGRAD_SIDE_STREAM) — the two then share the chip and each one's duration says nothing
+  # about the kernel itself.
   from lipreading_amd import frontend as _FE
-  from lipreading_amd import encoder as _ENC
-  _side_saved, _FE._WGRAD_SIDE_STREAM = _FE._WGRAD_SIDE_STREAM, False
-  # ... and the recurrent layers' weight-gradient GEMMs too (encoder.overlap_weight_grads puts them on a side stream,
-  # where they ran beside layer 3's backward: round 3's conv3_wgrad read 84 us on one visit and 199 on the next)
-  _ovl_saved, _ENC.overlap_weight_grads = _ENC.overlap_weight_grads, False
-  _C.check(L.lr_profile_enable(1), "lr_profile_enable")
-  n_prof = min(args.steps, 20 if not pixels else 5)
-  for _ in range(n_prof):    # eager launches of the same step (graph replays do not re-run the host code that records events)
-    if sync is not None:
-      with sync.hold():       # no bucket goes out from the hooks: this leg only samples kernel durations
-        step(graphs=None)
-    else:
-      step(graphs=None)
-  torch.cuda.synchronize()
-  L.lr_profile_enable(0)
-  _FE._WGRAD_SIDE_STREAM = _side_saved
-  _ENC.overlap_weight_grads = _ovl_saved
+  _side_saved = _FE._WGRAD_SIDE_STREAM
   prof = {}
-  for which, name in SLOTS.items():
-    ms, n = ctypes.c_float(0), ctypes.c_int(0)
-    L.lr_profile_read(which, ctypes.byref(ms), ctypes.byref(n))
-    if n.value:
-      prof[name] = (ms.value / n.value * 1e3, n.value / n_prof)   # us per launch, samples per step
+  if args.full:
+    from lipreading_amd import encoder as _ENC
+    _FE._WGRAD_SIDE_STREAM = False
+    # ... and the recurrent layers' weight-gradient GEMMs too (encoder.overlap_weight_grads puts them on a side
+    # stream, where they ran beside layer 3's backward: round 3's conv3_wgrad read 84 us on one visit and 199 on the next)
+    _ovl_saved, _ENC.overlap_weight_grads = _ENC.overlap_weight_grads, False
+    _C.check(L.lr_profile_enable(1), "lr_profile_enable")
+    n_prof = min(args.steps, 20 if not pixels else 5)
+    for _ in range(n_prof):    # eager launches of the same step (graph replays do not re-run the host code that records events)
+      if sync is not None:
+        with sync.hold():       # no bucket goes out from the hooks: this leg only samples kernel durations
+          step(graphs=None)
+      else:
+        step(graphs=None)
+    torch.cuda.synchronize()
+    L.lr_profile_enable(0)
+    _FE._WGRAD_SIDE_STREAM = _side_saved
+    _ENC.overlap_weight_grads = _ovl_saved
+    for which, name in SLOTS.items():
+      ms, n = ctypes.c_float(0), ctypes.c_int(0)
+      L.lr_profile_read(which, ctypes.byref(ms), ctypes.byref(n))
+      if n.value:
+        prof[name] = (ms.value / n.value * 1e3, n.value / n_prof)   # us per launch, samples per step
 
   el = torch.tensor(elapsed_all, dtype=torch.float64, device=dev)
   if DIST_ON:
@@ -795,9 +801,9 @@ def run_regime(args, regime, world, rank, dev, recurrence=None, dump=False):
   elapsed = elapsed_all[(len(elapsed_all) - 1) // 2]   # median (lower middle for an even count)
   elapsed_min = elapsed_all[0]
 
-  # the data-parallel exchange on its own: each bucket's all-reduce timed on the side stream it runs on
+  # the data-parallel exchange on its own (--full): each bucket's all-reduce timed on the side stream it runs on
   bucket_us = None
-  if sync is not None:
+  if sync is not None and args.full:
     bucket_us = []
     for lo, hi in sync.bounds:
       buf = flat.grad[lo:hi]
@@ -1070,10 +1076,11 @@ def main():
   ap.add_argument("--warmup", type=int, default=3)
   ap.add_argument("--model", choices=sorted(MODELS), default="gru256")
   ap.add_argument("--batch", type=int, default=32, help="per-GPU batch (weak scaling)")
-  ap.add_argument("--regime", choices=["pixels", "landmarks", "landmarks_attn", "pixels_tfm", "both", "all"], default="all",
-                  help="all (default): headline = pixels (the metric's (B,75,3,96,96) shape); the "
+  ap.add_argument("--regime", choices=["pixels", "landmarks", "landmarks_attn", "pixels_tfm", "both", "all"], default=None,
+                  help="the regimes to time; the first one is the headline.  Default: pixels (the metric's "
+                       "(B,75,3,96,96) shape) alone; all with --full or --dump-outputs, where the "
                        "reference-faithful landmarks regimes (encoder+CTC, and the whole step with the "
-                       "attention decoder) are reported under 'regimes'")
+                       "attention decoder) and pixels_tfm are reported under 'regimes'")
   ap.add_argument("--layers", type=int, default=None, help="recurrent layers (default 1; 2 for pixels)")
   ap.add_argument("--no-graph", action="store_true",
                   help="launch every kernel eagerly instead of replaying a captured hipGraph")
@@ -1088,17 +1095,24 @@ def main():
                        "recurrent layer every shipped config has, nn.LSTM / nn.GRU apply no dropout (it acts BETWEEN "
                        "layers): accepted so that a config can be quoted as shipped, and passed on to both modules")
   ap.add_argument("--model-scaling", action="store_true",
-                  help="one GPU only: also time the pixel step at the per-rank batches of a strong-scaling run (8, 16, 64) and "
-                       "print a MODELLED (not measured) 2/4/8-GPU weak and strong efficiency under `scaling_model`")
-  ap.add_argument("--no-cpu-baseline", action="store_true")
+                  help="with --full, one GPU only: also time the pixel step at the per-rank batches of a strong-scaling run "
+                       "(8, 16, 64) and print a MODELLED (not measured) 2/4/8-GPU weak and strong efficiency under "
+                       "`scaling_model`")
+  ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the parity blocks and CPU baselines")
   ap.add_argument("--cpu-budget", type=float, default=12.0,
                   help="seconds of timed CPU-oracle steps per regime (never fewer than 10 steps)")
   ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                   help="after the timed steps, write what each regime's last timed step returned (losses, status word, "
                        "updated weights; a fixed seeded sample of large arrays) to DIR/<regime>_<name>.npy")
+  ap.add_argument("--full", action="store_true",
+                  help="every regime of --regime (default all) and, for each, the measurements and checks beyond its "
+                       "timed steps: roofline leg (per-kernel durations), all-reduce buckets on their own, HIP-vs-oracle "
+                       "parity and the CPU baseline; the landmarks regime once more on the f32 recurrence")
   args = ap.parse_args()
   if args.steps < 1 or args.warmup < 0:
     ap.error("--steps must be at least 1 and --warmup at least 0")
+  if args.model_scaling and not args.full:
+    ap.error("--model-scaling needs --full (the model takes the conv backward's kernel durations from the roofline leg)")
 
   if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
     # started as plain `python bench.py --gpus N`: become the launcher of N ranks (one per GPU)
@@ -1123,13 +1137,16 @@ def main():
     os.environ.setdefault("MASTER_PORT", "29617")
     dist.init_process_group(backend="nccl", rank=rank, world_size=world, device_id=dev)
 
+  # a plain run times the headline alone; --dump-outputs writes every regime's outputs, so it times them all
+  many = args.full or args.dump_outputs is not None
+  regime = args.regime or ("all" if many else "pixels")
   order = {"both": ["pixels", "landmarks"],
-           "all": ["pixels", "landmarks", "landmarks_attn", "pixels_tfm"]}.get(args.regime, [args.regime])
+           "all": ["pixels", "landmarks", "landmarks_attn", "pixels_tfm"]}.get(regime, [regime])
   dump = args.dump_outputs is not None and rank == 0
   results = [run_regime(args, r, world, rank, dev, dump=dump) for r in order]
   # the reference-faithful regime once more on the OTHER recurrence: the per-step fp32 launches (every shape's fallback)
   options = {}
-  if "landmarks" in order and args.regime in ("all", "landmarks"):
+  if many and "landmarks" in order and regime in ("all", "landmarks"):
     options["f32"] = run_regime(args, "landmarks", world, rank, dev, recurrence="f32", dump=dump)
   if dump:
     write_outputs(args.dump_outputs, [(r["regime"], r) for r in results] +
@@ -1159,18 +1176,20 @@ def main():
         "timing": {"repeats": head["repeats"], "ms_per_step_median": head["ms_per_step"],
                    "ms_per_step_min": head["ms_per_step_min"],
                    "note": "the timed region of exactly `steps` steps is repeated back to back; value is the median repeat"},
-        "rccl_ranks": head["rccl_ranks"], "all_reduce_buckets": head["all_reduce_buckets"],
+        "rccl_ranks": head["rccl_ranks"],
         "pair_errors": sum(r.get("pair_errors", 0) for r in results),
-        "roofline": head["roofline"], "ctc": head.get("ctc"),
     }
+
+    def extras(r):   # what --full measured beside a regime's timed steps
+      return {"all_reduce_buckets": r["all_reduce_buckets"], "roofline": r["roofline"], "ctc": r.get("ctc")} if args.full else {}
+    out.update(extras(head))
     if head.get("decoder_recurrence"):
       out["config"]["decoder_recurrence"] = head["decoder_recurrence"]
     if len(results) > 1:
-      out["regimes"] = {r["regime"]: {"value": r["value"], "unit": "frames/s", "ms_per_step": r["ms_per_step"],
-                                      "ms_per_step_min": r["ms_per_step_min"],
-                                      "workload": r["workload"], "final_loss": round(r["loss"], 6),
-                                      "all_reduce_buckets": r["all_reduce_buckets"],
-                                      "roofline": r["roofline"], "ctc": r.get("ctc")} for r in results[1:]}
+      out["regimes"] = {r["regime"]: dict({"value": r["value"], "unit": "frames/s", "ms_per_step": r["ms_per_step"],
+                                           "ms_per_step_min": r["ms_per_step_min"],
+                                           "workload": r["workload"], "final_loss": round(r["loss"], 6)}, **extras(r))
+                        for r in results[1:]}
     if options:
       lm = out["regimes"]["landmarks"] if "landmarks" in out.get("regimes", {}) else (out if head["regime"] == "landmarks" else None)
       if lm is not None:
@@ -1194,7 +1213,7 @@ def main():
         by = (r.get("roofline") or {}).get("avg_launch_us_by_kernel") or {}
         legs[b] = {"ms": r["ms_per_step"], "conv_backward_us": sum(by.get(k, 0.0) for k in conv_bwd)}
       out["scaling_model"] = scaling_model(legs)
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
       # parity first (the metric's "+ CTC-loss parity"): HIP vs oracle on identical inputs and weights
       by_regime = {r["regime"]: r for r in results}
       par = {}

@@ -4,7 +4,7 @@ set -u
 OUT=gpurun_out; mkdir -p $OUT; TAG=${1:-ab}
 timeout 900 python -m pytest tests/test_gpu_frontend.py -m gpu -q -x > $OUT/${TAG}_pytest.log 2>&1
 echo "pytest exit $?"; grep -E "^(FAILED|ERROR)|passed|failed" $OUT/${TAG}_pytest.log | tail -5
-timeout 600 python bench.py --regime pixels --no-cpu-baseline > $OUT/${TAG}_bench.log 2>&1
+timeout 600 python bench.py --full --regime pixels --no-cpu-baseline > $OUT/${TAG}_bench.log 2>&1
 tail -1 $OUT/${TAG}_bench.log > $OUT/${TAG}_bench.json
 python - $TAG <<'PY'
 import json, sys

@@ -19,7 +19,7 @@ one in-tree | tee -a $OUT/ab_conv1.txt
 BEST=$(grep "weight gradient" $OUT/ab_conv1.txt | grep -v "^in-tree" | sed 's/^\([^:]*\):.*median \([0-9.]*\) us.*/\2 \1/' | sort -n | head -1 | cut -d' ' -f2)
 echo "fastest weight gradient: $BEST"
 line() {
-  timeout 300 python bench.py --regime pixels --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+  timeout 300 python bench.py --full --regime pixels --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 r = d.get('roofline') or {}

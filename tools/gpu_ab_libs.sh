@@ -13,7 +13,7 @@ if [ -n "$EXPR" ]; then
   timeout 900 python -m pytest tests -m gpu -q -x -k "$EXPR" 2>&1 | tail -2
 fi
 line() {
-  timeout 300 python bench.py --regime pixels --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+  timeout 300 python bench.py --full --regime pixels --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 r = d.get('roofline') or {}

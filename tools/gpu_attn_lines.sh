@@ -8,12 +8,12 @@ R=$PWD; TAG=${1:-r04}; OUT=$R/gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp
 A1="--regime landmarks_attn --model lstm512 --char-dim 256"
 A2="--regime landmarks_attn --model lstm700uni --char-dim 300 --no-ctc"
 for b in 32 4; do
-  timeout 600 python bench.py $A1 --batch $b 2>$OUT/attn_err.log | tail -1 > $OUT/${TAG}_bench_attn_lstm512_b$b.json || tail -5 $OUT/attn_err.log
-  timeout 600 python bench.py $A2 --batch $b 2>$OUT/attn_err.log | tail -1 > $OUT/${TAG}_bench_attn_lstm700uni_b$b.json || tail -5 $OUT/attn_err.log
+  timeout 600 python bench.py --full $A1 --batch $b 2>$OUT/attn_err.log | tail -1 > $OUT/${TAG}_bench_attn_lstm512_b$b.json || tail -5 $OUT/attn_err.log
+  timeout 600 python bench.py --full $A2 --batch $b 2>$OUT/attn_err.log | tail -1 > $OUT/${TAG}_bench_attn_lstm700uni_b$b.json || tail -5 $OUT/attn_err.log
 done
 kt() {
   local name=$1; shift
-  (cd /tmp && rocprofv3 --kernel-trace --stats -d "$OUT/kt_$name" -o kt -- python "$R/bench.py" "$@" --no-graph --steps 10 --warmup 2 --repeats 1 --no-cpu-baseline > /dev/null 2>&1)
+  (cd /tmp && rocprofv3 --kernel-trace --stats -d "$OUT/kt_$name" -o kt -- python "$R/bench.py" --full "$@" --no-graph --steps 10 --warmup 2 --repeats 1 --no-cpu-baseline > /dev/null 2>&1)
   python tools/rocpd_summary.py "$(find "$OUT/kt_$name" -name '*.db' | head -1)" 40 > "$OUT/${TAG}_${name}_kernel_stats.txt"
   rm -rf "$OUT/kt_$name"
 }

@@ -1,9 +1,10 @@
 #!/usr/bin/env bash
-# `python bench.py` exactly as the driver runs it (no flags), timed by the shell; the line -> gpurun_out/<tag>_bench_default_head.json
+# `python bench.py --full` (every regime, its roofline leg, parity and CPU baseline), timed by the shell; the line ->
+# <tag>_bench_default_head.json in the output folder
 set -u
 TAG=${1:-r05}; OUT=gpurun_out; mkdir -p $OUT
 t0=$(date +%s.%N)
-python bench.py 2> $OUT/${TAG}_head_err.log | tail -1 > $OUT/${TAG}_bench_default_head.json
+python bench.py --full 2> $OUT/${TAG}_head_err.log | tail -1 > $OUT/${TAG}_bench_default_head.json
 t1=$(date +%s.%N)
 python - <<PY
 import json

@@ -6,7 +6,7 @@ OUT=gpurun_out; mkdir -p $OUT
 T=$1; shift
 if [ -n "$T" ]; then timeout 900 python -m pytest -m gpu -q -x $T 2>&1 | tail -15; fi
 line() {
-  timeout 300 python bench.py "$@" --no-cpu-baseline 2>$OUT/quick_err.log | tail -1 | python -c "
+  timeout 300 python bench.py --full "$@" --no-cpu-baseline 2>$OUT/quick_err.log | tail -1 | python -c "
 import json, sys
 try:
   d = json.loads(sys.stdin.read())

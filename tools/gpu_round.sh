@@ -8,9 +8,9 @@ mkdir -p $OUT
 timeout 1200 python -m pytest tests -m gpu -x -q -s --durations=15 > $OUT/${TAG}_pytest_gpu.log 2>&1
 echo "pytest exit $?" >> $OUT/${TAG}_pytest_gpu.log
 grep -E "parity|vs oracle|split vs|passed|failed|FAILED|pytest exit" $OUT/${TAG}_pytest_gpu.log | tail -25
-timeout 900 python bench.py > $OUT/${TAG}_bench_default.log 2>&1
+timeout 900 python bench.py --full > $OUT/${TAG}_bench_default.log 2>&1
 tail -1 $OUT/${TAG}_bench_default.log > $OUT/${TAG}_bench_default.json
-LIPREADING_BENCH_FORCE_DIST=1 timeout 600 python bench.py --no-cpu-baseline --repeats 3 > $OUT/${TAG}_bench_forcedist.log 2>&1
+LIPREADING_BENCH_FORCE_DIST=1 timeout 600 python bench.py --full --no-cpu-baseline --repeats 3 > $OUT/${TAG}_bench_forcedist.log 2>&1
 tail -1 $OUT/${TAG}_bench_forcedist.log > $OUT/${TAG}_bench_forcedist.json
 python -c "
 import json,sys

@@ -3,7 +3,7 @@
 # 55c447f).  Every argument is a step, run in order; the output of each goes to gpurun_out/<tag>_*.  Steps:
 #   tag=<name>                      prefix of the files written (default: visit)
 #   test=<pytest args>              python -m pytest -m gpu -q -x <args>      -> <tag>_pytest_<n>.log, last lines echoed
-#   line=<name>:<bench args>        python bench.py <args> --no-cpu-baseline  -> <tag>_bench_<name>.json, one summary line
+#   line=<name>:<bench args>        python bench.py --full <args> --no-cpu-baseline  -> <tag>_bench_<name>.json, one summary line
 #   fullline=<name>:<bench args>    the same WITH the cpu baseline leg
 #   env=<VAR=val,...>               environment for the steps that follow (env= alone clears it)
 #   lib=<variant>                   LIPREADING_HIP_LIB = lipreading_amd/_lib/alt/<variant>.so for the steps that follow
@@ -57,20 +57,20 @@ for step in "$@"; do
       name=${arg%%:*}; bargs=${arg#*:}; f=$OUT/${TAG}_bench_$name.json
       extra="--no-cpu-baseline"; [ "$kind" = fullline ] && extra=""
       # shellcheck disable=SC2086
-      env ${ENVS[@]+"${ENVS[@]}"} timeout 900 python bench.py $bargs $extra 2> "${f%.json}.err" | tail -1 > "$f"
+      env ${ENVS[@]+"${ENVS[@]}"} timeout 900 python bench.py --full $bargs $extra 2> "${f%.json}.err" | tail -1 > "$f"
       summarise "$f" "line[$name ${ENVS[*]:-} ${LIPREADING_HIP_LIB:+lib=$(basename "$LIPREADING_HIP_LIB")}]" ;;
     kt)
       name=${arg%%:*}; bargs=${arg#*:}
       # shellcheck disable=SC2086
       (cd /tmp && env ${ENVS[@]+"${ENVS[@]}"} timeout 900 rocprofv3 --kernel-trace --stats -d "$OUT/kt_$name" -o kt -- \
-        python "$R/bench.py" $bargs --no-graph --no-cpu-baseline --steps 10 --warmup 2 --repeats 1 > /dev/null 2>&1)
+        python "$R/bench.py" --full $bargs --no-graph --no-cpu-baseline --steps 10 --warmup 2 --repeats 1 > /dev/null 2>&1)
       python tools/rocpd_summary.py "$(find "$OUT/kt_$name" -name '*.db' | head -1)" 60 > "$OUT/${TAG}_${name}_kernel_stats.txt"
       rm -rf "$OUT/kt_$name"; head -30 "$OUT/${TAG}_${name}_kernel_stats.txt" | cut -c1-160 ;;
     tl)
       name=${arg%%:*}; rest=${arg#*:}; anchor=${rest%%:*}; bargs=${rest#*:}
       # shellcheck disable=SC2086
       (cd /tmp && env ${ENVS[@]+"${ENVS[@]}"} timeout 900 rocprofv3 --kernel-trace -d "$OUT/tl_$name" -o kt -- \
-        python "$R/bench.py" $bargs --steps 8 --warmup 2 --repeats 1 --no-cpu-baseline > /dev/null 2>&1)
+        python "$R/bench.py" --full $bargs --steps 8 --warmup 2 --repeats 1 --no-cpu-baseline > /dev/null 2>&1)
       DB=$(find "$OUT/tl_$name" -name '*.db' | head -1)
       python tools/rocpd_timeline.py "$DB" "$anchor" "${TL_STEP:--9}" > "$OUT/${TAG}_${name}_step_timeline.txt"
       python tools/rocpd_summary.py "$DB" 60 > "$OUT/${TAG}_${name}_tl_kernel_stats.txt"

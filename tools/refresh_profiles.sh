@@ -38,7 +38,7 @@ kt() {   # name, bench args...
   # gradient beside its data gradient and the recurrent layers' weight-gradient GEMMs beside the conv backward, and two
   # kernels sharing the chip have no durations of their own)
   (cd /tmp && LIPREADING_CONV_WGRAD_SIDE=0 LIPREADING_OVERLAP_WGRAD=0 rocprofv3 --kernel-trace --stats -d "$OUT/kt_$name" -o kt -- \
-     python "$R/bench.py" "$@" --no-graph --steps 15 --warmup 2 --repeats 1 --no-cpu-baseline > /dev/null 2>&1)
+     python "$R/bench.py" --full "$@" --no-graph --steps 15 --warmup 2 --repeats 1 --no-cpu-baseline > /dev/null 2>&1)
   python tools/rocpd_summary.py "$(find "$OUT/kt_$name" -name '*.db' | head -1)" 60 > "$OUT/${TAG}_${name}_kernel_stats.txt"
   rm -rf "$OUT/kt_$name"
 }
@@ -49,7 +49,7 @@ tl() {   # name, anchor kernel, step index, bench args...: one step of the TIMED
          # untimed eager-versus-replay probe, with staging copies the timed steps do not have.)
   local name=$1 anchor=$2 which=$3; shift 3
   (cd /tmp && rocprofv3 --kernel-trace -d "$OUT/tl_$name" -o kt -- \
-     python "$R/bench.py" "$@" --steps 8 --warmup 2 --repeats 1 --no-cpu-baseline > /dev/null 2>&1)
+     python "$R/bench.py" --full "$@" --steps 8 --warmup 2 --repeats 1 --no-cpu-baseline > /dev/null 2>&1)
   python tools/rocpd_timeline.py "$(find "$OUT/tl_$name" -name '*.db' | head -1)" "$anchor" $which > "$OUT/${TAG}_${name}_step_timeline.txt"
   rm -rf "$OUT/tl_$name"
 }
@@ -59,40 +59,40 @@ pmc() {   # name, counter list, filters..., -- bench args
   while [ "$1" != "--" ]; do filters+=("$1"); shift; done
   shift
   (cd /tmp && LIPREADING_CONV_WGRAD_SIDE=0 LIPREADING_OVERLAP_WGRAD=0 rocprofv3 --pmc $counters -d "$OUT/pmc_$name" -o pm -- \
-     python "$R/bench.py" "$@" --no-graph --steps 2 --warmup 1 --repeats 1 --no-cpu-baseline > /dev/null 2>&1)
+     python "$R/bench.py" --full "$@" --no-graph --steps 2 --warmup 1 --repeats 1 --no-cpu-baseline > /dev/null 2>&1)
   python tools/rocpd_pmc.py "$(find "$OUT/pmc_$name" -name '*.db' | head -1)" "${filters[@]}" > "$OUT/${TAG}_${suffix}.txt"
   rm -rf "$OUT/pmc_$name"
 }
 
 # which kernels these artefacts are of (bench.py quotes the PMC figures only on a build with the same fingerprint)
 python -c "from lipreading_amd import _build; print(_build._fingerprint())" > "$OUT/${TAG}_source_fingerprint.txt"
-python bench.py 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_default.json"
+python bench.py --full 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_default.json"
 kt pixels --regime pixels
 for c in FETCH_SIZE WRITE_SIZE; do pmc px_$c $c pixels_pmc_$c -- --regime pixels; done
 tl pixels conv1_fwd -9 --regime pixels
 # the per-rank shapes of a data-parallel run of BASELINE configs[3] (64 clips): the whole batch on one GPU, and 8 per rank
 for b in 64 8; do
-  python bench.py --regime pixels --batch $b --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_pixels_b$b.json"
+  python bench.py --full --regime pixels --batch $b --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_pixels_b$b.json"
   tl pixels_b$b conv1_fwd -9 --regime pixels --batch $b
 done
-python bench.py --regime pixels --model-scaling --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_scaling_model.json"
+python bench.py --full --regime pixels --model-scaling --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_scaling_model.json"
 pmc clk "GRBM_GUI_ACTIVE GRBM_COUNT" pixels_pmc_clock conv_ conv1_ rnnc_ xgemm -- --regime pixels
 tl pixels_tfm conv1_fwd -9 --regime pixels_tfm
 kt pixels_tfm --regime pixels_tfm
-python bench.py --regime pixels_tfm --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_pixels_tfm.json"
+python bench.py --full --regime pixels_tfm --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_pixels_tfm.json"
 for c in FETCH_SIZE WRITE_SIZE; do pmc tfm_$c $c pixels_tfm_pmc_$c tfm_rb attn_fused fgemm -- --regime pixels_tfm; done
 pmc sq6 "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY" pixels_tfm_pmc_SQ_pass1 tfm_rb attn_fused fgemm -- --regime pixels_tfm
 if [ -f lipreading_amd/_lib/alt/rbtime.so ]; then
   LIPREADING_HIP_LIB=$R/lipreading_amd/_lib/alt/rbtime.so python tools/probes/rb_timing.py > "$OUT/${TAG}_rowblock_phase_timing.txt" 2>&1
 fi
-LIPREADING_BENCH_FORCE_DIST=1 python bench.py --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_forcedist.json"
+LIPREADING_BENCH_FORCE_DIST=1 python bench.py --full --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_forcedist.json"
 pmc sq1 "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY" pixels_pmc_SQ_pass1 conv_ conv1_ rnnc_ xgemm -- --regime pixels
 pmc sq2 "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_INSTS_MFMA" pixels_pmc_SQ_pass2 conv_ conv1_ rnnc_ xgemm -- --regime pixels
 # where the conv kernels' wave cycles go: parked (s_waitcnt / barrier), issue-stalled, or issuing — and in which pipe
 pmc sq2b "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_INSTS_SALU" pixels_pmc_SQ_pass3 conv_ conv1_ -- --regime pixels
 if [ "$ONLY" != "pixels" ]; then
   for m in gru256 lstm768 lstm700 lstm512 gru800; do
-    python bench.py --regime landmarks --model $m 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_$m.json"
+    python bench.py --full --regime landmarks --model $m 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_$m.json"
   done
   kt gru256 --regime landmarks --model gru256
   kt lstm768 --regime landmarks --model lstm768
@@ -101,10 +101,10 @@ if [ "$ONLY" != "pixels" ]; then
   # the reference's dominant flag-file family as shipped (config/archive/experiments/ecd/*: BiLSTM-768, char_dim 256,
   # attention none, rnn_dropout 0.3) at 32 and at the files' own batch of 128
   for b in 32 128; do
-    python bench.py --regime landmarks_attn --model lstm768 --attention none --char-dim 256 --rnn-dropout 0.3 --batch $b 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_ecd_lstm768_b$b.json"
+    python bench.py --full --regime landmarks_attn --model lstm768 --attention none --char-dim 256 --rnn-dropout 0.3 --batch $b 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_ecd_lstm768_b$b.json"
   done
   # config/train/attn/attention_type as shipped (BiLSTM-512 -> LSTM-1024, 1_layer_nn, char_dim 256) at B = 32
-  python bench.py --regime landmarks_attn --model lstm512 --char-dim 256 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_attn_lstm512_b32.json"
+  python bench.py --full --regime landmarks_attn --model lstm512 --char-dim 256 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_attn_lstm512_b32.json"
   kt ecd_lstm768_b32 --regime landmarks_attn --model lstm768 --attention none --char-dim 256 --batch 32
   kt ecd_lstm768_b128 --regime landmarks_attn --model lstm768 --attention none --char-dim 256 --batch 128
   for c in FETCH_SIZE WRITE_SIZE; do
@@ -113,11 +113,11 @@ if [ "$ONLY" != "pixels" ]; then
   pmc sq5 "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY" ecd_lstm768_pmc_SQ_pass1 rnng_ rnnc_ fgemm -- --regime landmarks_attn --model lstm768 --attention none --char-dim 256 --batch 32
   for a in "gru256 64" "gru256 128" "lstm512 64"; do
     set -- $a
-    python bench.py --regime landmarks --model $1 --batch $2 --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_$1_b$2.json"
+    python bench.py --full --regime landmarks --model $1 --batch $2 --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_$1_b$2.json"
   done
   # sixteen samples per cluster (BiLSTM-768 / 700 past B = 32)
   for b in 64 128; do
-    python bench.py --regime landmarks --model lstm768 --batch $b --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_lstm768_b$b.json"
+    python bench.py --full --regime landmarks --model lstm768 --batch $b --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_lstm768_b$b.json"
   done
   tl ecd_lstm768_b32 step_begin_ctc 8 --regime landmarks_attn --model lstm768 --attention none --char-dim 256 --batch 32
   if [ -f lipreading_amd/_lib/alt/gridtime.so ]; then
