@@ -489,6 +489,30 @@ int lr_decoder_beam_search(int mode, int attn_type, const lr_decoder_params* par
                            int32_t* rounds_host, void* workspace, size_t workspace_bytes, int B, int T, int Hd, int Cd,
                            int V, int A, lr_stream_t stream);
 
+/* Joint CTC/attention beam search (Watanabe et al. 2017): the search above, each hypothesis scored
+ * (1 - ctc_weight) * (attention log-prob) + ctc_weight * (CTC prefix log-prob), the CTC term computed on the device
+ * in float64 from the encoder's CTC head.  Rule, structure and costs: lipreading_amd/csrc/lr_attn_beam.hip
+ * (DESIGN.md §15).  Arguments as lr_decoder_beam_search, plus
+ *   ctc_lp               fp32 CTC log-probs, element (b, t, c) at ctc_lp[b*stride_b + t*stride_t + c] (strides in
+ *                        elements; the class dimension contiguous), C = V + 1 classes, class v + 1 = token v
+ *   blank                must be 0
+ *   ctc_weight           lambda in [0, 1]; at 0 the result is lr_decoder_beam_search's
+ *   pre_beam             P, the candidates per hypothesis: min(K, V - 2) <= P <= min(64, V - 2)
+ * out_scores are the joint scores.  Precondition: 1 <= enc_lens[b] <= T (as the attention needs; the CTC terms clamp
+ * it to stay in bounds).  Limits: those above and T <= 65535 (else LR_ERR_UNSUPPORTED); C != V + 1, blank != 0 or a
+ * weight outside [0, 1] (NaN included) is LR_ERR_INVALID_ARG.  The workspace query takes the search's sizes plus C
+ * and P (its size does not depend on the weight) and returns 0 for every request the search rejects. */
+size_t lr_decoder_joint_beam_workspace_bytes(int mode, int attn_type, int num_layers, int B, int K, int Lmax, int T,
+                                             int Hd, int Cd, int V, int A, int C, int pre_beam);
+int lr_decoder_joint_beam_search(int mode, int attn_type, const lr_decoder_params* params_host,
+                                 const lr_decoder_upper* upper_host, const float* enc, const int32_t* enc_lens,
+                                 const float* h0, const float* c0, const float* ctc_lp, int64_t stride_b,
+                                 int64_t stride_t, int C, int blank, double ctc_weight, int pre_beam, int bos, int eos,
+                                 int pad, int beam_width, int max_label_len, int poll_every, int32_t* out_ids,
+                                 int32_t* out_lens, float* out_scores, int32_t* rounds_host, void* workspace,
+                                 size_t workspace_bytes, int B, int T, int Hd, int Cd, int V, int A,
+                                 lr_stream_t stream);
+
 /* The decoder loss of the train loop (train_better_model.py:62,65): over the R = B*L (sample, step) rows,
  * -sum_r log_probs[r][label_r] for label_r != ignore_index (F.nll_loss(ignore_index=PAD, reduction='sum') summed
  * over the steps) divided by the number of such rows ((labels != PAD).sum()).  labels: int64, row (b, i) at

@@ -10,33 +10,56 @@ import torch
 from .data import BOS
 
 
-def encode_for_beam(encoder, frames, frame_lens, device):
-  """One encoder pass over the batch -> (hidden (B, T, Hd), frame_lens on the device, final_state)."""
+def encode_for_beam(encoder, frames, frame_lens, device, with_ctc=False):
+  """One encoder pass over the batch -> (hidden (B, T, Hd), frame_lens on the device, final_state), and with
+  with_ctc=True the CTC head's log-probs (B, T, V+1) of the same pass as a fourth item."""
+  if with_ctc:
+    need_ctc_head(encoder)
   max_len = int(frame_lens.max()) if not frame_lens.is_cuda else None
   frame_lens_d = frame_lens.to(device)
   out = encoder(frames.to(device), frame_lens_d, max_len=max_len)
   hidden, state = (out[1], out[2]) if encoder.enable_ctc else (out[0], out[1])
+  if with_ctc:
+    return hidden, frame_lens_d, state, out[0]
   return hidden, frame_lens_d, state
 
 
-def best_ids(decoding_step, hidden, frame_lens, state, beam_width, max_label_len):
-  """The best hypothesis of every utterance as host lists of token ids (the final EOS included when reached)."""
+def need_ctc_head(encoder):
+  """The joint search reads the encoder's CTC head: raise if it has none."""
+  if not getattr(encoder, "enable_ctc", False):
+    raise ValueError("joint CTC/attention decoding (ctc_weight > 0) needs an encoder built with enable_ctc=True")
+
+
+def best_ids(decoding_step, hidden, frame_lens, state, beam_width, max_label_len, ctc_log_probs=None,
+             ctc_weight=0.0, pre_beam=None):
+  """The best hypothesis of every utterance as host lists of token ids (the final EOS included when reached);
+  with ctc_log_probs, of the joint CTC/attention search."""
+  joint = {} if ctc_log_probs is None else dict(ctc_log_probs=ctc_log_probs, ctc_weight=ctc_weight,
+                                                 pre_beam=pre_beam)
   ids, lens, _ = decoding_step.beam_search(hidden, frame_lens, state, beam_width=beam_width,
-                                           max_label_len=max_label_len)
+                                           max_label_len=max_label_len, **joint)
   ids, lens = ids[:, 0].cpu(), lens[:, 0].cpu()
   return [ids[b, :int(lens[b])].tolist() for b in range(ids.shape[0])]
 
 
 def inference(encoder, decoding_step, frames, frame_lens, chars, char_lens, device, char2idx, beam_width=5,
-              max_label_len=100):
+              max_label_len=100, ctc_weight=0.0):
   """analysis.py:12-66.  Returns (outputs, gt): outputs[i] = '<BOS>' + the best hypothesis's characters (with
-  '<EOS>' if it reached one), gt[i] = chars[i][:char_lens[i]] joined."""
+  '<EOS>' if it reached one), gt[i] = chars[i][:char_lens[i]] joined.  ctc_weight > 0 runs the joint CTC/attention
+  search on the CTC head of the same encoder pass (the encoder needs enable_ctc)."""
+  if ctc_weight > 0:
+    need_ctc_head(encoder)
   idx2char = {val: key for key, val in char2idx.items()}
   encoder.eval()
   decoding_step.eval()
   with torch.no_grad():
-    hidden, lens_d, state = encode_for_beam(encoder, frames, frame_lens, device)
-    best = best_ids(decoding_step, hidden, lens_d, state, beam_width, max_label_len)
+    if ctc_weight > 0:
+      hidden, lens_d, state, y = encode_for_beam(encoder, frames, frame_lens, device, with_ctc=True)
+      best = best_ids(decoding_step, hidden, lens_d, state, beam_width, max_label_len, ctc_log_probs=y,
+                      ctc_weight=ctc_weight)
+    else:
+      hidden, lens_d, state = encode_for_beam(encoder, frames, frame_lens, device)
+      best = best_ids(decoding_step, hidden, lens_d, state, beam_width, max_label_len)
   outputs = [''.join(idx2char[int(i)] for i in [char2idx[BOS]] + h) for h in best]
   chars, char_lens = chars.cpu(), char_lens.cpu()
   gt = [''.join(idx2char[int(c)] for c in chars[i][:int(char_lens[i])]) for i in range(len(best))]

@@ -220,6 +220,31 @@ class _AttnDecoderFunction(torch.autograd.Function):
     return (None, None, None, None, None, None, d_enc, None, dh0, dc0, None, None) + pgrads
 
 
+def _joint_args(y, ctc_weight, pre_beam, K, V, enc, enc_lens):
+  """beam_search's checks of the joint search's arguments -> (ctc_weight as float, pre_beam as int)."""
+  if not torch.is_tensor(y) or not y.is_cuda:
+    raise ValueError("ctc_log_probs must be a device tensor")
+  if y.dtype != torch.float32:
+    raise ValueError("ctc_log_probs must be float32, got %s" % (y.dtype,))
+  if not torch.is_tensor(enc) or not enc.is_cuda or y.device != enc.device:
+    raise ValueError("ctc_log_probs must be on the encoder states' device")
+  if y.dim() != 3 or y.shape[0] != enc.shape[0] or y.shape[1] != enc.shape[1] or y.shape[2] != V + 1:
+    raise ValueError("ctc_log_probs must be (B, T, V+1) = (%d, %d, %d), got %s"
+                     % (enc.shape[0], enc.shape[1], V + 1, tuple(y.shape)))
+  if y.stride(2) != 1 or y.stride(0) < 0 or y.stride(1) < 0:
+    raise ValueError("ctc_log_probs needs a contiguous class dimension (stride 1), got strides %s" % (y.stride(),))
+  if isinstance(ctc_weight, bool) or not isinstance(ctc_weight, (int, float)) or not 0.0 <= ctc_weight <= 1.0:
+    raise ValueError("ctc_weight must be a number in [0, 1], got %r" % (ctc_weight,))
+  lo, hi = min(K, V - 2), min(64, V - 2)
+  P = min(V - 2, -(-3 * K // 2)) if pre_beam is None else pre_beam
+  if isinstance(P, bool) or not isinstance(P, int) or not lo <= P <= hi:
+    raise ValueError("pre_beam must be an int in [%d, %d], got %r" % (lo, hi, P))
+  lens = enc_lens.detach().cpu() if torch.is_tensor(enc_lens) else torch.as_tensor(enc_lens)
+  if lens.numel() != enc.shape[0] or bool((lens < 1).any()) or bool((lens > enc.shape[1]).any()):
+    raise ValueError("encoder_lens must hold B values in [1, T] for the joint search")
+  return float(ctc_weight), int(P)
+
+
 class CharDecodingStep(nn.Module):
   def __init__(self, encoder, char_dim, vocab_size, char2idx, rnn_dropout=0, attention_type='none',
                attn_hidden_size=-1, device="cpu"):
@@ -320,7 +345,7 @@ class CharDecodingStep(nn.Module):
     return lp, sampled, final_state
 
   def beam_search(self, encoder_hidden_states, encoder_lens, previous_state, beam_width=10, max_label_len=100,
-                  poll_every=8):
+                  poll_every=8, ctc_log_probs=None, ctc_weight=0.0, pre_beam=None):
     """Deterministic beam search through this decoder for every utterance of the batch at once, entirely on the
     device (lr_decoder_beam_search; the rule is in lipreading_amd/csrc/lr_attn_beam.hip and DESIGN.md §14; the
     reference's analysis.py:12-66 inference() does it one utterance at a time with sampled candidates).
@@ -329,7 +354,13 @@ class CharDecodingStep(nn.Module):
     tensors (ids (B, K, max_label_len + 1) int32, lens (B, K) int32, scores (B, K) float32): the final beam, best
     first; ids past lens[b, k] are PAD, and each hypothesis ends with EOS unless it hit the cap.  `poll_every`
     (how often the host checks whether every utterance has finished) changes nothing in the result.  The number of
-    rounds the search needed is left in `self.beam_rounds`."""
+    rounds the search needed is left in `self.beam_rounds`.
+
+    With `ctc_log_probs` (B, T, V+1) float32 on the device (the encoder's CTC head; batch and time may be strided,
+    the class dimension must be contiguous) the search is the joint CTC/attention one (lr_decoder_joint_beam_search,
+    DESIGN.md §15): each hypothesis is scored (1 - ctc_weight) * attention + ctc_weight * CTC prefix log-probability,
+    over `pre_beam` candidates per hypothesis (default min(V - 2, ceil(1.5 K))), and the scores returned are the
+    joint ones.  ctc_weight = 0 gives the attention-only result."""
     K, Lmax = beam_width, max_label_len
     if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= 32:
       raise ValueError("beam_width must be an int in [1, 32], got %r" % (K,))
@@ -341,6 +372,9 @@ class CharDecodingStep(nn.Module):
     for t in [encoder_hidden_states] + states:
       if not (torch.is_tensor(t) and t.is_cuda):
         raise ValueError("beam_search runs on the GPU: encoder states and previous_state must be device tensors")
+    V = self.vocab_size
+    if ctc_log_probs is not None:
+      lam, P = _joint_args(ctc_log_probs, ctc_weight, pre_beam, K, V, encoder_hidden_states, encoder_lens)
     L_ = _C.lib()
     mode = _MODES[self.rnn_type]
     enc = encoder_hidden_states.detach().to(torch.float32).contiguous()
@@ -357,6 +391,9 @@ class CharDecodingStep(nn.Module):
     V, Cd = self.vocab_size, self.char_dim
     A = max(int(self.attn_hidden_size), 0)
     at = _ATT_CODE[self.attention_type]
+    if ctc_log_probs is not None:
+      return self._joint_beam_search(L_, mode, at, pstruct, ustruct, NL, enc, enc_lens, h0, c0, ctc_log_probs.detach(),
+                                     lam, P, K, Lmax, poll_every, A)
     wbytes = L_.lr_decoder_beam_workspace_bytes(mode, at, NL, B, K, Lmax, T, Hd, Cd, V, A)
     if wbytes == 0:
       raise ValueError("beam search does not support this shape (B=%d, K=%d, max_label_len=%d, V=%d, Hd=%d)"
@@ -373,6 +410,32 @@ class CharDecodingStep(nn.Module):
                                        K, Lmax, poll_every, ids.data_ptr(), lens.data_ptr(), scores.data_ptr(),
                                        ctypes.byref(rounds), ws.data_ptr(), wbytes, B, T, Hd, Cd, V, A,
                                        _C.stream_handle()), "lr_decoder_beam_search")
+    self.beam_rounds = int(rounds.value)
+    return ids, lens, scores
+
+  def _joint_beam_search(self, L_, mode, at, pstruct, ustruct, NL, enc, enc_lens, h0, c0, y, lam, P, K, Lmax,
+                         poll_every, A):
+    """beam_search's joint CTC/attention call (arguments already checked)."""
+    dev = enc.device
+    B, T, Hd = enc.shape
+    V, Cd = self.vocab_size, self.char_dim
+    wbytes = L_.lr_decoder_joint_beam_workspace_bytes(mode, at, NL, B, K, Lmax, T, Hd, Cd, V, A, V + 1, P)
+    if wbytes == 0:
+      raise ValueError("joint beam search does not support this shape (B=%d, K=%d, max_label_len=%d, V=%d, Hd=%d, "
+                       "T=%d, pre_beam=%d)" % (B, K, Lmax, V, Hd, T, P))
+    ws = torch.empty(wbytes, dtype=torch.uint8, device=dev)
+    ids = torch.empty((B, K, Lmax + 1), dtype=torch.int32, device=dev)
+    lens = torch.empty((B, K), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, K), dtype=torch.float32, device=dev)
+    rounds = ctypes.c_int32(0)
+    c2i = self.char2idx
+    _C.check(L_.lr_decoder_joint_beam_search(mode, at, ctypes.byref(pstruct),
+                                             ctypes.byref(ustruct) if ustruct is not None else None, enc.data_ptr(),
+                                             enc_lens.data_ptr(), h0.data_ptr(), _C.ptr(c0), y.data_ptr(),
+                                             y.stride(0), y.stride(1), V + 1, 0, lam, P, c2i[BOS], c2i[EOS],
+                                             c2i[PAD], K, Lmax, poll_every, ids.data_ptr(), lens.data_ptr(),
+                                             scores.data_ptr(), ctypes.byref(rounds), ws.data_ptr(), wbytes, B, T,
+                                             Hd, Cd, V, A, _C.stream_handle()), "lr_decoder_joint_beam_search")
     self.beam_rounds = int(rounds.value)
     return ids, lens, scores
 

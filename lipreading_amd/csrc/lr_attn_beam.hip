@@ -50,6 +50,39 @@
 // Limits (LR_ERR_UNSUPPORTED, workspace query 0): 1 <= K <= 32, 1 <= Lmax <= 65535, 3 <= V <= 1024,
 // B * K <= 65535, the head's and the concat attention's LDS as in lr_decoder_forward; every RNN mode, every
 // attention type, 1 .. LR_DEC_MAX_LAYERS layers.
+//
+// ---- Joint CTC/attention search (lr_decoder_joint_beam_search; Watanabe et al. 2017) ----
+// Inputs beyond the above, per utterance b: CTC log-probs y[b, t, c] for t < T_b = enc_lens[b], C = V + 1 classes,
+// class 0 blank and decoder token v = class v + 1 (decoder.ctc_labels, the encoder head's layout); a weight lambda
+// in [0, 1]; a pre-beam size P, min(K, V - 2) <= P <= min(64, V - 2) (default min(V - 2, ceil(1.5 K)) on the host).
+//   * A hypothesis is (history g, state, attention score a, CTC score c); a is the sum of the decoder's lp as above,
+//     c = log psi(g), and the joint score is s = (1 - lambda) a + lambda c (s = a exactly at lambda = 0, where c is
+//     never computed; s = c at lambda = 1).
+//   * CTC terms (log domain, float64).  BOS is not part of g.  Empty prefix: gamma^n_t = 0 (log -inf),
+//     gamma^b_t = prod_{tau <= t} y_tau^blank, psi = 1.  Extension h = g + v, class k = v + 1:
+//       phi_t = gamma^b_t(g) + (gamma^n_t(g) if last(g) != k else 0),  phi_{-1} = [g empty];
+//       gamma^n_t(h) = (gamma^n_{t-1}(h) + phi_{t-1}) y_t^k,  gamma^n_{-1}(h) = 0;
+//       gamma^b_t(h) = (gamma^b_{t-1}(h) + gamma^n_{t-1}(h)) y_t^blank,  gamma^b_{-1}(h) = 0;
+//       psi(h) = sum_{t < T_b} phi_{t-1} y_t^k, the probability that the labelling starts with h.
+//     The CTC head was trained with EOS as its last label, so EOS is an ordinary class; an EOS candidate completes
+//     the hypothesis and its c is the full-sequence log(gamma^n_{T_b-1}(h) + gamma^b_{T_b-1}(h)), not log psi(h).
+//   * Start: one hypothesis, empty history, the encoder's final state, a = c = s = 0.
+//   * One round builds the list as above, except: an unfinished hypothesis's candidates are its P best tokens by lp
+//     (PAD, BOS excluded, ties to the lower id), each with a' = a + lp[v], its c' and s'; when lambda > 0 a
+//     candidate with c' = -inf (a structural zero: the prefix needs more frames than T_b) is not listed.  A finished
+//     hypothesis lists itself unchanged (a capped one keeps its prefix score).  The new beam is the first K of a
+//     STABLE sort by s.  An utterance whose list is empty is finished with an empty beam (length 0, score -inf).
+//   * The output is as above, with s as the score.  At lambda = 0 it is lr_decoder_beam_search's, bit for bit: a
+//     candidate ranked >= K within its own row cannot reach the top K.
+// Structure.  The round's step pieces are the same launches; the selection becomes joint_score_kernel (one wave per
+// row: the top P scan, then one lane per candidate running the recursion serially over t < T_b, the parent's
+// arrays read at the same address by every lane) and beam_select_kernel<true> (the per-utterance stable sort of
+// <= K*P entries; it also copies each surviving extension's arrays from the candidate buffer into its row).
+// Each row's (gamma^n_t, gamma^b_t) live in the workspace, [R][T] double2, single-buffered: the score kernel reads
+// them and writes candidates to cand [R][T][P] double2 (R*P*T*16 bytes, 5.8 MB at B = 32, K = 10, P = 15, T = 75);
+// the select kernel reads only cand.  The CTC log-probs are read in place through (stride_b, stride_t).
+// Extra limits: C = V + 1, blank = 0, lambda in [0, 1] (else LR_ERR_INVALID_ARG); the P range above and
+// T <= 65535 (LR_ERR_UNSUPPORTED).  Precondition: 1 <= enc_lens[b] <= T (the kernels clamp it to stay in bounds).
 #include "lr_common.h"
 #include "lr_decoder_dev.h"
 
@@ -58,6 +91,7 @@ namespace {
 constexpr int BEAM_MAX_K = 32;
 constexpr int BEAM_MAX_V = 1024;
 constexpr int BEAM_MAX_LMAX = 65535;
+constexpr int BEAM_JOINT_MAX_T = 65535;
 constexpr int MAXL = LR_DEC_MAX_LAYERS;
 constexpr int SEL_THREADS = 256;
 constexpr int VPL = BEAM_MAX_V / 64;   // vocabulary entries per lane in the top-K scan
@@ -69,6 +103,7 @@ inline int gates_of(int mode) { return mode == LR_RNN_GRU ? 3 : (mode == LR_RNN_
 
 struct Sizes {
   int B, K, LH, T, Hd, Cd, V, A, G, type, NL;   // LH = Lmax + 1: history capacity
+  int P;                                         // joint search: pre-beam size (0: the attention-only search)
 };
 
 // ---- workspace layout, in 4-byte words ------------------------------------------------------------------------
@@ -77,6 +112,7 @@ struct Ws {
   size_t ones, ids_used, logits, wts, ctx, pre, aux1, aux2, ph, lp;
   size_t score, len, fin, live, next_in, parent, hist, ustate, ctr, gemm, total;
   size_t hp_slot, gemm_bytes;
+  size_t sa, sc, ent_tok, ent_s, ent_a, ent_c, gam, cand;   // joint search only (empty when P == 0)
 };
 
 Ws ws_layout(const Sizes& z) {
@@ -127,6 +163,15 @@ Ws ws_layout(const Sizes& z) {
     if (g > w.gemm_bytes) w.gemm_bytes = g;
   }
   w.gemm = take((w.gemm_bytes + 3) / 4);
+  const size_t RP = R * z.P, RT = z.P ? R * z.T : 0;
+  w.sa = take(z.P ? 2 * R : 0);        // double: attention score a
+  w.sc = take(z.P ? 2 * R : 0);        // double: CTC score c
+  w.ent_tok = take(RP);                // the round's list, entry (row, candidate)
+  w.ent_s = take(2 * RP);
+  w.ent_a = take(2 * RP);
+  w.ent_c = take(2 * RP);
+  w.gam = take(4 * RT);                // double2 (gamma^n, gamma^b) [R][T]: each row's CTC arrays
+  w.cand = take(4 * RT * z.P);         // double2 [R][T][P]: each candidate's arrays, this round
   w.total = o;
   return w;
 }
@@ -144,6 +189,12 @@ bool sizes_ok(int mode, int type, int NL, int B, int K, int Lmax, int T, int Hd,
          (int64_t)B * K <= 65535 && Lmax >= 1 && Lmax <= BEAM_MAX_LMAX && T > 0 && Hd > 0 && Hd % 4 == 0 &&
          Cd > 0 && V >= 3 && V <= BEAM_MAX_V && (type != ATT_CONCAT || (A > 0 && (size_t)2 * A * 4 <= 60 * 1024)) &&
          head_rows(Hd, V) > 0;
+}
+
+// the joint search's own limits: C = V + 1 classes, min(K, V - 2) <= P <= min(64, V - 2), T <= 65535
+bool joint_ok(int K, int T, int V, int C, int P) {
+  const int hi = V - 2 < 64 ? V - 2 : 64, lo = K < V - 2 ? K : V - 2;
+  return C == V + 1 && P >= lo && P <= hi && T <= BEAM_JOINT_MAX_T;
 }
 
 // dst[b*K + k][:] = src[b][:] for every k (the start state of every row of utterance b)
@@ -181,17 +232,72 @@ __device__ __forceinline__ bool ranks_before(S sa, int ia, S sb, int ib) {
   return sa > sb || (sa == sb && ia < ib);
 }
 
+// One wave's scan of one row's lp [V]: the n tokens with the largest lp, PAD and BOS excluded, by lp descending
+// with ties to the lower id.  emit(c, v, lp) runs on every lane for c = 0 .. n-1 (all lanes hold the same values).
+template <typename F>
+__device__ __forceinline__ void wave_topn(const float* __restrict__ row, int lane, int V, int pad, int bos, int n,
+                                          F&& emit) {
+  float val[VPL];
+  unsigned avail = 0;
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    const int v = lane + 64 * i;
+    const bool ok = v < V && v != pad && v != bos;
+    val[i] = ok ? row[v] : LR_NEG_INF;
+    if (ok) avail |= 1u << i;
+  }
+  for (int c = 0; c < n; ++c) {
+    float bv = LR_NEG_INF;
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i)
+      if (((avail >> i) & 1u) && ranks_before(val[i], lane + 64 * i, bv, bi)) { bv = val[i]; bi = lane + 64 * i; }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const float ov = __shfl_xor(bv, d, 64);
+      const int oi = __shfl_xor(bi, d, 64);
+      if (ranks_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    if (bi == 0x7fffffff) break;   // (uniform) fewer than n tokens left: cannot happen with n <= V - 2
+    if ((bi & 63) == lane) avail &= ~(1u << (bi >> 6));
+    emit(c, bi, bv);
+  }
+}
+
+// The joint search's extra state (lr_decoder_joint_beam_search); unused by beam_select_kernel<false>.
+struct JointState {
+  const int32_t* ent_tok;   // [R][P] the round's list: token; -1 a finished hypothesis carried over; -2 no entry
+  const double* ent_s;      // [R][P] joint score s', attention score a', CTC score c'
+  const double* ent_a;
+  const double* ent_c;
+  double* sa;               // [R] each row's a and c (its s lives in `score`)
+  double* sc;
+  double2* gam;             // [R][T] each row's (gamma^n_t, gamma^b_t), log domain
+  const double2* cand;      // [R][T][P] each candidate's arrays, written by joint_score_kernel
+  const int32_t* enc_lens;
+  int T, P, ctc;            // ctc: lambda > 0 (the CTC terms are computed and carried)
+};
+
+__device__ __forceinline__ int utt_frames(const int32_t* enc_lens, int b, int T) {
+  const int t = enc_lens[b];
+  return t < 1 ? 1 : (t > T ? T : t);   // a precondition (1 <= enc_lens[b] <= T); clamped to stay in bounds
+}
+
 // One workgroup per utterance: the rule's round after the step pieces left each row's lp [R][V].
 // Entry e = k*Kc + c of the round's list is candidate c of row k (c = 0 only for a finished row, which
 // contributes itself); e is also the entry's place in the list, so the stable sort is a sort by (score desc, e).
+// JOINT: the list was built by joint_score_kernel (Kc = P, score = the joint score s); the new rows also take
+// their entry's a and c and, when the CTC terms are carried, their candidate's CTC arrays.
+template <bool JOINT>
 __global__ __launch_bounds__(SEL_THREADS) void beam_select_kernel(
     const float* __restrict__ lp, double* __restrict__ score, int32_t* __restrict__ len, int32_t* __restrict__ fin,
     int32_t* __restrict__ live, int32_t* __restrict__ next_in, int32_t* __restrict__ parent,
     int32_t* __restrict__ hist, int32_t* __restrict__ ustate, int32_t* __restrict__ ctr, int32_t* __restrict__ out_ids,
     int32_t* __restrict__ out_lens, float* __restrict__ out_scores, int K, int Kc, int V, int LH, int bos, int eos,
-    int pad) {
-  __shared__ double e_score[BEAM_MAX_K * BEAM_MAX_K];
-  __shared__ int e_tok[BEAM_MAX_K * BEAM_MAX_K];   // token; -1 = a finished hypothesis carried over; -2 = no entry
+    int pad, JointState js) {
+  constexpr int NEMAX = JOINT ? BEAM_MAX_K * 64 : BEAM_MAX_K * BEAM_MAX_K;
+  __shared__ double e_score[NEMAX];
+  __shared__ int e_tok[NEMAX];   // token; -1 = a finished hypothesis carried over; -2 = no entry
   __shared__ double o_score[BEAM_MAX_K];
   __shared__ int o_len[BEAM_MAX_K], o_state[BEAM_MAX_K];   // o_state: 0 empty slot, 1 unfinished, 2 finished
   __shared__ int sel[BEAM_MAX_K];
@@ -201,52 +307,42 @@ __global__ __launch_bounds__(SEL_THREADS) void beam_select_kernel(
   if (u[U_DONE]) return;   // (uniform) every hypothesis finished: a round changes nothing
   const int r0 = b * K;
   const int NE = K * Kc;
-  if (tid < K) {
-    o_score[tid] = score[r0 + tid];
-    o_len[tid] = len[r0 + tid];
-    o_state[tid] = live[r0 + tid] ? (fin[r0 + tid] ? 2 : 1) : 0;
-    sel[tid] = -1;
-  }
-  if (tid == 0) n_sel = 0;
-  for (int e = tid; e < NE; e += SEL_THREADS) e_tok[e] = -2;
-  __syncthreads();
+  if constexpr (JOINT) {
+    if (tid < K) {
+      o_len[tid] = len[r0 + tid];
+      sel[tid] = -1;
+    }
+    if (tid == 0) n_sel = 0;
+    for (int e = tid; e < NE; e += SEL_THREADS) {
+      e_tok[e] = js.ent_tok[(int64_t)r0 * Kc + e];
+      e_score[e] = js.ent_s[(int64_t)r0 * Kc + e];
+    }
+    __syncthreads();
+  } else {
+    if (tid < K) {
+      o_score[tid] = score[r0 + tid];
+      o_len[tid] = len[r0 + tid];
+      o_state[tid] = live[r0 + tid] ? (fin[r0 + tid] ? 2 : 1) : 0;
+      sel[tid] = -1;
+    }
+    if (tid == 0) n_sel = 0;
+    for (int e = tid; e < NE; e += SEL_THREADS) e_tok[e] = -2;
+    __syncthreads();
 
-  // candidates: one wave per row, Kc rounds of a wave argmax over the row's unused entries
-  for (int k = wave; k < K; k += SEL_THREADS / 64) {
-    const int st = o_state[k];
-    if (st == 0) continue;
-    if (st == 2) {
-      if (lane == 0) { e_tok[k * Kc] = -1; e_score[k * Kc] = o_score[k]; }
-      continue;
-    }
-    const float* row = lp + (int64_t)(r0 + k) * V;
-    float val[VPL];
-    unsigned avail = 0;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-      const int v = lane + 64 * i;
-      const bool ok = v < V && v != pad && v != bos;
-      val[i] = ok ? row[v] : LR_NEG_INF;
-      if (ok) avail |= 1u << i;
-    }
-    for (int c = 0; c < Kc; ++c) {
-      float bv = LR_NEG_INF;
-      int bi = 0x7fffffff;
-#pragma unroll
-      for (int i = 0; i < VPL; ++i)
-        if (((avail >> i) & 1u) && ranks_before(val[i], lane + 64 * i, bv, bi)) { bv = val[i]; bi = lane + 64 * i; }
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const float ov = __shfl_xor(bv, d, 64);
-        const int oi = __shfl_xor(bi, d, 64);
-        if (ranks_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    // candidates: one wave per row, Kc rounds of a wave argmax over the row's unused entries
+    for (int k = wave; k < K; k += SEL_THREADS / 64) {
+      const int st = o_state[k];
+      if (st == 0) continue;
+      if (st == 2) {
+        if (lane == 0) { e_tok[k * Kc] = -1; e_score[k * Kc] = o_score[k]; }
+        continue;
       }
-      if (bi == 0x7fffffff) break;   // (uniform) fewer than Kc tokens left: cannot happen with Kc <= V - 2
-      if ((bi & 63) == lane) avail &= ~(1u << (bi >> 6));
-      if (lane == 0) { e_tok[k * Kc + c] = bi; e_score[k * Kc + c] = o_score[k] + (double)bv; }
+      wave_topn(lp + (int64_t)(r0 + k) * V, lane, V, pad, bos, Kc, [&](int c, int v, float l) {
+        if (lane == 0) { e_tok[k * Kc + c] = v; e_score[k * Kc + c] = o_score[k] + (double)l; }
+      });
     }
+    __syncthreads();
   }
-  __syncthreads();
 
   // stable sort, first K: an entry's rank is the count of entries before it in (score desc, place asc)
   for (int e = tid; e < NE; e += SEL_THREADS) {
@@ -277,6 +373,18 @@ __global__ __launch_bounds__(SEL_THREADS) void beam_select_kernel(
     hout[idx] = v;
     oid[idx] = v;
   }
+  if constexpr (JOINT) {
+    // a new row that extends its parent takes the candidate's CTC arrays (a carried-over row never extends)
+    if (js.ctc) {
+      const int Tb = utt_frames(js.enc_lens, b, js.T);
+      for (int idx = tid; idx < nsel * Tb; idx += SEL_THREADS) {
+        const int s = idx / Tb, t = idx - s * Tb;
+        const int e = sel[s], k = e / Kc, c = e - k * Kc;
+        if (e_tok[e] >= 0)
+          js.gam[(int64_t)(r0 + s) * js.T + t] = js.cand[((int64_t)(r0 + k) * js.T + t) * Kc + c];
+      }
+    }
+  }
   if (tid == 0) all_fin = 1;
   __syncthreads();
   if (tid < K) {
@@ -286,6 +394,10 @@ __global__ __launch_bounds__(SEL_THREADS) void beam_select_kernel(
       const int nl = o_len[k] + (tok >= 0 ? 1 : 0);
       const bool f = tok < 0 || tok == eos || nl == LH;
       score[r] = e_score[e];
+      if constexpr (JOINT) {
+        js.sa[r] = js.ent_a[(int64_t)r0 * Kc + e];
+        js.sc[r] = js.ent_c[(int64_t)r0 * Kc + e];
+      }
       len[r] = nl;
       fin[r] = f;
       live[r] = 1;
@@ -315,6 +427,101 @@ __global__ __launch_bounds__(SEL_THREADS) void beam_select_kernel(
       u[U_DONE] = 1;
       atomicAdd(&ctr[0], 1);
     }
+  }
+}
+
+// log(e^x + e^y) in float64; -inf only when both are
+__device__ __forceinline__ double log_add(double x, double y) {
+  const double m = x > y ? x : y, d = x > y ? y : x;
+  if (m == -__builtin_inf()) return m;
+  return m + log1p(exp(d - m));
+}
+
+// The joint search's list for one row: one wave per row (grid R, 64 threads).  A finished row lists itself at
+// its place (c = 0); an unfinished row lists its P best tokens by lp, lane c holding candidate c.  Each lane
+// then runs the CTC prefix recursion of its candidate over the utterance's frames (serial in t; the parent's
+// arrays gam[r][t] are the same address for every lane of the row), writes its arrays to cand[r][t][c] (lanes of
+// one t side by side) and its entry (token, s', a', c').  With ctc == 0 (lambda = 0) s' = a' and nothing of the
+// CTC terms is computed.  A candidate whose c' is -inf (a structural zero) is dropped when lambda > 0.
+__global__ __launch_bounds__(64) void joint_score_kernel(
+    const float* __restrict__ lp, const double* __restrict__ score, const int32_t* __restrict__ len,
+    const int32_t* __restrict__ fin, const int32_t* __restrict__ live, const int32_t* __restrict__ next_in,
+    const int32_t* __restrict__ ustate, const float* __restrict__ y, int64_t stride_b, int64_t stride_t,
+    const double* __restrict__ sa, const double* __restrict__ sc, const double2* __restrict__ gam,
+    int32_t* __restrict__ ent_tok, double* __restrict__ ent_s, double* __restrict__ ent_a, double* __restrict__ ent_c,
+    double2* __restrict__ cand, const int32_t* __restrict__ enc_lens, double lambda, int ctc, int K, int P, int V,
+    int T, int blank, int bos, int eos, int pad) {
+  const int r = blockIdx.x, b = r / K, lane = threadIdx.x;
+  if (ustate[(int64_t)b * U_WORDS + U_DONE]) return;   // (uniform)
+  const int64_t e0 = (int64_t)r * P;
+  if (!live[r] || fin[r]) {
+    if (lane < P) {
+      const bool carry = live[r] && lane == 0;
+      ent_tok[e0 + lane] = carry ? -1 : -2;
+      if (carry) {
+        ent_s[e0] = score[r];
+        ent_a[e0] = sa[r];
+        ent_c[e0] = sc[r];
+      }
+    }
+    return;
+  }
+  int tok = 0;
+  float l = 0.f;
+  wave_topn(lp + (int64_t)r * V, lane, V, pad, bos, P, [&](int c, int v, float x) {
+    if (lane == c) { tok = v; l = x; }
+  });
+  if (lane >= P) return;
+  const double a = sa[r] + (double)l;
+  double c = 0.0, s = a;
+  if (ctc) {
+    const double NEG = -__builtin_inf();
+    const int Tb = utt_frames(enc_lens, b, T);
+    const int k = tok + 1;                                    // decoder token v is class v + 1
+    const int n0 = len[r];
+    const int lastk = n0 > 0 ? next_in[r] + 1 : -1;           // last(g)'s class; none for the empty prefix
+    const double2* g = gam + (int64_t)r * T;
+    const float* yb = y + (int64_t)b * stride_b;
+    double2* out = cand + (int64_t)r * T * P + lane;
+    double gn = NEG, gb = NEG, psi = NEG;
+    double phi = n0 == 0 ? 0.0 : NEG;                         // phi_{t-1}, from phi_{-1} = [g empty]
+#pragma unroll 4
+    for (int t = 0; t < Tb; ++t) {
+      const float* yt = yb + (int64_t)t * stride_t;
+      const double yk = (double)yt[k], y0 = (double)yt[blank];
+      const double2 gp = g[t];
+      const double x = phi + yk;
+      const double gn1 = log_add(gn, phi) + yk;
+      const double gb1 = log_add(gb, gn) + y0;
+      psi = log_add(psi, x);
+      gn = gn1;
+      gb = gb1;
+      out[(int64_t)t * P] = make_double2(gn, gb);
+      phi = k == lastk ? gp.y : log_add(gp.y, gp.x);         // phi_t of g for class k
+    }
+    c = tok == eos ? log_add(gn, gb) : psi;
+    s = lambda == 1.0 ? c : (1.0 - lambda) * a + lambda * c;
+  }
+  ent_tok[e0 + lane] = ctc && c == -__builtin_inf() ? -2 : tok;
+  ent_s[e0 + lane] = s;
+  ent_a[e0 + lane] = a;
+  ent_c[e0 + lane] = c;
+}
+
+// the start rows' CTC arrays: gamma^n(empty) = -inf, gamma^b_t(empty) = sum_{tau <= t} y_tau^blank; a = c = 0
+__global__ void joint_init_kernel(const float* __restrict__ y, int64_t stride_b, int64_t stride_t,
+                                  const int32_t* __restrict__ enc_lens, double* sa, double* sc, double2* gam, int B,
+                                  int K, int T, int blank, int ctc) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= B * K) return;
+  sa[r] = 0.0;
+  sc[r] = 0.0;
+  if (!ctc || r % K) return;
+  const int b = r / K, Tb = utt_frames(enc_lens, b, T);
+  double acc = 0.0;
+  for (int t = 0; t < Tb; ++t) {
+    acc += (double)y[(int64_t)b * stride_b + (int64_t)t * stride_t + blank];
+    gam[(int64_t)r * T + t] = make_double2(-__builtin_inf(), acc);
   }
 }
 
@@ -348,16 +555,34 @@ __global__ void beam_reorder_kernel(StatePtrs q, const int32_t* __restrict__ par
 extern "C" size_t lr_decoder_beam_workspace_bytes(int mode, int attn_type, int num_layers, int B, int K, int Lmax,
                                                   int T, int Hd, int Cd, int V, int A) {
   if (!sizes_ok(mode, attn_type, num_layers, B, K, Lmax, T, Hd, Cd, V, A)) return 0;
-  const Sizes z = {B, K, Lmax + 1, T, Hd, Cd, V, A, gates_of(mode), attn_type, num_layers};
+  const Sizes z = {B, K, Lmax + 1, T, Hd, Cd, V, A, gates_of(mode), attn_type, num_layers, 0};
   return ws_layout(z).total * 4;
 }
 
-extern "C" int lr_decoder_beam_search(int mode, int attn_type, const lr_decoder_params* p, const lr_decoder_upper* up,
-                                      const float* enc, const int32_t* enc_lens, const float* h0, const float* c0,
-                                      int bos, int eos, int pad, int beam_width, int max_label_len, int poll_every,
-                                      int32_t* out_ids, int32_t* out_lens, float* out_scores, int32_t* rounds_host,
-                                      void* workspace, size_t workspace_bytes, int B, int T, int Hd, int Cd, int V,
-                                      int A, lr_stream_t stream_) {
+extern "C" size_t lr_decoder_joint_beam_workspace_bytes(int mode, int attn_type, int num_layers, int B, int K,
+                                                        int Lmax, int T, int Hd, int Cd, int V, int A, int C,
+                                                        int pre_beam) {
+  if (!sizes_ok(mode, attn_type, num_layers, B, K, Lmax, T, Hd, Cd, V, A) || !joint_ok(K, T, V, C, pre_beam))
+    return 0;
+  const Sizes z = {B, K, Lmax + 1, T, Hd, Cd, V, A, gates_of(mode), attn_type, num_layers, pre_beam};
+  return ws_layout(z).total * 4;
+}
+
+namespace {
+
+// The joint search's inputs beyond lr_decoder_beam_search's (NULL: the attention-only search).
+struct JointArgs {
+  const float* y;
+  int64_t stride_b, stride_t;
+  int C, blank, P;
+  double lambda;
+};
+
+int beam_search_impl(int mode, int attn_type, const lr_decoder_params* p, const lr_decoder_upper* up,
+                     const float* enc, const int32_t* enc_lens, const float* h0, const float* c0, int bos, int eos,
+                     int pad, int beam_width, int max_label_len, int poll_every, int32_t* out_ids, int32_t* out_lens,
+                     float* out_scores, int32_t* rounds_host, void* workspace, size_t workspace_bytes, int B, int T,
+                     int Hd, int Cd, int V, int A, hipStream_t stream, const JointArgs* jt) {
   const int NL = up ? up->num_layers : 1;
   const int K = beam_width, Lmax = max_label_len;
   if (!sizes_ok(mode, attn_type, NL, B, K, Lmax, T, Hd, Cd, V, A)) {
@@ -375,10 +600,9 @@ extern "C" int lr_decoder_beam_search(int mode, int attn_type, const lr_decoder_
                eos != pad);
   if (attn_type == ATT_GENERAL || attn_type == ATT_1LNN) LR_CHECK_ARG(p->attn_w1 && p->attn_b1);
   if (attn_type == ATT_CONCAT) LR_CHECK_ARG(p->attn_w1 && p->attn_b1 && p->attn_w2 && p->attn_b2);
-  const Sizes z = {B, K, Lmax + 1, T, Hd, Cd, V, A, gates_of(mode), attn_type, NL};
+  const Sizes z = {B, K, Lmax + 1, T, Hd, Cd, V, A, gates_of(mode), attn_type, NL, jt ? jt->P : 0};
   const Ws w = ws_layout(z);
   if (workspace_bytes < w.total * 4) return LR_ERR_WORKSPACE;
-  hipStream_t stream = (hipStream_t)stream_;
   float* base = (float*)workspace;
   auto I = [&](size_t off) { return (int32_t*)(base + off); };
   const int G = z.G, GH = G * Hd, R = B * K, LH = Lmax + 1, Kc = K < V - 2 ? K : V - 2;
@@ -422,6 +646,16 @@ extern "C" int lr_decoder_beam_search(int mode, int attn_type, const lr_decoder_
   LR_LAUNCH(beam_init_kernel, dim3((R + 255) / 256), dim3(256), 0, stream, (double*)(base + w.score), I(w.len), I(w.fin),
             I(w.live), I(w.next_in), I(w.parent), I(w.ones), I(w.ustate), ctr, R, K, bos);
   LR_TRY(lr_launch_status());
+  JointState js = {};
+  const int ctc = jt && jt->lambda > 0.0;
+  if (jt) {
+    js = {I(w.ent_tok), (const double*)(base + w.ent_s), (const double*)(base + w.ent_a),
+          (const double*)(base + w.ent_c), (double*)(base + w.sa), (double*)(base + w.sc), (double2*)(base + w.gam),
+          (const double2*)(base + w.cand), enc_lens, T, jt->P, ctc};
+    LR_LAUNCH(joint_init_kernel, dim3((R + 255) / 256), dim3(256), 0, stream, jt->y, jt->stride_b, jt->stride_t,
+              enc_lens, js.sa, js.sc, js.gam, B, K, T, jt->blank, ctc);
+    LR_TRY(lr_launch_status());
+  }
   LR_TRY(lr_sgemm_impl(0, 1, V, GH, Cd, 1.f, p->emb, Cd, p->w_ih, Cd, 0.f, base + w.EW, GH, base + w.biasf[0], 0, 0,
                        gws, w.gemm_bytes, stream));
   const int BT = B * T;
@@ -498,9 +732,22 @@ extern "C" int lr_decoder_beam_search(int mode, int attn_type, const lr_decoder_
               attn ? pre : top, p->w_o, p->b_o, p->out_mask, lp, (int32_t*)nullptr, 1, Hd, V, 0, 1, R, out_rows,
               attn ? 1 : 0, (uint64_t)0);
     LR_TRY(lr_launch_status());
-    LR_LAUNCH(beam_select_kernel, dim3(B), dim3(SEL_THREADS), 0, stream, (const float*)lp, (double*)(base + w.score), I(w.len),
-              I(w.fin), I(w.live), I(w.next_in), I(w.parent), I(w.hist), I(w.ustate), ctr, out_ids, out_lens,
-              out_scores, K, Kc, V, LH, bos, eos, pad);
+    if (!jt) {
+      LR_LAUNCH(beam_select_kernel<false>, dim3(B), dim3(SEL_THREADS), 0, stream, (const float*)lp,
+                (double*)(base + w.score), I(w.len), I(w.fin), I(w.live), I(w.next_in), I(w.parent), I(w.hist),
+                I(w.ustate), ctr, out_ids, out_lens, out_scores, K, Kc, V, LH, bos, eos, pad, js);
+    } else {
+      LR_LAUNCH(joint_score_kernel, dim3(R), dim3(64), 0, stream, (const float*)lp, (const double*)(base + w.score),
+                (const int32_t*)I(w.len), (const int32_t*)I(w.fin), (const int32_t*)I(w.live),
+                (const int32_t*)I(w.next_in), (const int32_t*)I(w.ustate), jt->y, jt->stride_b, jt->stride_t,
+                (const double*)js.sa, (const double*)js.sc, (const double2*)js.gam, I(w.ent_tok),
+                (double*)(base + w.ent_s), (double*)(base + w.ent_a), (double*)(base + w.ent_c),
+                (double2*)(base + w.cand), enc_lens, jt->lambda, ctc, K, jt->P, V, T, jt->blank, bos, eos, pad);
+      LR_TRY(lr_launch_status());
+      LR_LAUNCH(beam_select_kernel<true>, dim3(B), dim3(SEL_THREADS), 0, stream, (const float*)lp,
+                (double*)(base + w.score), I(w.len), I(w.fin), I(w.live), I(w.next_in), I(w.parent), I(w.hist),
+                I(w.ustate), ctr, out_ids, out_lens, out_scores, K, jt->P, V, LH, bos, eos, pad, js);
+    }
     LR_TRY(lr_launch_status());
     LR_LAUNCH(beam_reorder_kernel, dim3(R, NL), dim3(256), 0, stream, sp, (const int32_t*)I(w.parent),
               (const int32_t*)I(w.ustate), K, Hd);
@@ -526,4 +773,38 @@ extern "C" int lr_decoder_beam_search(int mode, int attn_type, const lr_decoder_
     *rounds_host = host[1];
   }
   return LR_OK;
+}
+
+}  // namespace
+
+extern "C" int lr_decoder_beam_search(int mode, int attn_type, const lr_decoder_params* p, const lr_decoder_upper* up,
+                                      const float* enc, const int32_t* enc_lens, const float* h0, const float* c0,
+                                      int bos, int eos, int pad, int beam_width, int max_label_len, int poll_every,
+                                      int32_t* out_ids, int32_t* out_lens, float* out_scores, int32_t* rounds_host,
+                                      void* workspace, size_t workspace_bytes, int B, int T, int Hd, int Cd, int V,
+                                      int A, lr_stream_t stream) {
+  return beam_search_impl(mode, attn_type, p, up, enc, enc_lens, h0, c0, bos, eos, pad, beam_width, max_label_len,
+                          poll_every, out_ids, out_lens, out_scores, rounds_host, workspace, workspace_bytes, B, T, Hd,
+                          Cd, V, A, (hipStream_t)stream, nullptr);
+}
+
+extern "C" int lr_decoder_joint_beam_search(int mode, int attn_type, const lr_decoder_params* p,
+                                            const lr_decoder_upper* up, const float* enc, const int32_t* enc_lens,
+                                            const float* h0, const float* c0, const float* ctc_lp, int64_t stride_b,
+                                            int64_t stride_t, int C, int blank, double ctc_weight, int pre_beam,
+                                            int bos, int eos, int pad, int beam_width, int max_label_len,
+                                            int poll_every, int32_t* out_ids, int32_t* out_lens, float* out_scores,
+                                            int32_t* rounds_host, void* workspace, size_t workspace_bytes, int B,
+                                            int T, int Hd, int Cd, int V, int A, lr_stream_t stream) {
+  const int NL = up ? up->num_layers : 1;
+  if (sizes_ok(mode, attn_type, NL, B, beam_width, max_label_len, T, Hd, Cd, V, A)) {
+    LR_CHECK_ARG(C == V + 1 && blank == 0);
+    LR_CHECK_ARG(ctc_weight >= 0.0 && ctc_weight <= 1.0);   // false for NaN
+    if (!joint_ok(beam_width, T, V, C, pre_beam)) return LR_ERR_UNSUPPORTED;
+    LR_CHECK_ARG(ctc_lp && stride_b >= 0 && stride_t >= 0);
+  }
+  const JointArgs jt = {ctc_lp, stride_b, stride_t, C, blank, pre_beam, ctc_weight};
+  return beam_search_impl(mode, attn_type, p, up, enc, enc_lens, h0, c0, bos, eos, pad, beam_width, max_label_len,
+                          poll_every, out_ids, out_lens, out_scores, rounds_host, workspace, workspace_bytes, B, T, Hd,
+                          Cd, V, A, (hipStream_t)stream, &jt);
 }

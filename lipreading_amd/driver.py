@@ -44,8 +44,10 @@ DEFAULTS = dict(  # train.py:134-167
     ctc_decoder="greedy", beam_width=100, lm_path="", lm_alpha=0.0, lm_beta=0.0,
     # the error of a model WITH the attention decoder: teacher (the live loop's sampled-token mismatch rate under
     # teacher forcing, train.eval) or beam (the edit-distance CER of the decoder's own beam-search transcript,
-    # train.attention_cer, --attn_beam_width hypotheses of up to --attn_max_label_len characters)
-    attn_decode="teacher", attn_beam_width=10, attn_max_label_len=100,
+    # train.attention_cer, --attn_beam_width hypotheses of up to --attn_max_label_len characters) or joint (the same
+    # CER of the joint CTC/attention beam search, the CTC head's prefix probability weighted by --attn_ctc_weight;
+    # needs --enable_ctc)
+    attn_decode="teacher", attn_beam_width=10, attn_max_label_len=100, attn_ctc_weight=0.3,
 )
 
 
@@ -123,8 +125,12 @@ def parse_flags(argv, defaults=DEFAULTS):
     raise SystemExit("--ctc_decoder must be greedy or beam")
   if out.get("lm_path") and out.get("ctc_decoder") != "beam":
     raise SystemExit("--lm_path needs --ctc_decoder=beam")
-  if out.get("attn_decode") not in ("teacher", "beam"):
-    raise SystemExit("--attn_decode must be teacher or beam")
+  if out.get("attn_decode") not in ("teacher", "beam", "joint"):
+    raise SystemExit("--attn_decode must be teacher, beam or joint")
+  if out.get("attn_decode") == "joint" and not out.get("enable_ctc"):
+    raise SystemExit("--attn_decode=joint needs --enable_ctc (the CTC head's log-probs)")
+  if not 0.0 <= float(out.get("attn_ctc_weight", 0.3)) <= 1.0:
+    raise SystemExit("--attn_ctc_weight must be in [0, 1]")
   if not 1 <= int(out.get("attn_beam_width", 10)) <= 32:
     raise SystemExit("--attn_beam_width must be in [1, 32]")
   if int(out.get("attn_max_label_len", 100)) < 1:
@@ -222,7 +228,8 @@ def make_error_of(f, encoder, decoding_step, ctc_decoder, device, char2idx):
 
   def error_of(loader):
     """The live loop's "CER" is the sampled-token mismatch rate of the attention decoder (train.py:287-288
-    via eval's correct/count), or with --attn_decode=beam the edit-distance CER of its beam-search transcripts;
+    via eval's correct/count), or with --attn_decode=beam the edit-distance CER of its beam-search transcripts
+    (--attn_decode=joint: of the joint CTC/attention beam search's);
     without a decoder it is the greedy-decoded CER of the CTC head (decoder.py:64-73 on :182-197, as
     archive/train_model.py:351-357 composes them), or the beam-decoded one with --ctc_decoder=beam."""
     if decoding_step is None:
@@ -232,6 +239,9 @@ def make_error_of(f, encoder, decoding_step, ctc_decoder, device, char2idx):
     if f["attn_decode"] == "beam":
       return T.attention_cer(encoder, decoding_step, loader, device, char2idx, beam_width=f["attn_beam_width"],
                              max_label_len=f["attn_max_label_len"])
+    if f["attn_decode"] == "joint":
+      return T.attention_cer(encoder, decoding_step, loader, device, char2idx, beam_width=f["attn_beam_width"],
+                             max_label_len=f["attn_max_label_len"], ctc_weight=f["attn_ctc_weight"])
     _, correct, count, _ = T.eval(encoder, decoding_step, loader, device, char2idx)
     return _cer(correct, count)
   return error_of

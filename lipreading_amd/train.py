@@ -696,13 +696,18 @@ def ctc_cer(encoder, data_loader, device, char2idx, decoder):
   return dist / max(total, 1)
 
 
-def attention_cer(encoder, decoding_step, data_loader, device, char2idx, beam_width=10, max_label_len=100):
+def attention_cer(encoder, decoding_step, data_loader, device, char2idx, beam_width=10, max_label_len=100,
+                  ctc_weight=0.0, pre_beam=None):
   """CER of the attention decoder's own transcripts: the best hypothesis of CharDecodingStep.beam_search (the
   reference's analysis.inference, with this build's deterministic rule) with EOS stripped, scored as greedy_cer
   scores the CTC head (sum of space-free edit distances / sum of space-free reference lengths).  A batch whose
-  encoder recurrence timed out is encoded again with recurrence='f32', as in greedy_cer."""
-  from .analysis import best_ids, encode_for_beam
+  encoder recurrence timed out is encoded again with recurrence='f32', as in greedy_cer.  ctc_weight > 0 runs the
+  joint CTC/attention search on the CTC head of the same encoder pass (re-encoded with it)."""
+  from .analysis import best_ids, encode_for_beam, need_ctc_head
   from .decoder import _edit_distance
+  joint = ctc_weight > 0
+  if joint:
+    need_ctc_head(encoder)
   inv = {v: k for k, v in char2idx.items()}
   eos = char2idx[EOS]
   encoder.eval()
@@ -714,17 +719,22 @@ def attention_cer(encoder, decoding_step, data_loader, device, char2idx, beam_wi
     for frames, frame_lens, chars, char_lens in data_loader:
       if on_gpu:
         _roll_faults(device)
-      hidden, lens_d, state = encode_for_beam(encoder, frames, frame_lens, device)
+      enc_out = encode_for_beam(encoder, frames, frame_lens, device, with_ctc=joint)
       if on_gpu and not bool(_fault_keep(flag2)):
         # the one-launch recurrence timed out (see greedy_cer): encode this batch again on the per-step kernels
         inner = getattr(encoder, "encoder", encoder)
         if hasattr(inner, "recurrence"):
           saved, inner.recurrence = inner.recurrence, 'f32'
           try:
-            hidden, lens_d, state = encode_for_beam(encoder, frames, frame_lens, device)
+            enc_out = encode_for_beam(encoder, frames, frame_lens, device, with_ctc=joint)
           finally:
             inner.recurrence = saved
-      best = best_ids(decoding_step, hidden, lens_d, state, beam_width, max_label_len)
+      hidden, lens_d, state = enc_out[:3]
+      if joint:
+        best = best_ids(decoding_step, hidden, lens_d, state, beam_width, max_label_len, ctc_log_probs=enc_out[3],
+                        ctc_weight=ctc_weight, pre_beam=pre_beam)
+      else:
+        best = best_ids(decoding_step, hidden, lens_d, state, beam_width, max_label_len)
       for b, h in enumerate(best):
         ref = ''.join(inv[int(c)] for c in chars[b, 1:int(char_lens[b]) - 1])  # strip BOS/EOS
         hyp = ''.join(inv[int(i)] for i in h if i != eos)
