@@ -806,14 +806,17 @@ int lr_conv3d_pack_weights_multi(int n, const float* const* W, void* const* out,
 /* Y[b,t,ho,wo,n] = act( sum_{kt,kh,kw,c} X[b,t+kt-pt,ho*s+kh-ph,wo*s+kw-pw,c] * Wp[n][(kt,kh,kw)][c]
  *                       + bias[n] ),  zero padding, temporal stride 1 and KT = 2*pt+1, spatial stride s.
  *   X bf16 [B][T][Hin][Win][Cin] (Cin % 4 == 0), Wp from lr_conv3d_pack_weights, bias fp32 or NULL,
- *   Y bf16 [B][T][Ho][Wo][Cout] (Cout in {32,64,96}); flags & 1 applies max(.,0) (ReLU);
+ *   Y bf16 [B][T][Ho][Wo][Cout]; flags & 1 applies max(.,0) (ReLU);
  *   flags & 2 / flags & 4: Wp is fragment-major (lr_conv3d_pack_weights dgrad & 2 / & 4);
  *   flags & 8 (first STCNN layer only, LR_ERR_UNSUPPORTED elsewhere): X is the raw clip, uint8
  *   [B][T][3][Hin][Win], scaled by 1/255 on the way into LDS exactly as lr_clip_to_ndhwc_bf16
  *   would have — no bf16 copy of the clip is made.
  *   The first STCNN layer's geometry (Cin = 4, Cout = 32, taps 3x5x5, stride 2, padding 1,2,2) is a 3-channel
  *   layer padded to four: its kernel contracts channels 0..2 only — X[...,3] and Wp[...][3] are padding (zero, as
- *   lr_clip_to_ndhwc_bf16 and lr_conv3d_pack_weights with Cin_real = 3 write them) and are not read.  */
+ *   lr_clip_to_ndhwc_bf16 and lr_conv3d_pack_weights with Cin_real = 3 write them) and are not read.
+ *   Supported: that geometry; the patch-resident kernels (flags & 6); and otherwise the (Cin, Cout) pairs of the upper
+ *   layers' forwards, (32, 64) and (64, 96), and of their data gradients, (64, 32) and (96, 64).  Any other shape
+ *   returns LR_ERR_UNSUPPORTED.  */
 int lr_conv3d_forward(const void* X, const void* Wp, const float* bias, void* Y, int B, int T, int Hin,
                       int Win, int Cin, int Cout, int KT, int KH, int KW, int stride, int pt, int ph,
                       int pw, int flags, lr_stream_t stream);
@@ -845,7 +848,9 @@ int lr_conv3d_patch_supported(int Hin, int Win, int Cin, int Cout, int KT, int K
                               int pt, int ph, int pw);
 
 /* dW[Cout][Cin_real][KT][KH][KW] (fp32) (+)= sum_pixels dZ[pixel][n] * im2col(X)[pixel][(tap,c)];
- * dbias[n] (+)= sum_pixels dZ[pixel][n] (NULL to skip).  dZ bf16 [B][T][Ho][Wo][Cout].          */
+ * dbias[n] (+)= sum_pixels dZ[pixel][n] (NULL to skip).  dZ bf16 [B][T][Ho][Wo][Cout].
+ * Supported: the first STCNN layer's geometry with Cin_real = 3 (as lr_conv3d_forward) and the (Cin_pad, Cout) pairs
+ * of the upper layers, (32, 64) and (64, 96); any other shape returns LR_ERR_UNSUPPORTED.                        */
 size_t lr_conv3d_wgrad_workspace_bytes(int Cout, int Cin_pad, int KT, int KH, int KW);
 int lr_conv3d_wgrad(const void* X, const void* dZ, float* dW, float* dbias, void* workspace,
                     size_t workspace_bytes, int accumulate, int B, int T, int Hin, int Win, int Cin_pad,

@@ -1237,16 +1237,10 @@ static int conv_forward_impl(const void* X, const void* Wp, const float* bias, v
                             x, w, bias, y, relu);                                                      \
   } while (0)
   const int nt = Cout / 32;
-  if (Cin == 4 && nt == 1) LR_IGEMM(4, 1);
-  else if (Cin == 32 && nt == 2) LR_IGEMM(32, 2);
+  if (Cin == 32 && nt == 2) LR_IGEMM(32, 2);
   else if (Cin == 64 && nt == 3) LR_IGEMM(64, 3);
   else if (Cin == 64 && nt == 1) LR_IGEMM(64, 1);     // data gradient of layer 2
   else if (Cin == 96 && nt == 2) LR_IGEMM(96, 2);     // data gradient of layer 3
-  else if (Cin == 32 && nt == 1) LR_IGEMM(32, 1);
-  else if (Cin == 32 && nt == 3) LR_IGEMM(32, 3);
-  else if (Cin == 64 && nt == 2) LR_IGEMM(64, 2);
-  else if (Cin == 96 && nt == 1) LR_IGEMM(96, 1);
-  else if (Cin == 96 && nt == 3) LR_IGEMM(96, 3);
   else return LR_ERR_UNSUPPORTED;
 #undef LR_IGEMM
   return lr_launch_status();
@@ -1501,13 +1495,8 @@ extern "C" int lr_conv3d_wgrad(const void* X, const void* dZ, float* dW, float* 
     else hipLaunchKernelGGL((conv3d_wgrad_kernel<CI, MTT, NTT>), grid, dim3(256), 0, (hipStream_t)stream, \
                             g, x, dz, slabs, per);                                                      \
   } while (0)
-  if (Cin_pad == 4 && Cout == 32) LR_WGRAD(4, 1, 5);
-  else if (Cin_pad == 32 && Cout == 64) LR_WGRAD(32, 2, 4);
+  if (Cin_pad == 32 && Cout == 64) LR_WGRAD(32, 2, 4);
   else if (Cin_pad == 64 && Cout == 96) LR_WGRAD(64, 3, 2);
-  else if (Cin_pad == 32 && Cout == 32) LR_WGRAD(32, 1, 5);
-  else if (Cin_pad == 64 && Cout == 64) LR_WGRAD(64, 2, 4);
-  else if (Cin_pad == 32 && Cout == 96) LR_WGRAD(32, 3, 2);
-  else if (Cin_pad == 64 && Cout == 32) LR_WGRAD(64, 1, 5);
   else return LR_ERR_UNSUPPORTED;
 #undef LR_WGRAD
   int st = lr_launch_status();

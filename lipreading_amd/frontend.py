@@ -32,16 +32,8 @@ LAYERS = ((3, 32, (3, 5, 5), 2, (1, 2, 2)),
           (64, 96, (3, 3, 3), 1, (1, 1, 1)))
 
 
-# tests switch this off to compare the patch-resident kernels with the implicit-GEMM kernels
+# tests switch this off to compare the patch-resident kernels of layers 2 and 3 with the implicit-GEMM kernels
 _PATCH_KERNELS = True
-# ... and this one to compare the first layer's fused paths (raw uint8 clip into the kernels, weight
-# gradient that un-pools on the fly) with the staged ones (bf16 clip copy, materialised dZ)
-_FUSE_FIRST_LAYER = True
-# ... and this one to compare the data gradients that un-pool on the fly (lr_conv3d_dgrad_pooled: layers 2 and 3 take
-# the pooled gradient and the window codes) with the staged form (lr_unpool_code_bf16, then lr_conv3d_forward on dZ)
-# (LIPREADING_FUSE_UNPOOL: experiment switch for A/B timing — 0 = staged, 1 = only the data gradients un-pool on the fly)
-_FUSE_UNPOOL = os.environ.get("LIPREADING_FUSE_UNPOOL", "2") != "0"
-_FUSE_UNPOOL_WGRAD = os.environ.get("LIPREADING_FUSE_UNPOOL", "2") == "2"
 
 
 def _pad4(c):
@@ -59,9 +51,6 @@ def feature_dim(H, W):
 # ms).  So: on exactly when the encoder has deferred work in flight; LIPREADING_CONV_WGRAD_SIDE=0 / 1 forces it.
 _WGRAD_SIDE_ENV = os.environ.get("LIPREADING_CONV_WGRAD_SIDE", "auto")
 _WGRAD_SIDE_STREAM = _WGRAD_SIDE_ENV != "0"
-# the side stream's weight half of a layer starts when the layer's pooled gradient exists (1) — beside the layer's OWN
-# data gradient — or (0, rounds 2-4) when that data gradient has finished, i.e. beside the layer BELOW's
-_WGRAD_EARLY = os.environ.get("LIPREADING_CONV_WGRAD_EARLY", "1") != "0"
 _conv_side = None
 
 
@@ -97,17 +86,16 @@ class _ConvFrontendFunction(torch.autograd.Function):
     src = clips if is_u8 else clips.to(torch.float32)
     src = src.contiguous()
     cin0, cout0, (kt0, kh0, kw0), s0, (pt0, ph0, pw0) = LAYERS[0]
+    # the first layer pools in its forward's epilogue and its weight gradient un-pools on the fly at every H, W above
+    assert L.lr_conv3d_pool_fusion_supported(H, W, 4, cout0, kt0, kh0, kw0, s0, pt0, ph0, pw0)
+    assert L.lr_conv3d_wgrad_pooled_supported(H, W, 4, cin0, cout0, kt0, kh0, kw0, s0, pt0, ph0, pw0)
     # uint8 clips go straight into the first layer's patch kernels (forward and weight gradient), which
     # scale and convert while they fill LDS: no bf16 copy of the clip is written or kept
-    raw_u8 = bool(is_u8 and _PATCH_KERNELS and _FUSE_FIRST_LAYER and L.lr_conv3d_pool_fusion_supported(
-        H, W, 4, cout0, kt0, kh0, kw0, s0, pt0, ph0, pw0) and L.lr_conv3d_wgrad_pooled_supported(
-        H, W, 4, cin0, cout0, kt0, kh0, kw0, s0, pt0, ph0, pw0))
-    if raw_u8:
+    if is_u8:
       x = src.reshape(frames, 3, H, W)
     else:
       x = torch.empty((frames, H, W, 4), dtype=bf, device=dev)
-      _C.check(L.lr_clip_to_ndhwc_bf16(src.data_ptr(), 1 if is_u8 else 0, x.data_ptr(), frames, H, W, st),
-               "lr_clip_to_ndhwc_bf16")
+      _C.check(L.lr_clip_to_ndhwc_bf16(src.data_ptr(), 0, x.data_ptr(), frames, H, W, st), "lr_clip_to_ndhwc_bf16")
     saved = [x]
     # every bf16 weight operand of the step in ONE launch: the forward operand of each layer (fragment-major where
     # the layer has a patch-resident kernel) and, when a backward will follow, the flipped / channel-transposed
@@ -121,7 +109,7 @@ class _ConvFrontendFunction(torch.autograd.Function):
       packs.append((params[2 * li], wp, cout, cin, cin_p, kt, kh, kw, frag))
       fwd_ops.append((wp, frag))
       ho, wo = (h + 2 * ph - kh) // stride + 1, (w + 2 * pw - kw) // stride + 1
-      if li > 0 and any(ctx.needs_input_grad[2:]):
+      if li > 0 and any(ctx.needs_input_grad):
         fragd = L.lr_conv3d_patch_supported(ho, wo, cout, cin, kt, kh, kw, 1, pt, ph, pw) if _PATCH_KERNELS else 0
         wd = torch.empty((cin, kt * kh * kw, cout), dtype=bf, device=dev)
         packs.append((params[2 * li], wd, cout, cin, cin_p, kt, kh, kw, 1 | fragd))
@@ -136,15 +124,14 @@ class _ConvFrontendFunction(torch.autograd.Function):
       wp, frag = fwd_ops[li]
       ho, wo = (h + 2 * ph - kh) // stride + 1, (w + 2 * pw - kw) // stride + 1
       pooled = torch.empty((frames, ho // 2, wo // 2, cout), dtype=bf, device=dev)
-      fuse = _PATCH_KERNELS and (frag or cin_p == 4) and L.lr_conv3d_pool_fusion_supported(
-          h, w, cin_p, cout, kt, kh, kw, stride, pt, ph, pw)
-      if fuse:
-        # ReLU + max-pool in the conv epilogue: the full-resolution activation is never written; the
-        # backward gets the pooled activation and each window's argmax code (uint8) instead
+      if li == 0 or frag:
+        # ReLU + max-pool in the conv epilogue (the first layer, and the upper layers that have a patch-resident
+        # kernel): the full-resolution activation is never written; the backward gets the pooled activation and each
+        # window's argmax code (uint8) instead
         code = torch.empty(pooled.shape, dtype=torch.uint8, device=dev)
         _C.check(L.lr_conv3d_forward_pooled(x.data_ptr(), wp.data_ptr(), bias.data_ptr(), pooled.data_ptr(),
                                             code.data_ptr(), B, T, h, w, cin_p, cout, kt, kh, kw, stride, pt, ph,
-                                            pw, 1 | frag | (8 if (li == 0 and raw_u8) else 0), st),
+                                            pw, 1 | frag | (8 if (li == 0 and is_u8) else 0), st),
                  "lr_conv3d_forward_pooled")
         saved += [code, pooled]
       else:
@@ -197,119 +184,75 @@ class _ConvFrontendFunction(torch.autograd.Function):
       x_in, act, pooled = acts[2 * li], acts[2 * li + 1], acts[2 * li + 2]
       h, w = sizes[li]
       ho, wo = 2 * pooled.shape[1], 2 * pooled.shape[2]
+      acc = 1 if direct else 0
       wbytes = max(L.lr_conv3d_wgrad_workspace_bytes(cout, cin_p, kt, kh, kw), L.lr_unpool_workspace_bytes(cout))
       ws = torch.empty(wbytes, dtype=torch.uint8, device=dev)
-      if act.dtype == torch.uint8 and li == 0 and ((_PATCH_KERNELS and _FUSE_FIRST_LAYER) or x_in.dtype == torch.uint8) and L.lr_conv3d_wgrad_pooled_supported(
-          h, w, cin_p, cin, cout, kt, kh, kw, stride, pt, ph, pw):
+      if li == 0:
         # first layer (no data gradient needed): the weight-gradient kernel un-pools on the fly
         _C.check(L.lr_conv3d_wgrad_pooled(x_in.data_ptr(), pooled.data_ptr(), act.data_ptr(), dP.data_ptr(),
-                                          grads[0].data_ptr(), grads[1].data_ptr(), ws.data_ptr(), wbytes,
-                                          1 if direct else 0, B, T, h, w, cin_p, cin, cout, kt, kh, kw, stride, pt,
-                                          ph, pw, 1 if x_in.dtype == torch.uint8 else 0, st), "lr_conv3d_wgrad_pooled")
+                                          grads[0].data_ptr(), grads[1].data_ptr(), ws.data_ptr(), wbytes, acc, B, T,
+                                          h, w, cin_p, cin, cout, kt, kh, kw, stride, pt, ph, pw,
+                                          1 if x_in.dtype == torch.uint8 else 0, st), "lr_conv3d_wgrad_pooled")
         continue
       coded = act.dtype == torch.uint8   # the forward fused the pooling: act holds the window codes
       # data gradient of a stride-1 "same" convolution = the forward kernel on dZ with the flipped,
       # channel-transposed weights (packed with the forward operands: nothing updates the weights in between)
-      wd = frag = None
-      if li > 0:
-        if li in ctx.dgrad_ops:
-          wd, frag = ctx.dgrad_ops[li]
-        else:
-          wd = torch.empty((cin, kt * kh * kw, cout), dtype=bf, device=dev)
-          frag = L.lr_conv3d_patch_supported(ho, wo, cout, cin, kt, kh, kw, 1, pt, ph, pw) if _PATCH_KERNELS else 0
-          _C.check(L.lr_conv3d_pack_weights(params[2 * li].data_ptr(), wd.data_ptr(), cout, cin, cin_p, kt,
-                                            kh, kw, 1 | frag, st), "lr_conv3d_pack_weights")
-      # ... taken STRAIGHT from the pooled gradient and the window codes where the layer has the kernel: the layer
-      # below only waits for this, and the un-pooled dZ (75 % zeros) then exists for the weight gradient alone
+      wd, frag = ctx.dgrad_ops[li]
+      on_side = _WGRAD_SIDE_STREAM and direct and (_WGRAD_SIDE_ENV == "1" or _enc._deferred)
       dP_in = dP
-      fused_dgrad = bool(li > 0 and coded and _FUSE_UNPOOL and frag and frag == L.lr_conv3d_dgrad_pooled_supported(
-          ho, wo, cout, cin, kt, kh, kw, pt, ph, pw))
-      on_side = _WGRAD_SIDE_STREAM and direct and li > 0 and (_WGRAD_SIDE_ENV == "1" or _enc._deferred)
-      ready = None
-      if fused_dgrad:
-        if on_side and _WGRAD_EARLY:
-          # everything the weight half reads (dP_in, the codes, the layer's input) and its workspace exist HERE
-          ready = torch.cuda.Event()
-          ready.record(torch.cuda.current_stream())
+      pooled_wgrad = False
+      if coded:
+        if on_side:
+          # the side stream's weight half starts HERE, beside the layer's own data gradient: everything it reads
+          # (dP_in, the codes, the layer's input) and its workspace exist
+          ready = torch.cuda.current_stream().record_event()
+        # ... taken STRAIGHT from the pooled gradient and the window codes: the layer below only waits for this, and
+        # the un-pooled dZ (75 % zeros) is not written for it
+        assert frag == L.lr_conv3d_dgrad_pooled_supported(ho, wo, cout, cin, kt, kh, kw, pt, ph, pw)
         dP = torch.empty((frames, h, w, cin), dtype=bf, device=dev)
         _C.check(L.lr_conv3d_dgrad_pooled(dP_in.data_ptr(), act.data_ptr(), wd.data_ptr(), dP.data_ptr(), B, T, ho, wo,
                                           cout, cin, kt, kh, kw, pt, ph, pw, st), "lr_conv3d_dgrad_pooled")
-
-      # (decided — and the other path's full-resolution dZ allocated — HERE, on the stream this backward runs on: the
-      # weight half may be enqueued on the side stream, whose allocator pool a per-step dZ should not come from)
-      pooled_wgrad = bool(coded and _FUSE_UNPOOL_WGRAD and L.lr_conv3d_wgrad_pooled_supported_frames(
-          frames, h, w, cin_p, cin, cout, kt, kh, kw, stride, pt, ph, pw) == 2)
-      dZ_fallback = (torch.empty((frames, ho, wo, cout), dtype=bf, device=dev)
-                     if fused_dgrad and not pooled_wgrad else None)
+        # dW and the bias gradient un-pool on the fly as well, unless the frame count overflows that kernel's tile
+        # table: then dZ is materialised, allocated HERE, on the stream this backward runs on (the weight half may be
+        # enqueued on the side stream, whose allocator pool a per-step dZ should not come from)
+        pooled_wgrad = L.lr_conv3d_wgrad_pooled_supported_frames(frames, h, w, cin_p, cin, cout, kt, kh, kw, stride,
+                                                                 pt, ph, pw) == 2
+        dZ = None if pooled_wgrad else torch.empty((frames, ho, wo, cout), dtype=bf, device=dev)
+      else:
+        # the bias gradient (sum of the routed gradients) falls out of the un-pooling pass
+        dZ = torch.empty((frames, ho, wo, cout), dtype=bf, device=dev)
+        _C.check(L.lr_unpool_relu_mask_bf16(act.data_ptr(), dP_in.data_ptr(), dZ.data_ptr(),
+                                            grads[2 * li + 1].data_ptr(), acc, ws.data_ptr(), wbytes,
+                                            frames, ho, wo, cout, st), "lr_unpool_relu_mask_bf16")
 
       def weight_half(accumulate, stream):
-        # dW and the bias gradient straight from the pooled gradient and the codes where the layer has the kernel
-        # (no dZ at all then) ...
         if pooled_wgrad:
           _C.check(L.lr_conv3d_wgrad_pooled(x_in.data_ptr(), pooled.data_ptr(), act.data_ptr(), dP_in.data_ptr(),
                                             grads[2 * li].data_ptr(), grads[2 * li + 1].data_ptr(), ws.data_ptr(),
                                             wbytes, accumulate, B, T, h, w, cin_p, cin, cout, kt, kh, kw, stride, pt, ph,
                                             pw, 0, stream), "lr_conv3d_wgrad_pooled")
-          return None
-        # ... else un-pool (the bias gradient — the sum of the routed gradients — falls out of that pass), then dW
-        dZ = dZ_fallback
-        if coded:
+          return
+        if coded:   # the bias gradient falls out of the un-pooling pass
           _C.check(L.lr_unpool_code_bf16(pooled.data_ptr(), act.data_ptr(), dP_in.data_ptr(), dZ.data_ptr(),
                                          grads[2 * li + 1].data_ptr(), accumulate, ws.data_ptr(), wbytes,
                                          frames, ho, wo, cout, stream), "lr_unpool_code_bf16")
-        else:
-          _C.check(L.lr_unpool_relu_mask_bf16(act.data_ptr(), dP_in.data_ptr(), dZ.data_ptr(),
-                                              grads[2 * li + 1].data_ptr(), accumulate, ws.data_ptr(), wbytes,
-                                              frames, ho, wo, cout, stream), "lr_unpool_relu_mask_bf16")
         _C.check(L.lr_conv3d_wgrad(x_in.data_ptr(), dZ.data_ptr(), grads[2 * li].data_ptr(),
                                    None, ws.data_ptr(), wbytes, accumulate,
                                    B, T, h, w, cin_p, cin, cout, kt, kh, kw, stride, pt, ph, pw, stream),
                  "lr_conv3d_wgrad")
-        return dZ
 
-      if on_side and fused_dgrad:
-        # the whole weight half (un-pooling included) runs on a side stream beside the data gradient, joined at the
-        # end of this backward
-        side = _conv_side_stream(dev)
-        if ready is not None:
-          side.wait_event(ready)
-        else:
-          side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-          dZ = weight_half(1, _C.stream_handle())
-        side_keep.append((x_in, dZ, ws, dP_in))
-        continue
-      if fused_dgrad:
-        weight_half(1 if direct else 0, st)
-        continue
-      dZ = torch.empty((frames, ho, wo, cout), dtype=bf, device=dev)
-      # the bias gradient (sum of the routed gradients) falls out of the un-pooling pass
-      if coded:
-        _C.check(L.lr_unpool_code_bf16(pooled.data_ptr(), act.data_ptr(), dP.data_ptr(), dZ.data_ptr(),
-                                       grads[2 * li + 1].data_ptr(), 1 if direct else 0, ws.data_ptr(), wbytes,
-                                       frames, ho, wo, cout, st), "lr_unpool_code_bf16")
-      else:
-        _C.check(L.lr_unpool_relu_mask_bf16(act.data_ptr(), dP.data_ptr(), dZ.data_ptr(),
-                                            grads[2 * li + 1].data_ptr(), 1 if direct else 0, ws.data_ptr(), wbytes,
-                                            frames, ho, wo, cout, st), "lr_unpool_relu_mask_bf16")
       if on_side:
-        # the weight gradient and the data gradient of a layer both read dZ and feed nothing to each other: the
-        # weight gradient goes to a side stream (joined at the end of this backward), the data gradient — which
-        # the layer below waits for — stays on this one
+        # the weight half and the data gradient of a layer feed nothing to each other: the weight half goes to a side
+        # stream (joined at the end of this backward), the data gradient — which the layer below waits for — stays on
+        # this one
         side = _conv_side_stream(dev)
-        side.wait_stream(torch.cuda.current_stream())
+        side.wait_event(ready if coded else torch.cuda.current_stream().record_event())
         with torch.cuda.stream(side):
-          _C.check(L.lr_conv3d_wgrad(x_in.data_ptr(), dZ.data_ptr(), grads[2 * li].data_ptr(),
-                                     None, ws.data_ptr(), wbytes, 1,
-                                     B, T, h, w, cin_p, cin, cout, kt, kh, kw, stride, pt, ph, pw, _C.stream_handle()),
-                   "lr_conv3d_wgrad")
-        side_keep.append((x_in, dZ, ws))
+          weight_half(1, _C.stream_handle())
+        side_keep.append((x_in, dZ, ws, dP_in) if coded else (x_in, dZ, ws))
       else:
-        _C.check(L.lr_conv3d_wgrad(x_in.data_ptr(), dZ.data_ptr(), grads[2 * li].data_ptr(),
-                                   None, ws.data_ptr(), wbytes, 1 if direct else 0,
-                                   B, T, h, w, cin_p, cin, cout, kt, kh, kw, stride, pt, ph, pw, st),
-                 "lr_conv3d_wgrad")
-      if li > 0:
+        weight_half(acc, st)
+      if not coded:
         dP = torch.empty((frames, h, w, cin), dtype=bf, device=dev)
         _C.check(L.lr_conv3d_forward(dZ.data_ptr(), wd.data_ptr(), None, dP.data_ptr(), B, T, ho, wo, cout,
                                      cin, kt, kh, kw, 1, pt, ph, pw, frag, st), "lr_conv3d_forward(dgrad)")

@@ -150,63 +150,182 @@ def test_pixel_lipreader_trains_end_to_end(dev):
   assert np.isfinite(losses).all() and losses[-1] < 0.8 * losses[0], losses
 
 
+def _module_grads(fe, clips, wgt):
+  """features and [conv1.weight, conv1.bias, ..., conv3.bias] gradients of sum(features * wgt) through the module"""
+  fe.zero_grad()
+  out = fe(clips)
+  (out * wgt).sum().backward()
+  torch.cuda.synchronize()
+  return [out.detach().clone()] + [p.grad.detach().clone() for p in fe.parameters_in_order()]
+
+
+def _staged_frontend_grads(fe, clips, wgt, staged_first, staged_upper):
+  """What _module_grads returns, written out in ABI calls, with the first layer (staged_first) and / or the upper layers
+  whose forward pools in its epilogue (staged_upper) in the staged form: the clip is copied to bf16
+  (lr_clip_to_ndhwc_bf16), and the backward materialises each dZ (lr_unpool_code_bf16) for lr_conv3d_wgrad and the
+  data gradient (lr_conv3d_forward with the fragment flag) to read.  The other layers take the module's calls."""
+  from lipreading_amd import _C
+  from lipreading_amd.frontend import LAYERS, _pad4
+  L = _C.lib()
+  st = _C.stream_handle()
+  dev, bf, u8 = clips.device, torch.bfloat16, torch.uint8
+  B, T, _, H, W = clips.shape
+  F = B * T
+  params = [p.detach() for p in fe.parameters_in_order()]
+
+  def pack(li, flags):
+    cin, cout, (kt, kh, kw) = LAYERS[li][:3]
+    shape = (cin, kt * kh * kw, cout) if flags & 1 else (cout, kt * kh * kw, _pad4(cin))
+    out = torch.empty(shape, dtype=bf, device=dev)
+    _C.check(L.lr_conv3d_pack_weights(params[2 * li].data_ptr(), out.data_ptr(), cout, cin, _pad4(cin), kt, kh, kw,
+                                      flags, st), "lr_conv3d_pack_weights")
+    return out
+
+  x = clips
+  if staged_first:
+    x = torch.empty((F, H, W, 4), dtype=bf, device=dev)
+    _C.check(L.lr_clip_to_ndhwc_bf16(clips.data_ptr(), 1, x.data_ptr(), F, H, W, st), "lr_clip_to_ndhwc_bf16")
+  saved, h, w = [], H, W
+  for li, (cin, cout, (kt, kh, kw), s, (pt, ph, pw)) in enumerate(LAYERS):
+    ho, wo = (h + 2 * ph - kh) // s + 1, (w + 2 * pw - kw) // s + 1
+    frag = L.lr_conv3d_patch_supported(h, w, _pad4(cin), cout, kt, kh, kw, s, pt, ph, pw)
+    wp = pack(li, frag)
+    pooled = torch.empty((F, ho // 2, wo // 2, cout), dtype=bf, device=dev)
+    if li == 0 or frag:   # act = the window codes
+      act = torch.empty(pooled.shape, dtype=u8, device=dev)
+      _C.check(L.lr_conv3d_forward_pooled(x.data_ptr(), wp.data_ptr(), params[2 * li + 1].data_ptr(), pooled.data_ptr(),
+                                          act.data_ptr(), B, T, h, w, _pad4(cin), cout, kt, kh, kw, s, pt, ph, pw,
+                                          1 | frag | (8 if x.dtype == u8 else 0), st), "lr_conv3d_forward_pooled")
+    else:                 # act = the full-resolution activation
+      act = torch.empty((F, ho, wo, cout), dtype=bf, device=dev)
+      _C.check(L.lr_conv3d_forward(x.data_ptr(), wp.data_ptr(), params[2 * li + 1].data_ptr(), act.data_ptr(), B, T, h,
+                                   w, _pad4(cin), cout, kt, kh, kw, s, pt, ph, pw, 1, st), "lr_conv3d_forward")
+      _C.check(L.lr_maxpool_hw2_bf16(act.data_ptr(), pooled.data_ptr(), F, ho, wo, cout, st), "lr_maxpool_hw2_bf16")
+    saved.append((x, act, pooled, h, w, ho, wo))
+    x, h, w = pooled, ho // 2, wo // 2
+  res = [x.float().reshape(B, T, -1)]
+  grads = [torch.empty_like(p) for p in params]
+  dP = torch.empty(x.shape, dtype=bf, device=dev)
+  _C.check(L.lr_f32_to_bf16(wgt.contiguous().data_ptr(), dP.data_ptr(), wgt.numel(), st), "lr_f32_to_bf16")
+  for li in (2, 1, 0):
+    cin, cout, (kt, kh, kw), s, (pt, ph, pw) = LAYERS[li]
+    x, act, pooled, h, w, ho, wo = saved[li]
+    coded = act.dtype == u8
+    fused = coded and not (staged_first if li == 0 else staged_upper)
+    wbytes = max(L.lr_conv3d_wgrad_workspace_bytes(cout, _pad4(cin), kt, kh, kw), L.lr_unpool_workspace_bytes(cout))
+    ws = torch.empty(wbytes, dtype=u8, device=dev)
+    geom = (B, T, h, w, _pad4(cin), cin, cout, kt, kh, kw, s, pt, ph, pw)
+    if fused and L.lr_conv3d_wgrad_pooled_supported_frames(F, *geom[2:]):
+      _C.check(L.lr_conv3d_wgrad_pooled(x.data_ptr(), pooled.data_ptr(), act.data_ptr(), dP.data_ptr(),
+                                        grads[2 * li].data_ptr(), grads[2 * li + 1].data_ptr(), ws.data_ptr(), wbytes, 0,
+                                        *geom, 1 if x.dtype == u8 else 0, st), "lr_conv3d_wgrad_pooled")
+    else:
+      dZ = torch.empty((F, ho, wo, cout), dtype=bf, device=dev)
+      if coded:
+        _C.check(L.lr_unpool_code_bf16(pooled.data_ptr(), act.data_ptr(), dP.data_ptr(), dZ.data_ptr(),
+                                       grads[2 * li + 1].data_ptr(), 0, ws.data_ptr(), wbytes, F, ho, wo, cout, st),
+                 "lr_unpool_code_bf16")
+      else:
+        _C.check(L.lr_unpool_relu_mask_bf16(act.data_ptr(), dP.data_ptr(), dZ.data_ptr(), grads[2 * li + 1].data_ptr(),
+                                            0, ws.data_ptr(), wbytes, F, ho, wo, cout, st), "lr_unpool_relu_mask_bf16")
+      _C.check(L.lr_conv3d_wgrad(x.data_ptr(), dZ.data_ptr(), grads[2 * li].data_ptr(), None, ws.data_ptr(), wbytes, 0,
+                                 *geom, st), "lr_conv3d_wgrad")
+    if li > 0:
+      fragd = L.lr_conv3d_patch_supported(ho, wo, cout, cin, kt, kh, kw, 1, pt, ph, pw)
+      wd = pack(li, 1 | fragd)
+      dX = torch.empty((F, h, w, cin), dtype=bf, device=dev)
+      if fused:
+        _C.check(L.lr_conv3d_dgrad_pooled(dP.data_ptr(), act.data_ptr(), wd.data_ptr(), dX.data_ptr(), B, T, ho, wo,
+                                          cout, cin, kt, kh, kw, pt, ph, pw, st), "lr_conv3d_dgrad_pooled")
+      else:
+        _C.check(L.lr_conv3d_forward(dZ.data_ptr(), wd.data_ptr(), None, dX.data_ptr(), B, T, ho, wo, cout, cin, kt, kh,
+                                     kw, 1, pt, ph, pw, fragd, st), "lr_conv3d_forward(dgrad)")
+      dP = dX
+  torch.cuda.synchronize()
+  return res + grads
+
+
 @pytest.mark.parametrize("B,T,H", [(2, 9, 96), (1, 5, 96), (3, 7, 64), (2, 75, 96)])
 def test_data_gradients_that_unpool_on_the_fly_equal_the_staged_ones(dev, B, T, H):
   """Layers 2 and 3: lr_conv3d_dgrad_pooled takes the pooled gradient and the window codes and rebuilds its dZ patch
   on the way into LDS, and so does their weight gradient (lr_conv3d_wgrad_pooled); staged reference:
   lr_unpool_code_bf16 materialises dZ and lr_conv3d_forward / lr_conv3d_wgrad (the same kernels) read it.  The same
-  bf16 values reach the same MFMAs in the same order: every gradient is bit-identical."""
+  bf16 values reach the same MFMAs in the same order: every gradient is bit-identical — through the module against
+  _staged_frontend_grads, and kernel by kernel at the geometries of layers 2 and 3."""
+  from lipreading_amd import _C
   from lipreading_amd import frontend as FE
+  L = _C.lib()
+  st = _C.stream_handle()
+  bf = torch.bfloat16
   torch.manual_seed(19)
   fe = FE.ConvFrontend3D().to(dev)
   g = torch.Generator().manual_seed(20)
   clips = torch.randint(0, 256, (B, T, 3, H, H), generator=g, dtype=torch.uint8).to(dev)
   wgt = torch.randn(B, T, FE.feature_dim(H, H), generator=g).to(dev)
-  res = {}
-  for fused in (2, 1, 0):   # data and weight gradients un-pool on the fly | data gradients only | staged
-    FE._FUSE_UNPOOL, FE._FUSE_UNPOOL_WGRAD = fused > 0, fused > 1
-    try:
-      fe.zero_grad()
-      out = fe(clips)
-      (out * wgt).sum().backward()
-      torch.cuda.synchronize()
-      res[fused] = [out.detach().clone()] + [p.grad.detach().clone() for p in fe.parameters_in_order()]
-    finally:
-      FE._FUSE_UNPOOL = FE._FUSE_UNPOOL_WGRAD = True
-  for a, b in zip(res[1], res[0]):
-    assert torch.equal(a, b)
-  # the weight gradients that un-pool on the fly (lr_conv3d_wgrad_pooled, layers 2 and 3): the same products in the
-  # same order — bit-identical; their bias gradients are the same sums in another order
-  for i, (a, b) in enumerate(zip(res[2], res[0])):
+  got = _module_grads(fe, clips, wgt)
+  ref = _staged_frontend_grads(fe, clips, wgt, staged_first=False, staged_upper=True)
+  # the weight gradients that un-pool on the fly: the same products in the same order — bit-identical; their bias
+  # gradients are the same sums in another order
+  for i, (a, b) in enumerate(zip(got, ref)):
     if i in (4, 6):   # conv2.bias, conv3.bias
       assert float((a - b).abs().max()) <= 2e-5 * max(1e-6, float(b.abs().max())), i
     else:
       assert torch.equal(a, b), i
-  # the codes: 0..3 = position of the window's first maximum, 4 = pooled activation 0 (ReLU blocks the gradient)
-  from lipreading_amd import _C
-  L = _C.lib()
-  x = torch.randn(B * T, 24, 24, 32, generator=g).to(dev).bfloat16()
-  w = (torch.randn(64, 32, 3, 5, 5, generator=g) * 0.05).to(dev)
-  bias = torch.randn(64, generator=g).to(dev) - 1.0
-  wp = torch.empty((64, 75, 32), dtype=torch.bfloat16, device=dev)
-  frag = L.lr_conv3d_patch_supported(24, 24, 32, 64, 3, 5, 5, 1, 1, 2, 2)
-  _C.check(L.lr_conv3d_pack_weights(w.data_ptr(), wp.data_ptr(), 64, 32, 32, 3, 5, 5, frag, _C.stream_handle()), "pack")
-  pooled = torch.empty((B * T, 12, 12, 64), dtype=torch.bfloat16, device=dev)
-  code = torch.empty(pooled.shape, dtype=torch.uint8, device=dev)
-  _C.check(L.lr_conv3d_forward_pooled(x.data_ptr(), wp.data_ptr(), bias.data_ptr(), pooled.data_ptr(), code.data_ptr(), B, T,
-                                      24, 24, 32, 64, 3, 5, 5, 1, 1, 2, 2, 1 | frag, _C.stream_handle()), "fwd")
-  assert int(code.max()) == 4 and bool(((code == 4) == (pooled.float() == 0)).all())
+  # kernel by kernel, B * T frames at 96 x 96 (where layers 2 and 3 have these kernels at every H above)
+  F = B * T
+  for li, hw in ((1, 24), (2, 12)):
+    cin, cout, (kt, kh, kw), s, (pt, ph, pw) = FE.LAYERS[li]
+    x = torch.randn(F, hw, hw, cin, generator=g).clamp_min(0).to(dev).to(bf)
+    w = (torch.randn(cout, cin, kt, kh, kw, generator=g) * 0.05).to(dev)
+    bias = torch.randn(cout, generator=g).to(dev) - 1.0
+    frag = L.lr_conv3d_patch_supported(hw, hw, cin, cout, kt, kh, kw, 1, pt, ph, pw)
+    fragd = L.lr_conv3d_dgrad_pooled_supported(hw, hw, cout, cin, kt, kh, kw, pt, ph, pw)
+    assert frag and fragd
+    wp = torch.empty((cout, kt * kh * kw, cin), dtype=bf, device=dev)
+    wd = torch.empty((cin, kt * kh * kw, cout), dtype=bf, device=dev)
+    _C.check(L.lr_conv3d_pack_weights(w.data_ptr(), wp.data_ptr(), cout, cin, cin, kt, kh, kw, frag, st), "pack")
+    _C.check(L.lr_conv3d_pack_weights(w.data_ptr(), wd.data_ptr(), cout, cin, cin, kt, kh, kw, 1 | fragd, st), "pack")
+    pooled = torch.empty((F, hw // 2, hw // 2, cout), dtype=bf, device=dev)
+    code = torch.empty(pooled.shape, dtype=torch.uint8, device=dev)
+    _C.check(L.lr_conv3d_forward_pooled(x.data_ptr(), wp.data_ptr(), bias.data_ptr(), pooled.data_ptr(), code.data_ptr(),
+                                        B, T, hw, hw, cin, cout, kt, kh, kw, 1, pt, ph, pw, 1 | frag, st), "fwd")
+    # the codes: 0..3 = position of the window's first maximum, 4 = pooled activation 0 (ReLU blocks the gradient)
+    assert int(code.max()) == 4 and bool(((code == 4) == (pooled.float() == 0)).all())
+    dP = (torch.randn(pooled.shape, generator=g) * 0.1).to(dev).to(bf)
+    wbytes = max(L.lr_conv3d_wgrad_workspace_bytes(cout, cin, kt, kh, kw), L.lr_unpool_workspace_bytes(cout))
+    ws = torch.empty(wbytes, dtype=torch.uint8, device=dev)
+    dZ = torch.empty((F, hw, hw, cout), dtype=bf, device=dev)
+    db_staged = torch.empty(cout, device=dev)
+    _C.check(L.lr_unpool_code_bf16(pooled.data_ptr(), code.data_ptr(), dP.data_ptr(), dZ.data_ptr(), db_staged.data_ptr(),
+                                   0, ws.data_ptr(), wbytes, F, hw, hw, cout, st), "lr_unpool_code_bf16")
+    dx = [torch.empty((F, hw, hw, cin), dtype=bf, device=dev) for _ in range(2)]
+    _C.check(L.lr_conv3d_dgrad_pooled(dP.data_ptr(), code.data_ptr(), wd.data_ptr(), dx[0].data_ptr(), B, T, hw, hw,
+                                      cout, cin, kt, kh, kw, pt, ph, pw, st), "lr_conv3d_dgrad_pooled")
+    _C.check(L.lr_conv3d_forward(dZ.data_ptr(), wd.data_ptr(), None, dx[1].data_ptr(), B, T, hw, hw, cout, cin, kt, kh,
+                                 kw, 1, pt, ph, pw, fragd, st), "lr_conv3d_forward(dgrad)")
+    assert torch.equal(dx[0].view(torch.int16), dx[1].view(torch.int16)), li
+    assert int(dx[0].view(torch.int16).ne(0).sum()) > 0
+    if L.lr_conv3d_wgrad_pooled_supported_frames(F, hw, hw, cin, cin, cout, kt, kh, kw, 1, pt, ph, pw) == 2:
+      dw = [torch.empty((cout, cin, kt, kh, kw), device=dev) for _ in range(2)]
+      db = torch.empty(cout, device=dev)
+      _C.check(L.lr_conv3d_wgrad_pooled(x.data_ptr(), pooled.data_ptr(), code.data_ptr(), dP.data_ptr(), dw[0].data_ptr(),
+                                        db.data_ptr(), ws.data_ptr(), wbytes, 0, B, T, hw, hw, cin, cin, cout, kt, kh, kw,
+                                        1, pt, ph, pw, 0, st), "lr_conv3d_wgrad_pooled")
+      _C.check(L.lr_conv3d_wgrad(x.data_ptr(), dZ.data_ptr(), dw[1].data_ptr(), None, ws.data_ptr(), wbytes, 0, B, T, hw,
+                                 hw, cin, cin, cout, kt, kh, kw, 1, pt, ph, pw, st), "lr_conv3d_wgrad")
+      assert torch.equal(dw[0], dw[1]), li
+      assert float((db - db_staged).abs().max()) <= 2e-5 * max(1e-6, float(db_staged.abs().max())), li
 
 
 @pytest.mark.parametrize("B,T,H,shift", [(2, 9, 96, 0), (2, 80, 96, 0), (3, 7, 64, 0), (2, 9, 96, 1), (1, 40, 96, 2)])
 def test_first_layer_fused_paths_equal_the_staged_ones(dev, B, T, H, shift):
   """The first layer's kernels read the raw uint8 clip and its weight gradient rebuilds dZ from the pooled gradient and
-  the window codes on the fly (lr_conv3d_forward_pooled flags & 8, lr_conv3d_wgrad_pooled).  Staged reference:
-  lr_clip_to_ndhwc_bf16 copy, lr_unpool_code_bf16 + lr_conv3d_wgrad on the materialised dZ.  Same arithmetic on the
-  same bf16 values: features and conv1.weight.grad are bit-identical, the bias gradient is the same sum in another
-  order.  (2, 80, 96): 1440 tiles, five or six per workgroup of the weight gradient, walk starts (t = 0) in the middle
-  of a workgroup's range and a clip boundary; shift: the clip starts 1 / 2 bytes off a dword boundary, where the
-  weight gradient reads it in bytes instead of dwords and the forward in bytes instead of pairs."""
+  the window codes on the fly (lr_conv3d_forward_pooled flags & 8, lr_conv3d_wgrad_pooled).  Staged reference
+  (_staged_frontend_grads): lr_clip_to_ndhwc_bf16 copy, lr_unpool_code_bf16 + lr_conv3d_wgrad on the materialised dZ.
+  Same arithmetic on the same bf16 values: features and conv1.weight.grad are bit-identical, the bias gradient is the
+  same sum in another order.  (2, 80, 96): 1440 tiles, five or six per workgroup of the weight gradient, walk starts
+  (t = 0) in the middle of a workgroup's range and a clip boundary; shift: the clip starts 1 / 2 bytes off a dword
+  boundary, where the weight gradient reads it in bytes instead of dwords and the forward in bytes instead of pairs."""
   from lipreading_amd import frontend as FE
   torch.manual_seed(9)
   fe = FE.ConvFrontend3D().to(dev)
@@ -215,20 +334,12 @@ def test_first_layer_fused_paths_equal_the_staged_ones(dev, B, T, H, shift):
   clips = raw[shift:shift + B * T * 3 * H * H].view(B, T, 3, H, H)
   assert clips.data_ptr() % 4 == shift
   wgt = torch.randn(B, T, FE.feature_dim(H, H), generator=g).to(dev)
-  res = {}
-  for fused in (True, False):
-    FE._FUSE_FIRST_LAYER = fused
-    try:
-      fe.zero_grad()
-      out = fe(clips)
-      (out * wgt).sum().backward()
-      res[fused] = [out.detach().clone()] + [p.grad.detach().clone() for p in fe.parameters_in_order()]
-    finally:
-      FE._FUSE_FIRST_LAYER = True
-  assert torch.equal(res[True][0], res[False][0])
-  assert torch.equal(res[True][1], res[False][1])                  # conv1.weight.grad
-  assert float((res[True][2] - res[False][2]).abs().max()) <= 1e-5 * float(res[False][2].abs().max())   # conv1.bias.grad
-  for a, b in zip(res[True][3:], res[False][3:]):
+  got = _module_grads(fe, clips, wgt)
+  ref = _staged_frontend_grads(fe, clips, wgt, staged_first=True, staged_upper=False)
+  assert torch.equal(got[0], ref[0])
+  assert torch.equal(got[1], ref[1])                  # conv1.weight.grad
+  assert float((got[2] - ref[2]).abs().max()) <= 1e-5 * float(ref[2].abs().max())   # conv1.bias.grad
+  for a, b in zip(got[3:], ref[3:]):
     assert torch.equal(a, b)
 
 

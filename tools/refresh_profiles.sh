@@ -18,8 +18,8 @@
 #            (the per-rank shapes of BASELINE configs[3]), <round>_bench_scaling_model.json (bench.py --model-scaling),
 #            <round>_ecd_lstm768_pmc_{FETCH,WRITE}_SIZE.txt / _pmc_SQ_pass1.txt (the grid recurrence's traffic and matrix pipe),
 #            <round>_pixels_pmc_clock.txt (GRBM_GUI_ACTIVE: the effective shader clock of the conv kernels),
-#            <round>_grid_phase_timing.txt / <round>_conv_patch_phase_timing.txt (shader-clock stamps of the timing variants,
-#            when lipreading_amd/_lib/alt/{gridtime,patchtime}.so were built before the visit)
+#            <round>_grid_phase_timing.txt (shader-clock stamps of the timing variant,
+#            when lipreading_amd/_lib/alt/gridtime.so was built before the visit)
 #            <round>_bench_pixels_tfm.json, <round>_pixels_tfm_pmc_{FETCH,WRITE}_SIZE.txt / _pmc_SQ_pass1.txt (the transformer stage's
 #            row-block, attention and product kernels), <round>_rowblock_phase_timing.txt (alt/rbtime.so: the forward
 #            row-block launch by phase)
@@ -122,9 +122,6 @@ if [ "$ONLY" != "pixels" ]; then
   tl ecd_lstm768_b32 step_begin_ctc 8 --regime landmarks_attn --model lstm768 --attention none --char-dim 256 --batch 32
   if [ -f lipreading_amd/_lib/alt/gridtime.so ]; then
     (LIPREADING_HIP_LIB=$R/lipreading_amd/_lib/alt/gridtime.so python tools/probes/grid_timing.py 32 31; LIPREADING_HIP_LIB=$R/lipreading_amd/_lib/alt/gridtime.so python tools/probes/grid_timing.py 64 31) > "$OUT/${TAG}_grid_phase_timing.txt" 2>&1
-  fi
-  if [ -f lipreading_amd/_lib/alt/patchtime.so ]; then
-    LIPREADING_HIP_LIB=$R/lipreading_amd/_lib/alt/patchtime.so python tools/probes/conv_patch_timing.py > "$OUT/${TAG}_conv_patch_phase_timing.txt" 2>&1
   fi
   tl gru256 step_begin 8 --regime landmarks --model gru256
   tl lstm768 step_begin 8 --regime landmarks --model lstm768
