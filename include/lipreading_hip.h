@@ -540,7 +540,8 @@ int lr_sgemm_batched(int transA, int transB, int M, int N, int K, float alpha, c
                      int batch_outer, int batch_inner, lr_stream_t stream);
 /* y = LayerNorm(x + residual) * gamma + beta over rows of D (residual may be NULL); stats [R][2] =
  * (mean, rstd) for the backward.  Backward: dx is the gradient of BOTH x and residual; dgamma / dbeta
- * overwritten or (accumulate != 0) added to. */
+ * overwritten or (accumulate != 0) added to.  The forward takes any D; the backward keeps 4 x 2 x D floats in LDS
+ * and returns LR_ERR_UNSUPPORTED past D = 1920 (nothing is written then). */
 int lr_layernorm_forward(const float* x, const float* residual, const float* gamma, const float* beta,
                          float* y, float* stats, int R, int D, float eps, lr_stream_t stream);
 size_t lr_layernorm_workspace_bytes(int D);
@@ -548,7 +549,9 @@ int lr_layernorm_backward(const float* x, const float* residual, const float* ga
                           const float* dy, float* dx, float* dgamma, float* dbeta, void* workspace,
                           size_t workspace_bytes, int accumulate, int R, int D, lr_stream_t stream);
 /* In place: scores [B][Hh][T][T] -> softmax over keys of scale*scores with keys >= key_lens[b] masked
- * (probability 0).  Backward, in place over dprobs: dscores = scale * P * (dP - sum_k dP P). */
+ * (probability 0).  key_lens[b] is clamped to [1, T]: a sample of length 0 attends to key 0 alone (every output stays
+ * finite; torch gives NaN there), the same rule as lr_attn_fused_*.  Backward, in place over dprobs:
+ * dscores = scale * P * (dP - sum_k dP P). */
 int lr_attn_softmax_forward(float* scores, const int32_t* key_lens, float scale, int B, int Hh, int T,
                             lr_stream_t stream);
 int lr_attn_softmax_backward(const float* probs, float* dprobs, float scale, int B, int Hh, int T,
@@ -558,7 +561,8 @@ int lr_attn_softmax_backward(const float* probs, float* dprobs, float scale, int
  * projection qkv [B][T][3*nhead*dh] (head h at columns h*dh of each third), out [B][T][nhead*dh]; backward:
  * dout -> dqkv (same layout as qkv; every element written).  One workgroup per (sample, head), T <= 96, dh in
  * {32, 64} (lr_attn_fused_supported); the T x T probabilities never leave the chip (the backward recomputes
- * them).  bf16 operands, fp32 accumulation and softmax. */
+ * them).  bf16 operands, fp32 accumulation and softmax.  key_lens[b] is clamped to [1, T] as in
+ * lr_attn_softmax_forward: a sample of length 0 attends to key 0 alone. */
 int lr_attn_fused_supported(int T, int dh);
 int lr_attn_fused_forward(const float* qkv, const int32_t* key_lens, float* out, float scale, int B, int T,
                           int nhead, int dh, lr_stream_t stream);
@@ -621,7 +625,9 @@ long long lr_fgemm_slab_floats(int M, int N, int splits);
 #define LR_TFM_ATTN_FUSED 8
 #define LR_TFM_ROWBLOCK 16   /* out-projection .. LN2 (and their backward) as ONE launch per layer and direction over 32-row
                                 blocks (lr_tfm_rowblock.hip); needs LR_TFM_X3 and lr_tfm_rowblock_supported(): d_model 256,
-                                feed-forward width 256, 512, 1024 or 2048, at most 8 layers */
+                                feed-forward width 256, 512, 1024 or 2048, at most 8 layers, and B * T * max(F, 768) * 4 <
+                                2^31 (the kernels form 32-bit byte offsets into [B*T][width] tensors and keep the top bit
+                                for "out of range"): 699 050 rows up to F = 512, 524 287 at 1024, 262 143 at 2048 */
 int lr_tfm_rowblock_supported(int B, int T, int Dm, int F, int nlayers);
 size_t lr_tfm_reserve_bytes(int mode, int B, int T, int I, int Dm, int nhead, int F, int nlayers);
 size_t lr_tfm_workspace_bytes(int mode, int B, int T, int I, int Dm, int nhead, int F, int nlayers);

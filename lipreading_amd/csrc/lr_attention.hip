@@ -87,7 +87,7 @@ __device__ __forceinline__ void softmax_keys(f32x16 (&s)[3], int h, int len, flo
       m = fmaxf(m, s[kt][r]);
     }
   m = fmaxf(m, __shfl_xor(m, 32, 64));
-  if (m == LR_NEG_INF) m = 0.f;     // no valid key at all (len == 0): every probability becomes 0
+  if (m == LR_NEG_INF) m = 0.f;     // (no valid key: cannot happen, the callers clamp len to >= 1; kept so that it stays finite)
   float sum = 0.f;
 #pragma unroll
   for (int kt = 0; kt < 3; ++kt)
@@ -122,8 +122,7 @@ __global__ __launch_bounds__(256) void attn_fused_fwd_kernel(const float* __rest
   stage(base + 2 * D, D3, T, dh, nullptr, Vt);
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 31, h = lane >> 5;
-  int len = key_lens[b];
-  if (len > T) len = T;
+  const int len = min(max(key_lens[b], 1), T);   // a sample of length 0 attends to key 0, as lr_attn_softmax_forward has it
   if (wave < 3) {     // query tile `wave`: all three key tiles, so a query's 96 scores sit in two lanes
     f32x16 s[3];
 #pragma unroll
@@ -186,8 +185,7 @@ __global__ __launch_bounds__(256) void attn_fused_bwd_kernel(const float* __rest
   stage(dout + (int64_t)b * T * D + head * dh, D, T, dh, dOs, dOT);
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 31, h = lane >> 5;
-  int len = key_lens[b];
-  if (len > T) len = T;
+  const int len = min(max(key_lens[b], 1), T);   // a sample of length 0 attends to key 0, as lr_attn_softmax_forward has it
   f32x16 p[3], dp[3];
   if (wave < 3) {
 #pragma unroll

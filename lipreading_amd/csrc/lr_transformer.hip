@@ -512,5 +512,10 @@ extern "C" int lr_tfm_backward_weights(int mode, const void* x, float* const* gr
 }
 
 extern "C" int lr_tfm_rowblock_supported(int B, int T, int Dm, int F, int nlayers) {
-  return B > 0 && T > 0 && lr_tfm_rb_supported(Dm, F, nlayers);
+  if (!(B > 0 && T > 0 && lr_tfm_rb_supported(Dm, F, nlayers))) return 0;
+  // the row-block kernels address their [R][ld] tensors (ld up to max(F, 768): f1 / df1, qkv / dqkv) through buffer
+  // resources of 2^31 - 1 bytes with a 32-bit byte offset whose top bit means "out of range" (lr_tfm_rowblock.hip roff):
+  // the largest tensor has to end below 2^31 bytes, which also keeps roff's int element index from wrapping
+  const int64_t ld = F > 768 ? F : 768;
+  return (int64_t)B * T * ld * 4 < ((int64_t)1 << 31);
 }

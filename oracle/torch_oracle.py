@@ -516,3 +516,114 @@ class OracleTransformerEncoder(nn.Module):
     h = self.encoder(h, src_key_padding_mask=pad)
     logits = self.output_proj(h)
     return masked_log_softmax(logits, self.output_mask.expand_as(logits)), h
+
+
+# ---- the transformer encoder layer, piece by piece (include/lipreading_hip.h, "A10"; lr_tfm_*) ------------------------
+# Plain formulas in whatever dtype the arguments have (float64: the reference the kernels are held to; float32: what the
+# exact-fp32 kernels evaluate, in another summation order).  Every Linear goes through `mm`, so the same code restates
+# the LR_TFM_X3 arithmetic (split_bf16_matmul) forward AND backward, which autograd could not do.
+# tests/test_tfm_layer_reference.py pins the float64 evaluation to nn.TransformerEncoderLayer.
+
+def split_bf16_matmul(a, b):
+  """LR_FGEMM_X3 / LR_TFM_X3 on the CPU: each fp32 operand -> bf16 hi = bf16(x) and lo = bf16(x - hi), then
+  a_hi b_hi + a_hi b_lo + a_lo b_hi as three fp32 products (lr_fgemm.hip; the lo x lo term is dropped)."""
+  a, b = a.float(), b.float()
+  ah, bh = a.bfloat16().float(), b.bfloat16().float()
+  al, bl = (a - ah).bfloat16().float(), (b - bh).bfloat16().float()
+  return (ah @ bh + ah @ bl) + al @ bh
+
+
+def layernorm_forward(s, gamma, beta, eps):
+  """-> y, mean [R,1], rstd [R,1] (two passes, biased variance)"""
+  mean = s.mean(-1, keepdim=True)
+  d = s - mean
+  rstd = 1.0 / torch.sqrt((d * d).mean(-1, keepdim=True) + eps)
+  return d * rstd * gamma + beta, mean, rstd
+
+
+def layernorm_backward(s, gamma, mean, rstd, dy):
+  """-> ds, dgamma, dbeta:  ds = rstd (g - mean(g) - xhat mean(g xhat)), g = dy gamma"""
+  xh = (s - mean) * rstd
+  g = dy * gamma
+  ds = rstd * (g - g.mean(-1, keepdim=True) - xh * (g * xh).mean(-1, keepdim=True))
+  return ds, (dy * xh).sum(0), dy.sum(0)
+
+
+def attn_softmax_forward(scores, key_lens, scale):
+  """scores [B,H,T,T] -> softmax over keys of scale * scores, keys >= key_lens[b] at probability exactly 0.  key_lens
+  is clamped to [1, T] (the header's rule: a sample of length 0 attends to key 0 alone; torch gives NaN there)."""
+  T = scores.shape[-1]
+  n = key_lens.clamp(1, T).view(-1, 1, 1, 1)
+  masked = torch.arange(T).view(1, 1, 1, T) >= n
+  return torch.softmax((scores * scale).masked_fill(masked, float("-inf")), dim=-1)
+
+
+def attn_softmax_backward(probs, dprobs, scale):
+  return scale * probs * (dprobs - (dprobs * probs).sum(-1, keepdim=True))
+
+
+def attention_forward(qkv, key_lens, nhead):
+  """qkv [B,T,3D] -> context [B,T,D], probs [B,H,T,T]"""
+  B, T, D3 = qkv.shape
+  D = D3 // 3
+  dh = D // nhead
+  q, k, v = [t.reshape(B, T, nhead, dh).transpose(1, 2) for t in qkv.split(D, dim=-1)]
+  probs = attn_softmax_forward(q @ k.transpose(-1, -2), key_lens, 1.0 / math.sqrt(dh))
+  return (probs @ v).transpose(1, 2).reshape(B, T, D), probs
+
+
+def attention_backward(qkv, probs, da, nhead):
+  B, T, D3 = qkv.shape
+  D = D3 // 3
+  dh = D // nhead
+  q, k, v = [t.reshape(B, T, nhead, dh).transpose(1, 2) for t in qkv.split(D, dim=-1)]
+  do = da.reshape(B, T, nhead, dh).transpose(1, 2)
+  dv = probs.transpose(-1, -2) @ do
+  ds = attn_softmax_backward(probs, do @ v.transpose(-1, -2), 1.0 / math.sqrt(dh))
+  dq, dk = ds @ k, ds.transpose(-1, -2) @ q
+  return torch.cat([t.transpose(1, 2).reshape(B, T, D) for t in (dq, dk, dv)], dim=-1)
+
+
+TFM_LAYER_NAMES = ["input_proj.weight", "input_proj.bias", "in_proj_weight", "in_proj_bias", "out_proj.weight",
+                   "out_proj.bias", "linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias", "norm1.weight",
+                   "norm1.bias", "norm2.weight", "norm2.bias"]
+
+
+def tfm_layer_forward(x, lens, W, pe, nhead, eps=1e-5, mm=torch.matmul):
+  """Input projection + positional table + ONE post-LN encoder layer (the header's formulas at lr_tfm_forward).
+  x [B,T,I]; W: the 14 tensors of TFM_LAYER_NAMES.  Returns everything the backward needs; c['h2'] is the output,
+  c['z'] the feed-forward pre-activations."""
+  B, T, I = x.shape
+  Dm = W[0].shape[0]
+  c = {"x": x.reshape(B * T, I), "B": B, "T": T, "nhead": nhead, "lens": lens}
+  c["h0"] = mm(c["x"], W[0].t()) + W[1] + pe[:T].to(x.dtype).repeat(B, 1)
+  c["qkv"] = mm(c["h0"], W[2].t()) + W[3]
+  a, c["probs"] = attention_forward(c["qkv"].reshape(B, T, 3 * Dm), lens, nhead)
+  c["a"] = a.reshape(B * T, Dm)
+  c["s1"] = mm(c["a"], W[4].t()) + W[5] + c["h0"]
+  c["h1"], c["m1"], c["r1"] = layernorm_forward(c["s1"], W[10], W[11], eps)
+  c["z"] = mm(c["h1"], W[6].t()) + W[7]
+  c["f1"] = torch.relu(c["z"])
+  c["s2"] = mm(c["f1"], W[8].t()) + W[9] + c["h1"]
+  c["h2"], c["m2"], c["r2"] = layernorm_forward(c["s2"], W[12], W[13], eps)
+  return c
+
+
+def tfm_layer_backward(c, W, dh_out, mm=torch.matmul):
+  """dh_out [B*T, Dm] -> dx [B*T, I] and the 14 parameter gradients in TFM_LAYER_NAMES order."""
+  B, T, nhead = c["B"], c["T"], c["nhead"]
+  Dm = W[0].shape[0]
+  g = [None] * 14
+  ds2, g[12], g[13] = layernorm_backward(c["s2"], W[12], c["m2"], c["r2"], dh_out)
+  df1 = mm(ds2, W[8]) * (c["f1"] > 0).to(ds2.dtype)
+  dh1 = mm(df1, W[6]) + ds2
+  ds1, g[10], g[11] = layernorm_backward(c["s1"], W[10], c["m1"], c["r1"], dh1)
+  da = mm(ds1, W[4])
+  dqkv = attention_backward(c["qkv"].reshape(B, T, 3 * Dm), c["probs"], da.reshape(B, T, Dm), nhead).reshape(B * T, 3 * Dm)
+  dh0 = mm(dqkv, W[2]) + ds1
+  g[8], g[9] = mm(ds2.t(), c["f1"]), ds2.sum(0)
+  g[6], g[7] = mm(df1.t(), c["h1"]), df1.sum(0)
+  g[4], g[5] = mm(ds1.t(), c["a"]), ds1.sum(0)
+  g[2], g[3] = mm(dqkv.t(), c["h0"]), dqkv.sum(0)
+  g[0], g[1] = mm(dh0.t(), c["x"]), dh0.sum(0)
+  return mm(dh0, W[0]), g
