@@ -160,6 +160,19 @@ int lr_lmk_landmarks(const float* cropped_pos, const int32_t* rects, const int32
 int lr_lip_crop_u8(const void* frames, const float* lmk, void* out, int n, int H, int W, int S, int npts,
                    int lo, int hi, float margin, lr_stream_t stream);
 
+/* A9 for a whole ragged batch, written straight into the zero-padded batch in ONE launch (the loader's hot path).
+ *   frames  uint8 [sum(lens)][3][H][W]   samples back to back
+ *   lmk     f32   [sum(lens)][npts][3]
+ *   offsets [B] int64  index of sample b's first frame;  lens [B] int32, 1 <= lens[b] <= t_max
+ *   out     uint8 [B][t_max][3][S][S]:
+ *           out[b,t] = t < lens[b] ? crop(frames[offsets[b]+t], lmk[offsets[b]+t]) : 0
+ * crop() is lr_lip_crop_u8's arithmetic (one shared device function): the bytes are identical to B per-sample calls
+ * into a zeroed batch.  EVERY byte of out is written, so the caller allocates it uninitialised.  lens[b] > t_max is
+ * the caller's error and is clamped (nothing is written outside out). */
+int lr_lip_crop_collate_u8(const void* frames, const float* lmk, const int64_t* offsets, const int32_t* lens,
+                           void* out, int B, int t_max, int H, int W, int S, int npts, int lo, int hi, float margin,
+                           lr_stream_t stream);
+
 /* ---- dense fp32 contraction (MFMA f32 16x16x4 / 32x32x2), used by A3 ------------------- */
 
 /* C[M,N] = alpha * op(A)[M,K] * op(B)[K,N] + beta * C + bias[N]   (row-major, fp32)

@@ -881,24 +881,50 @@ int lr_colsum_partial(const float* x, int ld, int rows, int ncol, float* partial
 // of landmarks [lo,hi) in image coordinates -> centre (cx,cy), side = max(w,h)*(1+2*margin), at least
 // 2 px -> square window resampled to S x S with bilinear interpolation, half-pixel centres, source
 // coordinates clamped to the image (edge replication), result rounded to nearest uint8.
+// lip_crop_box / lip_crop_pixel are the ONE statement of that arithmetic: the per-sample kernel (lr_lip_crop_u8) and the
+// whole-batch kernel (lr_lip_crop_collate_u8) both inline them, so the compiler contracts the same multiplies and
+// adds in both and their bytes agree.  The multiply-adds whose rounding matters are spelled fmaf (what the compiler
+// made of `a + b * c` here all along); the other products are by 0.5 or 2 and exact either way.
+namespace {
+// box[0] = left, box[1] = top, box[2] = source pixels per output pixel
+__device__ __forceinline__ void lip_crop_box(const float* __restrict__ L, int lo, int hi, float margin, int S,
+                                             float* box) {
+  float x0 = L[lo * 3], x1 = x0, y0 = L[lo * 3 + 1], y1 = y0;
+  for (int p = lo + 1; p < hi; ++p) {
+    const float x = L[p * 3], y = L[p * 3 + 1];
+    x0 = fminf(x0, x); x1 = fmaxf(x1, x); y0 = fminf(y0, y); y1 = fmaxf(y1, y);
+  }
+  float side = fmaxf(x1 - x0, y1 - y0) * (1.f + 2.f * margin);
+  side = fmaxf(side, 2.f);
+  box[0] = 0.5f * (x0 + x1) - 0.5f * side;   // left
+  box[1] = 0.5f * (y0 + y1) - 0.5f * side;   // top
+  box[2] = side / (float)S;                  // source pixels per output pixel
+}
+
+// output pixel (oy, ox) of the plane P [H][W]
+__device__ __forceinline__ unsigned char lip_crop_pixel(const unsigned char* __restrict__ P, int H, int W, int oy, int ox,
+                                                        float left, float top, float scale) {
+  float sx = fmaf((float)ox + 0.5f, scale, left) - 0.5f;
+  float sy = fmaf((float)oy + 0.5f, scale, top) - 0.5f;
+  sx = fminf(fmaxf(sx, 0.f), (float)(W - 1));
+  sy = fminf(fmaxf(sy, 0.f), (float)(H - 1));
+  const int ix = (int)floorf(sx), iy = (int)floorf(sy);
+  const int ix1 = min(ix + 1, W - 1), iy1 = min(iy + 1, H - 1);
+  const float fx = sx - (float)ix, fy = sy - (float)iy;
+  const float a = (float)P[iy * W + ix], b = (float)P[iy * W + ix1];
+  const float d = (float)P[iy1 * W + ix], e = (float)P[iy1 * W + ix1];
+  const float top_v = fmaf(b - a, fx, a), bot_v = fmaf(e - d, fx, d);
+  const float v = fmaf(bot_v - top_v, fy, top_v);
+  return (unsigned char)fminf(fmaxf(floorf(v + 0.5f), 0.f), 255.f);
+}
+}  // namespace
+
 __global__ void lip_crop_kernel(const unsigned char* __restrict__ frames, const float* __restrict__ lmk,
                                 unsigned char* __restrict__ out, int H, int W, int S, int npts, int lo,
                                 int hi, float margin) {
   __shared__ float box[4];
   const int n = blockIdx.x;
-  const float* L = lmk + (int64_t)n * npts * 3;
-  if (threadIdx.x == 0) {
-    float x0 = L[lo * 3], x1 = x0, y0 = L[lo * 3 + 1], y1 = y0;
-    for (int p = lo + 1; p < hi; ++p) {
-      const float x = L[p * 3], y = L[p * 3 + 1];
-      x0 = fminf(x0, x); x1 = fmaxf(x1, x); y0 = fminf(y0, y); y1 = fmaxf(y1, y);
-    }
-    float side = fmaxf(x1 - x0, y1 - y0) * (1.f + 2.f * margin);
-    side = fmaxf(side, 2.f);
-    box[0] = 0.5f * (x0 + x1) - 0.5f * side;   // left
-    box[1] = 0.5f * (y0 + y1) - 0.5f * side;   // top
-    box[2] = side / (float)S;                  // source pixels per output pixel
-  }
+  if (threadIdx.x == 0) lip_crop_box(lmk + (int64_t)n * npts * 3, lo, hi, margin, S, box);
   __syncthreads();
   const float left = box[0], top = box[1], scale = box[2];
   const unsigned char* F = frames + (int64_t)n * 3 * H * W;
@@ -906,19 +932,7 @@ __global__ void lip_crop_kernel(const unsigned char* __restrict__ frames, const 
   for (int i = threadIdx.x; i < 3 * S * S; i += blockDim.x) {
     const int c = i / (S * S), r = i - c * S * S;
     const int oy = r / S, ox = r - oy * S;
-    float sx = left + ((float)ox + 0.5f) * scale - 0.5f;
-    float sy = top + ((float)oy + 0.5f) * scale - 0.5f;
-    sx = fminf(fmaxf(sx, 0.f), (float)(W - 1));
-    sy = fminf(fmaxf(sy, 0.f), (float)(H - 1));
-    const int ix = (int)floorf(sx), iy = (int)floorf(sy);
-    const int ix1 = min(ix + 1, W - 1), iy1 = min(iy + 1, H - 1);
-    const float fx = sx - (float)ix, fy = sy - (float)iy;
-    const unsigned char* P = F + (int64_t)c * H * W;
-    const float a = (float)P[iy * W + ix], b = (float)P[iy * W + ix1];
-    const float d = (float)P[iy1 * W + ix], e = (float)P[iy1 * W + ix1];
-    const float top_v = a + (b - a) * fx, bot_v = d + (e - d) * fx;
-    const float v = top_v + (bot_v - top_v) * fy;
-    O[i] = (unsigned char)fminf(fmaxf(floorf(v + 0.5f), 0.f), 255.f);
+    O[i] = lip_crop_pixel(F + (int64_t)c * H * W, H, W, oy, ox, left, top, scale);
   }
 }
 
@@ -928,6 +942,84 @@ extern "C" int lr_lip_crop_u8(const void* frames, const float* lmk, void* out, i
   LR_CHECK_ARG(npts > 0 && lo >= 0 && hi > lo && hi <= npts && margin >= 0.f);
   LR_LAUNCH(lip_crop_kernel, dim3(n), dim3(256), 0, stream, (const unsigned char*)frames, lmk,
             (unsigned char*)out, H, W, S, npts, lo, hi, margin);
+  return lr_launch_status();
+}
+
+// A9 for a whole ragged batch in one launch (lr_lip_crop_collate_u8): a capped grid strides over the B * t_max
+// (sample, frame) pairs of the padded batch.  A real frame is cropped exactly as lip_crop_kernel crops it, V
+// horizontally adjacent pixels per thread stored as one V-byte vector; a padding frame is filled with zeros V bytes at
+// a time.  Every byte of out is written.  The box of a frame is computed by one lane into one of two LDS slots, so
+// that one barrier per frame is enough: the slot written for frame i + 2 is the one whose readers all passed the
+// barrier of frame i + 1.
+namespace {
+template <int V> struct CropVec;
+template <> struct CropVec<1> { typedef unsigned char T; };
+template <> struct CropVec<4> { typedef uint32_t T; };
+template <> struct CropVec<16> { typedef uint4 T; };
+
+template <int V>
+__global__ __launch_bounds__(256) void lip_crop_collate_kernel(
+    const unsigned char* __restrict__ frames, const float* __restrict__ lmk, const int64_t* __restrict__ offsets,
+    const int32_t* __restrict__ lens, unsigned char* __restrict__ out, int B, int t_max, int H, int W, int S, int npts,
+    int lo, int hi, float margin) {
+  typedef typename CropVec<V>::T vec_t;
+  __shared__ float box[2][4];
+  const int per_row = S / V;                 // S % V == 0 (the launcher picks V)
+  const int items = 3 * S * per_row;         // V-pixel groups of one frame
+  const int pairs = B * t_max;
+  int parity = 0;
+  for (int p = blockIdx.x; p < pairs; p += gridDim.x) {   // uniform per workgroup: the barrier below is safe
+    const int b = p / t_max, t = p - b * t_max;
+    const int len = min(lens[b], t_max);     // lens[b] > t_max is the caller's error; never write outside out
+    vec_t* O = reinterpret_cast<vec_t*>(out + (int64_t)p * 3 * S * S);
+    if (t >= len) {
+      vec_t zero;
+      __builtin_memset(&zero, 0, sizeof(zero));
+      for (int i = threadIdx.x; i < items; i += blockDim.x) O[i] = zero;
+      continue;
+    }
+    const int64_t n = offsets[b] + t;
+    float* bx = box[parity];
+    parity ^= 1;
+    if (threadIdx.x == 0) lip_crop_box(lmk + n * npts * 3, lo, hi, margin, S, bx);
+    __syncthreads();
+    const float left = bx[0], top = bx[1], scale = bx[2];
+    const unsigned char* F = frames + n * 3 * H * W;
+    for (int i = threadIdx.x; i < items; i += blockDim.x) {
+      const int c = i / (S * per_row), r = i - c * S * per_row;
+      const int oy = r / per_row, ox = (r - oy * per_row) * V;
+      const unsigned char* P = F + (int64_t)c * H * W;
+      union { vec_t v; unsigned char px[V]; } u;
+#pragma unroll
+      for (int k = 0; k < V; ++k) u.px[k] = lip_crop_pixel(P, H, W, oy, ox + k, left, top, scale);
+      O[i] = u.v;
+    }
+  }
+}
+}  // namespace
+
+extern "C" int lr_lip_crop_collate_u8(const void* frames, const float* lmk, const int64_t* offsets,
+                                      const int32_t* lens, void* out, int B, int t_max, int H, int W, int S, int npts,
+                                      int lo, int hi, float margin, lr_stream_t stream) {
+  LR_CHECK_ARG(frames && lmk && offsets && lens && out && B > 0 && t_max > 0 && H > 0 && W > 0 && S > 0);
+  LR_CHECK_ARG(npts > 0 && lo >= 0 && hi > lo && hi <= npts && margin >= 0.f);
+  LR_CHECK_ARG((int64_t)B * t_max <= INT32_MAX && (int64_t)S * S <= INT32_MAX / 3);
+  const int pairs = B * t_max;
+  const dim3 grid(pairs < 2048 ? pairs : 2048);   // 256 CUs x 8 workgroups; the rest by the grid stride
+  const unsigned char* f = (const unsigned char*)frames;
+  unsigned char* o = (unsigned char*)out;
+  // a frame of out starts at a multiple of 3 * S * S bytes: vector stores need S % V == 0 and an aligned base
+  const bool aligned = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+  if (aligned && S % 16 == 0) {
+    LR_LAUNCH(lip_crop_collate_kernel<16>, grid, dim3(256), 0, stream, f, lmk, offsets, lens, o, B, t_max, H, W, S,
+              npts, lo, hi, margin);
+  } else if (aligned && S % 4 == 0) {
+    LR_LAUNCH(lip_crop_collate_kernel<4>, grid, dim3(256), 0, stream, f, lmk, offsets, lens, o, B, t_max, H, W, S,
+              npts, lo, hi, margin);
+  } else {
+    LR_LAUNCH(lip_crop_collate_kernel<1>, grid, dim3(256), 0, stream, f, lmk, offsets, lens, o, B, t_max, H, W, S,
+              npts, lo, hi, margin);
+  }
   return lr_launch_status();
 }
 

@@ -254,8 +254,13 @@ class BatchLoader(object):
     return iterate_batches(self.dataset, self.batch_size, self.collate_fn)
 
 
-def make_loader(dataset, batch_size, collate_fn):
-  return BatchLoader(dataset, batch_size, collate_fn)
+def make_loader(dataset, batch_size, collate_fn, prefetch=0, **loader_args):
+  """prefetch=0: the plain BatchLoader over `collate_fn`.  prefetch=N > 0: a loader.PrefetchLoader of depth N that
+  yields the same batches (loader_args: device, pixels, size, margin, workers — what `collate_fn` was made with)."""
+  if not prefetch:
+    return BatchLoader(dataset, batch_size, collate_fn)
+  from .loader import PrefetchLoader
+  return PrefetchLoader(dataset, batch_size, depth=int(prefetch), **loader_args)
 
 
 _WORDS = ("the quick brown fox jumps over a lazy dog and then it went home to see what was going on "

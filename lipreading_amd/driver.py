@@ -48,6 +48,9 @@ DEFAULTS = dict(  # train.py:134-167
     # CER of the joint CTC/attention beam search, the CTC head's prefix probability weighted by --attn_ctc_weight;
     # needs --enable_ctc)
     attn_decode="teacher", attn_beam_width=10, attn_max_label_len=100, attn_ctc_weight=0.3,
+    # --prefetch=N > 0: the three loaders are loader.PrefetchLoader of depth N (batch k+1 is gathered into pinned
+    # memory, uploaded and collated on a copy stream while step k runs); 0 = the plain BatchLoader
+    prefetch=0,
 )
 
 
@@ -278,7 +281,8 @@ def run(**flags):
     collate = make_pixel_collate_fn(device, size=f["crop_size"])
   else:
     collate = make_collate_fn(device)   # padded on the GPU (lr_collate_pad_f32); lengths stay on the host
-  train_loader, val_loader, test_loader = (make_loader(d, f["batch_size"], collate) for d in sets)
+  train_loader, val_loader, test_loader = (make_loader(d, f["batch_size"], collate, prefetch=f["prefetch"], device=device,
+                                                       pixels=pixels, size=f["crop_size"]) for d in sets)
   print("Initializing model")
   ctc_only = bool(f["ctc_only"])
   if pixels or f["encoder"] == "transformer":

@@ -1,0 +1,429 @@
+"""Prefetching batch loader: batch k+1 is gathered, uploaded and collated while the GPU runs step k.
+
+`PrefetchLoader` yields what `BatchLoader(dataset, batch_size, make_collate_fn(device))` (or the pixel collate)
+yields — the same batches in the same order, bit for bit — but takes the work in front of the step off the step's
+stream and off the step's critical path:
+
+  host stage    worker threads gather the samples of the next `depth` batches straight into a ring of `depth + 1`
+                PINNED host slots (one contiguous slot per batch: frames or landmark rows, landmarks, offsets, lens),
+                each sample copied once (numpy's copy releases the GIL), and build the padded chars and the lengths;
+  device stage  the thread that iterates the loader uploads a ready slot with ONE asynchronous copy on the loader's
+                own stream, collates it there in ONE launch (lr_lip_crop_collate_u8 / lr_collate_pad_f32) and records
+                an event; the consumer's stream waits on that event (no host synchronisation).
+
+Rules (DESIGN.md "Prefetching loader"):
+  * no HIP call on a worker thread — workers touch host memory only; every enqueue, event record and event query is
+    issued by the iterating thread between two steps, never while a step is being captured into a hipGraph;
+  * a padded batch is an ordinary tensor of torch's allocator and stays valid for as long as the caller holds it; only
+    the pinned slots and the ragged device staging are recycled, a slot only after the event behind its upload has
+    completed;
+  * a worker's exception is re-raised at the batch it belongs to; abandoning an iteration joins the workers; every
+    blocking host wait has a time limit.
+
+The host stage (`HostStage`) needs no GPU: it takes the buffer factory as a parameter.
+"""
+import queue
+import threading
+import time
+
+import numpy as np
+import torch
+
+from . import _C
+
+MAX_WORKERS = 8         # a GPU job may use 16 CPUs; never sized by os.cpu_count()
+WAIT_SECONDS = 120.0    # upper bound of every blocking wait on the host
+_ALIGN = 256            # every region of a slot starts on a 256-byte boundary (vector loads, int64 offsets)
+
+
+def _align(n):
+  return (int(n) + _ALIGN - 1) // _ALIGN * _ALIGN
+
+
+def batch_plan(n, batch_size):
+  """Index ranges [(lo, hi)] of `BatchLoader`'s batches: consecutive, un-shuffled, a ragged last one."""
+  assert batch_size > 0
+  return [(lo, min(lo + batch_size, n)) for lo in range(0, n, batch_size)]
+
+
+class PackedBatch(object):
+  """What the host stage leaves in a slot: the byte offsets of its regions and the host half of the batch.
+
+  pixels:    frames u8 [rows][3][H][W] | lmk f32 [rows][68][3] | offsets i64 [B] | lens i32 [B]
+  landmarks: rows f32 [rows][feat]                             | offsets i64 [B] | lens i32 [B]
+  frame_lens / chars / char_lens: int64 numpy arrays, the values the plain collate functions return."""
+
+  def __init__(self):
+    self.index = self.slot = None
+    self.pixels = False
+    self.B = self.t_max = self.rows = self.nbytes = 0
+    self.frames_off = self.lmk_off = self.offsets_off = self.lens_off = 0
+    self.H = self.W = self.feat = 0
+    self.tail = ()
+    self.frame_lens = self.chars = self.char_lens = None
+
+  def region(self, buf, name):
+    """A numpy view of one region of `buf` (the uint8 array the batch was packed into)."""
+    B, rows = self.B, self.rows
+    if name == "frames":
+      if self.pixels:
+        return buf[self.frames_off:self.frames_off + rows * 3 * self.H * self.W].reshape(rows, 3, self.H, self.W)
+      return buf[self.frames_off:self.frames_off + rows * self.feat * 4].view(np.float32).reshape(rows, self.feat)
+    if name == "lmk":
+      assert self.pixels
+      return buf[self.lmk_off:self.lmk_off + rows * 68 * 3 * 4].view(np.float32).reshape(rows, 68, 3)
+    if name == "offsets":
+      return buf[self.offsets_off:self.offsets_off + B * 8].view(np.int64)
+    if name == "lens":
+      return buf[self.lens_off:self.lens_off + B * 4].view(np.int32)
+    raise KeyError(name)
+
+
+def _pad_chars(captions):
+  """The host half of data.make_collate_fn: chars int64 (B, Cmax) PAD=0 and their lengths."""
+  caps = [np.asarray(c, dtype=np.int64) for c in captions]
+  char_lens = np.array([len(c) for c in caps], dtype=np.int64)
+  chars = np.zeros((len(caps), int(char_lens.max())), dtype=np.int64)
+  for i, c in enumerate(caps):
+    chars[i, :len(c)] = c
+  return chars, char_lens
+
+
+def pack_batch(samples, pixels, buf):
+  """Gather one batch into `buf` (1-D uint8 numpy array, a slot of the ring).  Host memory only.  Raises what the
+  plain collate raises for a malformed batch (AssertionError), before anything is written."""
+  pb = PackedBatch()
+  pb.pixels = bool(pixels)
+  assert len(samples) > 0
+  if pixels:
+    assert all(len(x) == 2 and len(x[0]) == 2 for x in samples)          # data.make_pixel_collate_fn
+    pairs, captions = zip(*samples)
+    pix = [np.asarray(p[0]) for p in pairs]
+    lmk = [np.asarray(p[1]) for p in pairs]
+    H, W = pix[0].shape[2], pix[0].shape[3]
+    assert all(p.dtype == np.uint8 and p.shape[1:] == (3, H, W) for p in pix)
+    assert all(l.shape[0] == p.shape[0] and l.shape[1:] == (68, 3) for l, p in zip(lmk, pix))
+    lens = np.array([len(p) for p in pix], dtype=np.int64)
+    rows = int(lens.sum())
+    pb.H, pb.W = int(H), int(W)
+    pb.frames_off = 0
+    pb.lmk_off = _align(rows * 3 * H * W)
+    pb.offsets_off = pb.lmk_off + _align(rows * 68 * 3 * 4)
+  else:
+    assert all(len(x) == 2 for x in samples)                              # data.make_collate_fn
+    seqs, captions = zip(*samples)
+    pix = [np.asarray(s) for s in seqs]
+    tail = pix[0].shape[1:]
+    assert all(a.shape[1:] == tail for a in pix)                          # data.pad_frames
+    lens = np.array([len(a) for a in pix], dtype=np.int64)
+    rows = int(lens.sum())
+    pb.tail = tuple(int(d) for d in tail)
+    pb.feat = int(np.prod(tail)) if tail else 1
+    pb.frames_off = 0
+    pb.offsets_off = _align(rows * pb.feat * 4)
+  pb.B, pb.rows, pb.t_max = len(samples), rows, int(lens.max())
+  pb.lens_off = pb.offsets_off + _align(pb.B * 8)
+  pb.nbytes = pb.lens_off + _align(pb.B * 4)
+  assert pb.nbytes <= buf.shape[0], "slot of %d bytes is too small for a batch of %d" % (buf.shape[0], pb.nbytes)
+  offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+  frames = pb.region(buf, "frames")
+  lmk_rows = pb.region(buf, "lmk") if pixels else None
+  for b in range(pb.B):                      # every sample is copied (and converted) once, straight into the slot
+    lo, n = int(offsets[b]), int(lens[b])
+    if pixels:
+      np.copyto(frames[lo:lo + n], pix[b])
+      np.copyto(lmk_rows[lo:lo + n], lmk[b], casting="unsafe")             # as np.asarray(.., dtype=float32)
+    else:
+      np.copyto(frames[lo:lo + n], pix[b].reshape(n, pb.feat), casting="unsafe")
+  pb.region(buf, "offsets")[:] = offsets
+  pb.region(buf, "lens")[:] = lens
+  pb.frame_lens = lens
+  pb.chars, pb.char_lens = _pad_chars(captions)
+  return pb
+
+
+def _slot_bytes(dataset, plan, pixels):
+  """Bytes of the largest batch (the dataset is in memory): sizes only, the shape checks belong to pack_batch."""
+  most = _ALIGN
+  for lo, hi in plan:
+    a = b = 0
+    for i in range(lo, hi):
+      try:
+        x = dataset[i][0]
+        if pixels:
+          a += int(np.asarray(x[0]).nbytes)
+          b += int(np.asarray(x[1]).size) * 4
+        else:
+          a += int(np.asarray(x).size) * 4
+      except Exception:     # a malformed sample: its batch raises when it is packed
+        continue
+    most = max(most, _align(a) + _align(b) + _align((hi - lo) * 8) + _align((hi - lo) * 4))
+  return most
+
+
+def _plain_alloc(nbytes):
+  return torch.empty(int(nbytes), dtype=torch.uint8)
+
+
+def _pinned_alloc(nbytes):
+  return torch.empty(int(nbytes), dtype=torch.uint8, pin_memory=True)
+
+
+class _HostEpoch(object):
+  """The workers of one pass over the dataset.  submit(slot) hands the next batch of the plan to a worker together
+  with the slot it may fill; get(k) returns batch k's PackedBatch or re-raises its worker's exception."""
+
+  def __init__(self, stage):
+    self._dataset, self._plan, self._pixels = stage.dataset, stage.plan, stage.pixels
+    self._bufs = stage._np
+    self._tasks = queue.Queue()
+    self._cv = threading.Condition()
+    self._results = {}
+    self._stop = threading.Event()
+    self.submitted = 0
+    self.threads = [threading.Thread(target=self._work, name="lipreading-prefetch-%d" % i, daemon=True)
+                    for i in range(stage.workers)]
+    for t in self.threads:
+      t.start()
+
+  def _work(self):
+    while True:
+      task = self._tasks.get()
+      if task is None or self._stop.is_set():
+        return
+      k, slot = task
+      try:
+        lo, hi = self._plan[k]
+        res = pack_batch([self._dataset[i] for i in range(lo, hi)], self._pixels, self._bufs[slot])
+        res.index, res.slot = k, slot
+      except BaseException as exc:   # handed to the consumer, which raises it at batch k
+        res = exc
+      with self._cv:
+        self._results[k] = res
+        self._cv.notify_all()
+
+  def submit(self, slot):
+    if self._stop.is_set() or self.submitted >= len(self._plan):
+      return False
+    self._tasks.put((self.submitted, slot))
+    self.submitted += 1
+    return True
+
+  def ready(self, k):
+    with self._cv:
+      return k in self._results
+
+  def get(self, k, timeout=WAIT_SECONDS):
+    assert k < self.submitted, "batch %d was never handed to a worker" % k
+    with self._cv:
+      if not self._cv.wait_for(lambda: k in self._results, timeout):
+        raise TimeoutError("batch %d was not packed within %.0f s" % (k, timeout))
+      res = self._results.pop(k)
+    if isinstance(res, BaseException):
+      raise res
+    return res
+
+  def close(self, timeout=WAIT_SECONDS):
+    """Stop and join the workers (a worker finishes the sample copy it is in, nothing more)."""
+    if self._stop.is_set() and not any(t.is_alive() for t in self.threads):
+      return
+    self._stop.set()
+    for _ in self.threads:
+      self._tasks.put(None)
+    deadline = time.monotonic() + timeout
+    for t in self.threads:
+      t.join(max(0.0, deadline - time.monotonic()))
+    alive = [t.name for t in self.threads if t.is_alive()]
+    if alive:
+      raise RuntimeError("prefetch workers did not stop within %.0f s: %s" % (timeout, ", ".join(alive)))
+
+
+class HostStage(object):
+  """Batch plan, ring of host slots and worker threads; no GPU needed.
+
+  alloc(nbytes) -> 1-D uint8 CPU tensor: pinned for the GPU path, plain `torch.empty` for host-only use.  Iterating
+  the stage yields the PackedBatch of every batch in order; a batch's slot goes back to the workers when the consumer
+  asks for the next batch (PrefetchLoader drives the same workers but returns a slot only after its upload)."""
+
+  def __init__(self, dataset, batch_size, pixels=False, depth=2, workers=2, alloc=None):
+    assert depth >= 1 and workers >= 1
+    self.dataset, self.batch_size, self.pixels = dataset, int(batch_size), bool(pixels)
+    self.depth, self.workers = int(depth), min(int(workers), MAX_WORKERS)
+    self.plan = batch_plan(len(dataset), self.batch_size)
+    self.slot_bytes = _slot_bytes(dataset, self.plan, self.pixels)
+    alloc = alloc or _plain_alloc
+    self.slots = [alloc(self.slot_bytes) for _ in range(self.depth + 1)]
+    assert all(s.dtype == torch.uint8 and s.dim() == 1 and s.numel() >= self.slot_bytes and not s.is_cuda
+               for s in self.slots)
+    self._np = [s.numpy() for s in self.slots]
+    self._epoch = None
+
+  def __len__(self):
+    return len(self.plan)
+
+  def open(self):
+    """Start the workers of a new pass (the previous pass, if it was abandoned, is shut down first)."""
+    self.close()
+    self._epoch = _HostEpoch(self)
+    return self._epoch
+
+  def close(self):
+    ep, self._epoch = self._epoch, None
+    if ep is not None:
+      ep.close()
+
+  def threads_alive(self):
+    ep = self._epoch
+    return 0 if ep is None else sum(t.is_alive() for t in ep.threads)
+
+  def __iter__(self):
+    ep = self.open()
+    try:
+      for slot in range(len(self.slots)):
+        ep.submit(slot)
+      for k in range(len(self.plan)):
+        pb = ep.get(k)
+        yield pb
+        ep.submit(pb.slot)
+    finally:
+      ep.close()
+      if self._epoch is ep:
+        self._epoch = None
+
+  def __del__(self):
+    try:
+      self.close()
+    except Exception:
+      pass
+
+
+def _host_tensors(pb, pinned):
+  """frame_lens, chars, char_lens as fresh int64 host tensors (pinned: the caller's .to(device, non_blocking=True) is
+  then asynchronous) — views of ONE allocation that the batch owns; it is not part of the recycled slot."""
+  B, C = pb.chars.shape
+  t = torch.empty(B * (C + 2), dtype=torch.int64, pin_memory=pinned)
+  a = t.numpy()
+  a[:B] = pb.frame_lens
+  a[B:2 * B] = pb.char_lens
+  a[2 * B:].reshape(B, C)[...] = pb.chars
+  return t[:B], t[2 * B:].view(B, C), t[B:2 * B]
+
+
+class PrefetchLoader(object):
+  """Drop-in for `BatchLoader(dataset, batch_size, make_collate_fn(device))` — with pixels=True for
+  `make_pixel_collate_fn(device, size, margin)` — that prepares up to `depth` batches ahead of the consumer.
+
+  Yields (frames f32 (B,Tmax,68,3) or clips u8 (B,Tmax,3,size,size) on `device`, frame_lens i64, chars i64 (B,Cmax)
+  PAD=0, char_lens i64), the last three on the host (pinned).  Re-iterable; one pass at a time."""
+
+  def __init__(self, dataset, batch_size, device, pixels=False, size=96, margin=0.3, depth=2, workers=2, alloc=None):
+    dev = torch.device(device)
+    if dev.type != "cuda":
+      raise _C.LipReadingHipError("collation runs on the MI355X only (no CPU fallback)")
+    if dev.index is None:
+      dev = torch.device("cuda", torch.cuda.current_device())
+    self.dataset, self.batch_size, self.device = dataset, int(batch_size), dev
+    self.pixels, self.size, self.margin = bool(pixels), int(size), float(margin)
+    self.depth = int(depth)
+    self._pinned = alloc is None
+    self.host = HostStage(dataset, batch_size, pixels=pixels, depth=depth, workers=workers,
+                          alloc=alloc or _pinned_alloc)
+    with torch.cuda.device(dev):
+      self._copy = torch.cuda.Stream(dev)
+      # ragged device staging, one per slot: rewritten only by a later upload on the same stream
+      self._stage = [torch.empty(self.host.slot_bytes, dtype=torch.uint8, device=dev) for _ in self.host.slots]
+    self._pending = [None] * len(self.host.slots)    # the event behind the last upload out of each slot
+    from .landmarks import _mouth
+    self._mouth = _mouth
+
+  def __len__(self):
+    return len(self.host)
+
+  def close(self):
+    self.host.close()
+
+  def _enqueue(self, pb):
+    """Upload slot -> staging, collate into a fresh padded batch, record the event.  Iterating thread only."""
+    L = _C.lib()
+    dev, slot = self.device, pb.slot
+    with torch.cuda.device(dev), torch.cuda.stream(self._copy):
+      stage = self._stage[slot]
+      stage[:pb.nbytes].copy_(self.host.slots[slot][:pb.nbytes], non_blocking=True)    # the batch's ONE upload
+      base, s = stage.data_ptr(), self._copy.cuda_stream
+      if self.pixels:
+        out = torch.empty((pb.B, pb.t_max, 3, self.size, self.size), dtype=torch.uint8, device=dev)
+        _C.check(L.lr_lip_crop_collate_u8(base + pb.frames_off, base + pb.lmk_off, base + pb.offsets_off,
+                                          base + pb.lens_off, out.data_ptr(), pb.B, pb.t_max, pb.H, pb.W, self.size,
+                                          68, self._mouth.start, self._mouth.stop, self.margin, s), "lr_lip_crop_collate_u8")
+      else:
+        out = torch.empty((pb.B, pb.t_max, pb.feat), dtype=torch.float32, device=dev)
+        _C.check(L.lr_collate_pad_f32(base + pb.frames_off, base + pb.offsets_off, base + pb.lens_off,
+                                      out.data_ptr(), pb.B, pb.t_max, pb.feat, s), "lr_collate_pad_f32")
+        out = out.reshape((pb.B, pb.t_max) + pb.tail)
+      event = torch.cuda.Event()
+      event.record(self._copy)
+    self._pending[slot] = event
+    return out, event, _host_tensors(pb, self._pinned)
+
+  def _recycle(self, ep, busy, block=False):
+    """Slots whose upload (and collate) has completed go back to the workers.  block: wait, with a time limit, until
+    at least one has."""
+    deadline = time.monotonic() + WAIT_SECONDS
+    while True:
+      recycled = 0
+      for slot in list(busy):
+        ev = self._pending[slot]
+        if ev is None or ev.query():
+          self._pending[slot] = None
+          busy.remove(slot)
+          ep.submit(slot)
+          recycled += 1
+      if not block or recycled:
+        return
+      assert busy, "no slot is being uploaded and none is with a worker"
+      if time.monotonic() > deadline:
+        raise TimeoutError("no upload of the prefetch ring completed within %.0f s" % WAIT_SECONDS)
+      time.sleep(1e-4)
+
+  def __iter__(self):
+    ep = self.host.open()
+    try:
+      nb = len(self.host.plan)
+      busy = list(range(len(self._pending)))     # slots not with a worker (an abandoned pass may have left events)
+      inflight = {}
+      enq = 0                                    # next batch to enqueue on the device
+      failed = None                              # the exception of a batch ahead of the consumer
+      for k in range(nb):
+        self._recycle(ep, busy)
+        while ep.submitted <= k:                 # every slot is still being uploaded: wait for one
+          self._recycle(ep, busy, block=True)
+        # batch k itself (the first call of a pass primes the pipe), then whatever is ready of the batches behind it
+        while enq < nb and (enq <= k or (failed is None and enq <= k + self.depth and enq < ep.submitted
+                                         and ep.ready(enq))):
+          try:
+            if failed is not None:
+              raise failed
+            pb = ep.get(enq)
+          except BaseException as exc:           # a worker's exception belongs to ITS batch: raised when k gets there
+            if enq <= k:
+              raise
+            failed = exc
+            break
+          inflight[enq] = self._enqueue(pb)
+          busy.append(pb.slot)
+          enq += 1
+        out, event, (frame_lens, chars, char_lens) = inflight.pop(k)
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(event)                    # device-side wait only
+        out.record_stream(cur)                   # allocated under the copy stream, consumed on this one
+        yield out, frame_lens, chars, char_lens
+    finally:
+      ep.close()
+      if self.host._epoch is ep:
+        self.host._epoch = None
+
+  def __del__(self):
+    try:
+      self.close()
+    except Exception:
+      pass
