@@ -796,6 +796,59 @@ int lr_ctc_beam_lm_decode(const float* probs, int64_t stride_b, int64_t stride_t
                           int32_t* out_ids, int32_t* out_offsets, int32_t* out_lens, float* out_scores,
                           void* workspace, size_t workspace_bytes, int B, int T, int C, lr_stream_t stream);
 
+/* ---- A6d: edit-distance scoring of decoded ids — decoder.py:44-73 (Decoder.wer / Decoder.cer) on the device ---- */
+/* The reference scores joined label strings on the host with the Levenshtein package.  Here the ids stay on the
+ * device (lipreading_amd/csrc/lr_edit.hip): every class id spells a string over the caller's
+ * alphabet of K symbols — spell_sym[spell_off[c] .. spell_off[c+1]) for class c, spell_off [n_classes+1], both int32
+ * on the device; a dropped marker spells nothing — and a sequence expands to the concatenation of its spellings.
+ *   LR_EDIT_CHARS        symbols equal to space_sym (-1: none) are deleted from both expansions; Levenshtein distance
+ *                        over symbols (Decoder.cer).
+ *   LR_EDIT_WORDS        both expansions are split at runs of space_sym, no empty words (str.split()); Levenshtein
+ *                        distance over words, two words equal iff their symbols are (Decoder.wer).
+ *   LR_EDIT_CHARS_ALIGN  LR_EDIT_CHARS plus the alignment: from (n, m), at (i, j) the diagonal if i, j > 0 and
+ *                        D[i][j] == D[i-1][j-1] + (h[i-1] != r[j-1]) (a hit, or a substitution), else the reference
+ *                        side if j > 0 and D[i][j] == D[i][j-1] + 1 (a deletion), else the hypothesis side (an
+ *                        insertion).  conf [(K+1)][(K+1)] int64, or NULL: conf[r][h] += 1 per diagonal step,
+ *                        conf[r][K] per deletion, conf[K][h] per insertion.
+ *   hyp / ref            int32 ids, pair b's row at hyp + b * hyp_stride (elements), hyp_width / ref_width ids wide;
+ *                        hyp_lens / ref_lens int32, pair b's at [b * *_lens_stride].  Ids past the length are never
+ *                        read.
+ *   out                  [B][LR_EDIT_OUT_STRIDE] int32: status, distance, reference length, hypothesis length (in
+ *                        units), hits, substitutions, insertions, deletions (0 without alignment).  status 0, or
+ *                        LR_EDIT_BAD_ID (an id inside the length outside [0, n_classes)), LR_EDIT_BAD_LENGTH (a length
+ *                        outside [0, width]), LR_EDIT_BAD_SPELLING (an expansion longer than width * max_spelling):
+ *                        such a pair reads nothing out of bounds, writes zeros and adds to nothing.
+ *   totals               NULL or int64 [16], ACCUMULATED: [0..7] for the character unit, [8..15] for the word unit:
+ *                        distance, reference length, hypothesis length, hits, substitutions, insertions, deletions,
+ *                        pairs.
+ *   gate                 NULL or one int32 on the device: when *gate != 0, totals and conf are left untouched (out is
+ *                        still written) — lets a caller discard a batch by a device-side fault word without reading it.
+ * Limits, decided from the widths and max_spelling (the longest spelling) alone: width * max_spelling <=
+ * LR_EDIT_MAX_CHARS per side, LR_EDIT_MAX_ALIGN_CHARS per side with the alignment, else LR_ERR_UNSUPPORTED before
+ * any launch.  K < 65535. */
+#define LR_EDIT_CHARS 0
+#define LR_EDIT_WORDS 1
+#define LR_EDIT_CHARS_ALIGN 2
+#define LR_EDIT_OUT_STRIDE 8
+#define LR_EDIT_MAX_CHARS 4096
+#define LR_EDIT_MAX_ALIGN_CHARS 2048
+#define LR_EDIT_BAD_ID (-1)
+#define LR_EDIT_BAD_LENGTH (-2)
+#define LR_EDIT_BAD_SPELLING (-3)
+
+/* Workspace lr_edit_distance needs; 0 for arguments it rejects (invalid or past the limits).  16 bytes, except for an
+ * alignment whose 2-bit-per-cell walk-back table does not fit beside the sequences in 64 KB of LDS: then
+ * B * align4(hyp_width * max_spelling * ceil(ref_width * max_spelling / 4)) bytes. */
+size_t lr_edit_workspace_bytes(int B, int hyp_width, int ref_width, int max_spelling, int mode);
+
+/* One launch, one pair per workgroup. */
+int lr_edit_distance(const int32_t* hyp, int64_t hyp_stride, const int32_t* hyp_lens, int64_t hyp_lens_stride,
+                     const int32_t* ref, int64_t ref_stride, const int32_t* ref_lens, int64_t ref_lens_stride,
+                     const int32_t* spell_off, const int32_t* spell_sym, int n_classes, int max_spelling,
+                     int space_sym, int mode, int32_t* out, int64_t* totals, int64_t* conf, int K,
+                     const int32_t* gate, void* workspace, size_t workspace_bytes, int B, int hyp_width,
+                     int ref_width, lr_stream_t stream);
+
 /* ---- A8 (BUILD-DEFINED, no reference symbol): 3-D conv frontend on bf16 MFMA -------------- */
 /* The reference has no conv frontend (src/models/lipreader/model.py:122,153-156 are comments, the
  * `ced` configs are empty); BASELINE.json's north_star asks for one ("im2col + MFMA GEMM for the 3D

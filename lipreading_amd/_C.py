@@ -126,6 +126,9 @@ SIGNATURES = {
     "lr_ctc_beam_lm_pack": (c_int, [P, c_size_t, c_int, P, P, P, P, c_int, c_int64, P, P, P, c_int]),
     "lr_ctc_beam_lm_decode": (c_int, [P, c_int64, c_int64, P, c_int, c_int, c_float, c_int, c_int, P, P, c_float,
                                        c_float, P, P, P, P, P, c_size_t, c_int, c_int, c_int, P]),
+    "lr_edit_workspace_bytes": (c_size_t, [c_int] * 5),
+    "lr_edit_distance": (c_int, [P, c_int64, P, c_int64, P, c_int64, P, c_int64, P, P, c_int, c_int, c_int, c_int,
+                                 P, P, P, c_int, P, P, c_size_t, c_int, c_int, c_int, P]),
     "lr_clip_to_ndhwc_bf16": (c_int, [P, c_int, P, c_int64, c_int, c_int, P]),
     "lr_conv3d_pack_weights": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "lr_conv3d_pack_weights_multi": (c_int, [c_int] + [P] * 9 + [P]),

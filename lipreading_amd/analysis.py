@@ -3,11 +3,15 @@
 The reference decodes one utterance at a time on the host, drawing each hypothesis's candidates with a multinomial.
 Here the whole batch goes through one encoder pass and one `CharDecodingStep.beam_search` call on the device, with
 the deterministic rule of lipreading_amd/csrc/lr_attn_beam.hip (top-K candidates; PAD and BOS never candidates).
-The strings keep the reference's format.  The reference's confusion-matrix plots are not ported.
+The strings keep the reference's format.  The reference's confusion matrix (analysis.py:132-153) is computed here
+from the decoded transcript's alignment on the device (confusion_matrix below); its plots are not ported.
 """
 import torch
 
 from .data import BOS
+
+# analysis.py:133-139: the 26 letters grouped by viseme (vowels and w / b p m / f v / alveolars / j / velars and x / h)
+VISEME_ORDER = list("aeiyouw" "bpm" "fv" "tdnszlr" "j" "kqcgx" "h")
 
 
 def encode_for_beam(encoder, frames, frame_lens, device, with_ctc=False):
@@ -64,3 +68,29 @@ def inference(encoder, decoding_step, frames, frame_lens, chars, char_lens, devi
   chars, char_lens = chars.cpu(), char_lens.cpu()
   gt = [''.join(idx2char[int(c)] for c in chars[i][:int(char_lens[i])]) for i in range(len(best))]
   return outputs, gt
+
+
+def confusion_matrix(encoder, data_loader, device, char2idx, decoder=None, class_names=None):
+  """Character confusion matrix of the CTC head's transcripts over `data_loader`: a numpy int64
+  (len(class_names), len(class_names)) array, rows = the label's character, columns = the decoded one, in the
+  reference's viseme order (VISEME_ORDER) by default.  decoder=None scores the greedy path, a BeamCTCDecoder its best
+  hypothesis.
+
+  This differs from the reference on purpose.  The reference (analysis.py:97-153) tabulates multinomial SAMPLES of
+  the attention decoder under teacher forcing, position by position; this tabulates the DECODED transcript aligned
+  to the label by the edit-distance walk back of lr_edit_distance (diagonal first, then a deletion,
+  then an insertion), so a dropped or extra character shifts nothing.  Insertions and deletions have no cell in
+  the returned cut; a class name outside the scorer's alphabet gets an all-zero row and column."""
+  from . import train as T
+  names = list(VISEME_ORDER if class_names is None else class_names)
+  _, scorer = T._device_score_run(encoder, data_loader, device, char2idx, decoder=decoder, units=('char',), align=True)
+  conf, symbols = scorer.confusion()
+  conf = conf.cpu().numpy()
+  at = {ch: i for i, ch in enumerate(symbols)}
+  import numpy as np
+  out = np.zeros((len(names), len(names)), dtype=np.int64)
+  for i, r in enumerate(names):
+    for j, h in enumerate(names):
+      if r in at and h in at:
+        out[i, j] = conf[at[r], at[h]]
+  return out

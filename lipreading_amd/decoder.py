@@ -58,6 +58,12 @@ class Decoder(object):
   def decode(self, probs, sizes=None):
     raise NotImplementedError
 
+  def scorer(self):
+    """An EditScorer over this decoder's labels: decode_ids' output -> CER / WER on the device, no strings
+    (lipreading_amd/scoring.py)."""
+    from .scoring import EditScorer
+    return EditScorer(self.labels)
+
 
 class BeamCTCDecoder(Decoder):
   """decoder.py:90-143 on lr_ctc_beam_decode.  `log_probs_input` is ctcdecode's later keyword: True when

@@ -51,6 +51,10 @@ DEFAULTS = dict(  # train.py:134-167
     # --prefetch=N > 0: the three loaders are loader.PrefetchLoader of depth N (batch k+1 is gathered into pinned
     # memory, uploaded and collated on a copy stream while step k runs); 0 = the plain BatchLoader
     prefetch=0,
+    # who scores the transcripts behind the edit-distance errors (greedy, --ctc_decoder=beam, --attn_decode=beam|joint):
+    # host (the Python loops of train.greedy_cer / ctc_cer / attention_cer) or device (train.device_scores: the ids
+    # never leave the GPU, lr_edit_distance scores them, one read per loader; the epoch summary then carries val_wer)
+    score="host",
 )
 
 
@@ -138,6 +142,8 @@ def parse_flags(argv, defaults=DEFAULTS):
     raise SystemExit("--attn_beam_width must be in [1, 32]")
   if int(out.get("attn_max_label_len", 100)) < 1:
     raise SystemExit("--attn_max_label_len must be positive")
+  if out.get("score") not in ("host", "device"):
+    raise SystemExit("--score must be host or device")
   if out["frontend"] != "none" or out["encoder"] != "rnn":
     # the build-defined regimes are encoder + CTC (BASELINE configs[1], [4]); no attention decoder behind them
     for name in ("enable_ctc", "ctc_only"):
@@ -226,8 +232,15 @@ def _cer(correct, count):
 
 
 def make_error_of(f, encoder, decoding_step, ctc_decoder, device, char2idx):
-  """The driver's error measure for a loader, by the flags `f`."""
+  """The driver's error measure for a loader, by the flags `f`.  With --score=device the edit-distance errors are
+  scored on the GPU (train.device_scores: the same floats) and `error_of.last_scores` holds the latest call's dict
+  (cer, wer, ...); the teacher-forced mismatch rate is not an edit distance and is untouched."""
   from . import train as T
+  on_device = f.get("score", "host") == "device"
+
+  def scored(loader, **how):
+    error_of.last_scores = T.device_scores(encoder, loader, device, char2idx, **how)
+    return error_of.last_scores["cer"]
 
   def error_of(loader):
     """The live loop's "CER" is the sampled-token mismatch rate of the attention decoder (train.py:287-288
@@ -235,6 +248,12 @@ def make_error_of(f, encoder, decoding_step, ctc_decoder, device, char2idx):
     (--attn_decode=joint: of the joint CTC/attention beam search's);
     without a decoder it is the greedy-decoded CER of the CTC head (decoder.py:64-73 on :182-197, as
     archive/train_model.py:351-357 composes them), or the beam-decoded one with --ctc_decoder=beam."""
+    if on_device and decoding_step is None:
+      return scored(loader, decoder=ctc_decoder)
+    if on_device and f["attn_decode"] in ("beam", "joint"):
+      return scored(loader, decoding_step=decoding_step, beam_width=f["attn_beam_width"],
+                    max_label_len=f["attn_max_label_len"],
+                    ctc_weight=f["attn_ctc_weight"] if f["attn_decode"] == "joint" else 0.0)
     if decoding_step is None:
       if ctc_decoder is not None:
         return T.ctc_cer(encoder, loader, device, char2idx, ctc_decoder)
@@ -247,6 +266,7 @@ def make_error_of(f, encoder, decoding_step, ctc_decoder, device, char2idx):
                              max_label_len=f["attn_max_label_len"], ctc_weight=f["attn_ctc_weight"])
     _, correct, count, _ = T.eval(encoder, decoding_step, loader, device, char2idx)
     return _cer(correct, count)
+  error_of.last_scores = None
   return error_of
 
 
@@ -353,7 +373,9 @@ def run(**flags):
                                  teacher_forcing_ratio=tfr, grad_norm=f["grad_norm"], graphs=graphs)
     print(f'\tAVG Decoder Loss: {dec_loss}')
     print(f'\tAVG CTC Loss: {ctc_loss}')
-    val_cer, train_cer = error_of(val_loader), error_of(train_loader)
+    val_cer = error_of(val_loader)
+    val_scores = error_of.last_scores   # (--score=device: the validation pass's dict, before the next pass replaces it)
+    train_cer = error_of(train_loader)
     encoder.save_best_model(val_cer, encoder_path)
     if not ctc_only:
       decoding_step.save_best_model(val_cer, decoder_path)
@@ -367,6 +389,9 @@ def run(**flags):
                         # batches that updated nothing (the reference's `continue`, train_better_model.py:49-50) and how
                         # many of them because a one-launch recurrence timed out
                         skipped_batches=stats.get("skipped", 0), recurrence_faults=stats.get("recurrence_faults", 0)))
+    if val_scores is not None:
+      history[-1]["val_wer"] = val_scores["wer"]
+      print(f'\tVal WER: {val_scores["wer"]}')
     if val_cer < best_val_cer:   # :339-341
       best_val_cer, best_idx = val_cer, epochs
     epochs += 1

@@ -741,3 +741,155 @@ def attention_cer(encoder, decoding_step, data_loader, device, char2idx, beam_wi
         dist += _edit_distance(hyp.replace(' ', ''), ref.replace(' ', ''))
         total += len(ref.replace(' ', ''))
   return dist / max(total, 1)
+
+
+# ---- scoring on the device (lipreading_amd/scoring.py) -------------------------------------------------
+# The three loops above copy the ids to the host every batch, join label strings and run decoder._edit_distance (a
+# pure-Python O(n m) loop) per utterance, with the GPU idle.  device_scores keeps the ids on the device: per batch
+# it enqueues encoder -> decode_ids / beam_search -> lr_edit_distance and reads nothing back.
+
+last_device_score_stats = None   # {"batches", "gated", "rescored"} of the latest device_scores call
+_SCORERS = {}                    # label tuple -> EditScorer (its tables are uploaded once per device)
+
+
+def _fault_gate(flag2):
+  """Exports the fault words into `flag2` on the stream and returns the int32 view whose first element is non-zero
+  iff a one-launch recurrence has timed out since the last roll — lr_edit_distance's `gate`; no host read."""
+  _C.check(_C.lib().lr_fault_export(None, flag2.data_ptr(), _C.stream_handle()), "lr_fault_export")
+  return flag2[1:]
+
+
+class _DeviceScoring(object):
+  """What a device_scores call carries from batch to batch."""
+
+  def __init__(self, encoder, device, char2idx, decoder, decoding_step, beam_width, max_label_len, ctc_weight, pre_beam,
+               units, align, n_batches):
+    from .decoder import GreedyDecoder, ctc_labels
+    from .scoring import EditScorer
+    self.encoder, self.device, self.decoding_step = encoder, torch.device(device), decoding_step
+    self.beam = dict(beam_width=beam_width, max_label_len=max_label_len)
+    self.joint = decoding_step is not None and ctc_weight > 0
+    self.ctc_weight, self.pre_beam = ctc_weight, pre_beam
+    self.units, self.align = tuple(units), bool(align)
+    inv = {v: k for k, v in char2idx.items()}
+    if decoding_step is None:
+      # CTC classes: character id + 1, blank at 0; the references are shifted the same way (as lr_ctc_prepare_i64 does)
+      labels, self.shift = ctc_labels(char2idx), 1
+      self.decoder = decoder if decoder is not None else GreedyDecoder(labels, blank_index=0)
+      if not hasattr(self.decoder, "decode_ids"):
+        raise TypeError("device scoring needs a decoder with decode_ids() (GreedyDecoder, BeamCTCDecoder)")
+      if list(self.decoder.labels) != labels:
+        raise ValueError("the decoder's labels are not ctc_labels(char2idx)")
+    else:
+      labels, self.shift, self.decoder = [inv[i] for i in range(len(inv))], 0, None
+    key = tuple(labels)
+    self.scorer = _SCORERS.get(key)
+    if self.scorer is None:
+      self.scorer = _SCORERS[key] = EditScorer(labels)
+    self.scorer._state(self.device)   # the tables' upload (once per device) happens here, not in the first batch
+    self.flag2 = torch.zeros(2, dtype=torch.int32, device=self.device)
+    self.gated = torch.zeros(max(n_batches, 1), dtype=torch.int32, device=self.device)
+
+  def hypotheses(self, frames, frame_lens, frame_lens_d):
+    """One encoder pass and one search, all enqueued: (ids (B, W) int32 view, lens (B,) int32 view)."""
+    max_len = int(frame_lens.max()) if not frame_lens.is_cuda else None
+    if self.decoding_step is None:
+      log_probs, _, _ = self.encoder(frames, frame_lens_d, max_len=max_len)
+      got = self.decoder.decode_ids(log_probs, frame_lens_d)
+      if len(got) == 3:
+        return got[0], got[2]
+      return got[0][:, 0], got[2][:, 0]       # the best hypothesis of (B, W, T) / (B, W)
+    from .analysis import encode_for_beam
+    enc_out = encode_for_beam(self.encoder, frames, frame_lens, self.device, with_ctc=self.joint)
+    hidden, lens_d, state = enc_out[:3]
+    joint = dict(ctc_log_probs=enc_out[3], ctc_weight=self.ctc_weight, pre_beam=self.pre_beam) if self.joint else {}
+    ids, lens, _ = self.decoding_step.beam_search(hidden, lens_d, state, **self.beam, **joint)
+    return ids[:, 0], lens[:, 0]
+
+
+def _device_batch(ctx, k, frames, frame_lens, frame_lens_d, chars_d, char_lens_d, gated=True):
+  """Batch k, after its upload: everything here is an enqueue.  With gated=False (the re-score pass) the fault word
+  is not consulted."""
+  _roll_faults(ctx.device)
+  hyp, hyp_lens = ctx.hypotheses(frames, frame_lens, frame_lens_d)
+  # BOS and EOS stripped as the host loops do: chars[b, 1:char_lens[b] - 1]
+  ref = (chars_d + ctx.shift if ctx.shift else chars_d).to(torch.int32)[:, 1:]
+  ref_lens = (char_lens_d - 2).clamp_(min=0).to(torch.int32)
+  gate = None
+  if gated:
+    gate = _fault_gate(ctx.flag2)
+    ctx.gated[k:k + 1].copy_(gate[:1])
+  for unit in ctx.units:
+    ctx.scorer.score(hyp, hyp_lens, ref, ref_lens, unit=unit, align=ctx.align and unit == 'char', gate=gate)
+
+
+def _device_score_run(encoder, data_loader, device, char2idx, decoder=None, decoding_step=None, beam_width=10,
+                      max_label_len=100, ctc_weight=0.0, pre_beam=None, units=('char', 'word'), align=False):
+  global last_device_score_stats
+  device = torch.device(device)
+  if device.type != "cuda":
+    raise _C.LipReadingHipError("device scoring runs on the MI355X only (no CPU fallback)")
+  if decoding_step is not None and ctc_weight > 0:
+    from .analysis import need_ctc_head
+    need_ctc_head(encoder)
+  ctx = _DeviceScoring(encoder, device, char2idx, decoder, decoding_step, beam_width, max_label_len, ctc_weight, pre_beam,
+                       units, align, len(data_loader))
+  ctx.scorer.reset()
+  encoder.eval()
+  if decoding_step is not None:
+    decoding_step.eval()
+
+  def upload(batch):
+    frames, frame_lens, chars, char_lens = batch
+    return (frames.to(device), frame_lens, frame_lens.to(device), chars.to(device), char_lens.to(device))
+
+  with torch.no_grad():
+    for k, batch in enumerate(data_loader):
+      _device_batch(ctx, k, *upload(batch))
+    # the one read: the totals and which batches the fault word kept out of them
+    res, gated = ctx.scorer.read(extra=ctx.gated)
+    again = set(i for i, g in enumerate(gated.tolist()) if g != 0)
+    rescored = 0
+    if again:
+      # a one-launch recurrence timed out in those batches (see greedy_cer): they were left out of the totals; encode
+      # just them again on the per-step kernels and score them — the host loops' immediate re-decode, deferred
+      inner = getattr(encoder, "encoder", encoder)   # (PixelLipReader wraps the VideoEncoder)
+      saved = getattr(inner, "recurrence", None)
+      if saved is not None:
+        inner.recurrence = 'f32'
+      try:
+        for k, batch in enumerate(data_loader):
+          if k in again:
+            _device_batch(ctx, k, *upload(batch), gated=False)
+            rescored += 1
+      finally:
+        if saved is not None:
+          inner.recurrence = saved
+      res = ctx.scorer.result()
+  last_device_score_stats = {"batches": len(data_loader), "gated": len(again), "rescored": rescored}
+  return res, ctx.scorer
+
+
+def device_scores(encoder, data_loader, device, char2idx, decoder=None, decoding_step=None, beam_width=10,
+                  max_label_len=100, ctc_weight=0.0, pre_beam=None, units=('char', 'word'), align=False):
+  """greedy_cer / ctc_cer / attention_cer's evaluation with the scoring on the device: the dict of
+  scoring.EditScorer.result() — cer, wer, distance, ref_len, pairs, ... (hits / sub / ins / dele with align=True).
+
+  decoder=None, decoding_step=None: the CTC head's greedy path (greedy_cer).  decoder = a BeamCTCDecoder over
+  ctc_labels(char2idx): its best hypothesis (ctc_cer).  decoding_step: the attention decoder's beam search
+  (attention_cer; beam_width, max_label_len, and ctc_weight > 0 with pre_beam for the joint search).
+
+  Per batch nothing is read back.  A recurrence time-out is handled as in the host loops, but without their per-batch
+  read: the device-side fault word gates the batch out of the totals (lr_edit_distance's `gate`), a device vector
+  records which batches were gated, and after the last batch one read covers the totals and that vector; only if some
+  batch was gated is the loader walked again and just those batches re-encoded with recurrence='f32' and scored."""
+  return _device_score_run(encoder, data_loader, device, char2idx, decoder, decoding_step, beam_width, max_label_len,
+                           ctc_weight, pre_beam, units, align)[0]
+
+
+def device_cer(encoder, data_loader, device, char2idx, decoder=None, decoding_step=None, beam_width=10,
+               max_label_len=100, ctc_weight=0.0, pre_beam=None):
+  """The same float as greedy_cer (no decoder), ctc_cer (`decoder`) or attention_cer (`decoding_step`): sum of
+  space-free edit distances / sum of space-free reference lengths, scored on the device (device_scores)."""
+  return device_scores(encoder, data_loader, device, char2idx, decoder, decoding_step, beam_width, max_label_len,
+                       ctc_weight, pre_beam, units=('char',))["cer"]
