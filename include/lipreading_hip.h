@@ -173,6 +173,28 @@ int lr_lip_crop_collate_u8(const void* frames, const float* lmk, const int64_t* 
                            void* out, int B, int t_max, int H, int W, int S, int npts, int lo, int hi, float margin,
                            lr_stream_t stream);
 
+/* lr_lip_crop_collate_u8 with training-time clip augmentation applied inside the same launch.  The host draws
+ * (lipreading_amd/augment.py), the kernel applies: no random number is made on the device.
+ *   clip_aug f32 [B][4] = (dx, dy, zoom, flip) per CLIP;  tmap int32 [sum(lens)], indexed like the frames:
+ *   tmap[offsets[b]+t] = source frame of output frame t within sample b, or < 0 for a masked frame.
+ *   out[b,t] = 0                                   for t >= min(lens[b], t_max) or tmap[offsets[b]+t] < 0
+ *            = crop'(row n = offsets[b] + min(tmap[offsets[b]+t], lens[b]-1))   otherwise
+ * (a map value past the sample is clamped: no row of another sample is ever read).  crop' starts from the centre
+ * (cx, cy) and side of lr_lip_crop_u8's window of row n:  side' = max(side*zoom, 2),
+ * left = fmaf(dx, side, cx) - side'/2, top likewise with dy, scale = side'/S, and output pixel (oy, ox) is
+ * lr_lip_crop_u8's pixel (oy, flip != 0 ? S-1-ox : ox) of that window: the shift is in units of the un-zoomed side,
+ * the flip mirrors output columns.  The identity record (0,0,1,0) with tmap[t] = t gives lr_lip_crop_collate_u8's
+ * bytes.  Source coordinates are clamped to the frame, so no value of the record reads outside it; keeping the
+ * values in range is the host's job.  EVERY byte of out is written. */
+int lr_lip_crop_collate_aug_u8(const void* frames, const float* lmk, const int64_t* offsets, const int32_t* lens,
+                               const float* clip_aug, const int32_t* tmap, void* out, int B, int t_max, int H, int W,
+                               int S, int npts, int lo, int hi, float margin, lr_stream_t stream);
+
+/* lr_collate_pad_f32 with the same frame map (landmark regime: temporal jitter and time masks only):
+ *   out[b,t,:] = t < lens[b] ? (m < 0 ? 0 : packed[offsets[b] + min(m, lens[b]-1), :]) : 0,  m = tmap[offsets[b]+t] */
+int lr_collate_pad_aug_f32(const float* packed, const int64_t* offsets, const int32_t* lens, const int32_t* tmap,
+                           float* out, int B, int t_max, int feat, lr_stream_t stream);
+
 /* ---- dense fp32 contraction (MFMA f32 16x16x4 / 32x32x2), used by A3 ------------------- */
 
 /* C[M,N] = alpha * op(A)[M,K] * op(B)[K,N] + beta * C + bias[N]   (row-major, fp32)

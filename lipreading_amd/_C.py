@@ -30,6 +30,8 @@ SIGNATURES = {
     "lr_lmk_landmarks": (c_int, [P, P, P, c_double, P, P, P, P, c_int, c_int, c_int, P]),
     "lr_lip_crop_u8": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P]),
     "lr_lip_crop_collate_u8": (c_int, [P, P, P, P, P] + [c_int] * 8 + [c_float, P]),
+    "lr_lip_crop_collate_aug_u8": (c_int, [P, P, P, P, P, P, P] + [c_int] * 8 + [c_float, P]),
+    "lr_collate_pad_aug_f32": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P]),
     "lr_sgemm_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "lr_sgemm": (c_int, [c_int, c_int, c_int, c_int, c_int, c_float, P, c_int, P, c_int, c_float,
                           P, c_int, P, c_int, c_int, P, c_size_t, P]),

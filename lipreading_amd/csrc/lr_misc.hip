@@ -1023,6 +1023,214 @@ extern "C" int lr_lip_crop_collate_u8(const void* frames, const float* lmk, cons
   return lr_launch_status();
 }
 
+// Training-time clip augmentation inside the collate launch (lr_lip_crop_collate_aug_u8).  The host draws, the kernel
+// applies: clip_aug[b] = (dx, dy, zoom, flip) moves, scales and mirrors the crop window of every frame of sample b, and
+// tmap[offsets[b] + t] names the source frame (within sample b) of output frame t, or < 0 for a masked (all-zero) frame.
+// The window starts from lip_crop_box's centre and side of the SOURCE row: the shift is in units of the un-zoomed
+// side, the zoom scales the side about the shifted centre, the flip mirrors output columns.  With the identity record
+// (0, 0, 1, 0) every expression rounds to lip_crop_box's: fmaf(0, side, c) = c and max(side * 1, 2) = side.  Grid, LDS
+// slots, barrier and stores are lip_crop_collate_kernel's.  Three things differ, each measured:
+//  * A mirrored frame is computed group by group exactly as the plain one — the same source columns per lane,
+//    ascending across the wave (gathering them in descending order was 40 % slower) — and each group of V pixels is
+//    stored at its mirrored place with its bytes reversed (v_perm with a uniform selector: one loop for both).
+//  * The extent is taken by the first wave together, one landmark per lane, instead of by one lane point after point:
+//    min and max do not depend on the order.
+//  * A workgroup has one or two frames to do, so a frame's prologue (lens, offsets -> map -> landmarks: three dependent
+//    loads) is on the critical path.  The NEXT frame's prologue loads are issued before the pixels of this one, and
+//    only their reduction is left for afterwards (one landmark per lane is held meanwhile; with more than 64
+//    landmarks in [lo, hi) they are loaded when the frame is started).
+// The 4-pixel variant (S % 16 != 0, off the bench shape) sits at the 64 VGPRs of 8 waves per SIMD already: it keeps the
+// one-lane extent (taken when the frame is started) and mirrors by reversing the source columns, which holds it there.
+namespace {
+// The landmarks' bounding box in two steps, by threads 0 .. LANES-1 together (LANES = 64: the first wave, every lane
+// of it; or 1).  lip_crop_partial: each lane's share of the points (the loads); lip_crop_finish: the reduction over the
+// lanes, then twice the centre (sx2 = x0 + x1, sy2 = y0 + y1) and the window's side (lip_crop_box's), in every lane.
+template <int LANES>
+__device__ __forceinline__ void lip_crop_partial(const float* __restrict__ L, int lo, int hi, float& x0, float& x1,
+                                                 float& y0, float& y1) {
+  x0 = x1 = L[lo * 3];
+  y0 = y1 = L[lo * 3 + 1];
+  for (int p = lo + (LANES > 1 ? (int)threadIdx.x : 1); p < hi; p += LANES) {
+    const float x = L[p * 3], y = L[p * 3 + 1];
+    x0 = fminf(x0, x); x1 = fmaxf(x1, x); y0 = fminf(y0, y); y1 = fmaxf(y1, y);
+  }
+}
+
+template <int LANES>
+__device__ __forceinline__ void lip_crop_finish(float x0, float x1, float y0, float y1, float margin, float& sx2,
+                                                float& sy2, float& side) {
+#pragma unroll
+  for (int off = LANES / 2; off > 0; off >>= 1) {
+    x0 = fminf(x0, __shfl_xor(x0, off, 64)); x1 = fmaxf(x1, __shfl_xor(x1, off, 64));
+    y0 = fminf(y0, __shfl_xor(y0, off, 64)); y1 = fmaxf(y1, __shfl_xor(y1, off, 64));
+  }
+  side = fmaxf(x1 - x0, y1 - y0) * (1.f + 2.f * margin);
+  side = fmaxf(side, 2.f);
+  sx2 = x0 + x1;
+  sy2 = y0 + y1;
+}
+
+// the bytes of a group in reverse order when flip is set (sel: v_perm's byte selector, identity or reversed)
+__device__ __forceinline__ unsigned char crop_vec_mirror(unsigned char v, bool, uint32_t) { return v; }
+__device__ __forceinline__ uint32_t crop_vec_mirror(uint32_t v, bool, uint32_t sel) {
+  return __builtin_amdgcn_perm(v, v, sel);
+}
+__device__ __forceinline__ uint4 crop_vec_mirror(uint4 v, bool flip, uint32_t sel) {
+  const uint32_t a = __builtin_amdgcn_perm(v.x, v.x, sel), b = __builtin_amdgcn_perm(v.y, v.y, sel);
+  const uint32_t c = __builtin_amdgcn_perm(v.z, v.z, sel), d = __builtin_amdgcn_perm(v.w, v.w, sel);
+  return make_uint4(flip ? d : a, flip ? c : b, flip ? b : c, flip ? a : d);
+}
+template <int V>
+__global__ __launch_bounds__(256) void lip_augment_collate_kernel(
+    const unsigned char* __restrict__ frames, const float* __restrict__ lmk, const int64_t* __restrict__ offsets,
+    const int32_t* __restrict__ lens, const float* __restrict__ clip_aug, const int32_t* __restrict__ tmap,
+    unsigned char* __restrict__ out, int B, int t_max, int H, int W, int S, int npts, int lo, int hi, float margin) {
+  typedef typename CropVec<V>::T vec_t;
+  constexpr bool kWide = V != 4;             // (see above)
+  constexpr int kLanes = kWide ? 64 : 1;
+  __shared__ float box[2][4];
+  const int per_row = S / V;                 // S % V == 0 (the launcher picks V)
+  const int items = 3 * S * per_row;         // V-pixel groups of one frame
+  const int pairs = B * t_max;
+  int p = blockIdx.x;                        // (sample, frame) pairs p, p + gridDim.x, ...: uniform per workgroup
+  if (p >= pairs) return;
+  // the pair whose prologue loads are in flight: its map value (< 0: a frame of zeros), source row and record, and in
+  // the first wave each lane's landmark (x0, y0)
+  int m;
+  int64_t n;
+  float dx, dy, zoom, flipf;
+  float x0 = 0.f, x1 = 0.f, y0 = 0.f, y1 = 0.f;
+  auto fetch = [&](int q) {
+    const int b = q / t_max, t = q - b * t_max;
+    const int rows_b = lens[b];
+    const int len = min(rows_b, t_max);      // lens[b] > t_max is the caller's error; never write outside out
+    const int64_t first = offsets[b];
+    const float* A = clip_aug + (int64_t)b * 4;
+    dx = A[0]; dy = A[1]; zoom = A[2]; flipf = A[3];
+    m = t < len ? tmap[first + t] : -1;
+    n = first + min(max(m, 0), rows_b - 1);  // whatever the map holds, the row is one of sample b's
+    if (kWide && hi - lo <= kLanes && m >= 0 && threadIdx.x < kLanes) {   // one point per lane (spare lanes: the last)
+      const float* Lq = lmk + n * npts * 3 + (lo + min((int)threadIdx.x, hi - lo - 1)) * 3;
+      x0 = Lq[0];
+      y0 = Lq[1];
+    }
+  };
+  fetch(p);
+  int parity = 0;
+  for (;;) {
+    const int m_now = m;
+    const bool flip = flipf != 0.f;
+    const unsigned char* F = frames + n * 3 * H * W;
+    vec_t* O = reinterpret_cast<vec_t*>(out + (int64_t)p * 3 * S * S);
+    float left = 0.f, top = 0.f, scale = 0.f;
+    if (m_now >= 0) {                        // uniform: the barrier is safe
+      float* bx = box[parity];
+      parity ^= 1;
+      if (threadIdx.x < kLanes) {
+        if (kWide && hi - lo <= kLanes) {    // prefetched
+          x1 = x0;
+          y1 = y0;
+        } else {
+          lip_crop_partial<kLanes>(lmk + n * npts * 3, lo, hi, x0, x1, y0, y1);
+        }
+        float sx2, sy2, side;
+        lip_crop_finish<kLanes>(x0, x1, y0, y1, margin, sx2, sy2, side);
+        if (threadIdx.x == 0) {
+          const float side_z = fmaxf(side * zoom, 2.f);
+          bx[0] = fmaf(dx, side, 0.5f * sx2) - 0.5f * side_z;   // left
+          bx[1] = fmaf(dy, side, 0.5f * sy2) - 0.5f * side_z;   // top
+          bx[2] = side_z / (float)S;                            // source pixels per output pixel
+        }
+      }
+      __syncthreads();
+      left = bx[0]; top = bx[1]; scale = bx[2];
+    }
+    const int p_next = p + gridDim.x;
+    if (p_next < pairs) fetch(p_next);       // in flight while this frame's pixels are made
+    if (m_now < 0) {                         // padding or a masked frame
+      vec_t zero;
+      __builtin_memset(&zero, 0, sizeof(zero));
+      for (int i = threadIdx.x; i < items; i += blockDim.x) O[i] = zero;
+    } else {
+      // mirrored, output column S - 1 - x shows source column x: group g is stored at group per_row - 1 - g with its
+      // bytes reversed (4-pixel variant: the group at S - V - ox is computed in place of the one at ox)
+      const int mirror = flip ? 1 : 0, src0 = flip && !kWide ? S - V : 0, dir = flip && !kWide ? -1 : 1;
+      const uint32_t sel = flip ? 0x00010203u : 0x03020100u;
+      for (int i = threadIdx.x; i < items; i += blockDim.x) {
+        const int c = i / (S * per_row), r = i - c * S * per_row;
+        const int oy = r / per_row, g = r - oy * per_row, ox = g * V;
+        const unsigned char* P = F + (int64_t)c * H * W;
+        union { vec_t v; unsigned char px[V]; } u;
+        const int src = kWide ? ox : src0 + dir * ox;
+#pragma unroll
+        for (int k = 0; k < V; ++k) u.px[k] = lip_crop_pixel(P, H, W, oy, src + k, left, top, scale);
+        O[kWide ? i + mirror * (per_row - 1 - 2 * g) : i] = crop_vec_mirror(u.v, flip, sel);
+      }
+    }
+    if (p_next >= pairs) break;
+    p = p_next;
+  }
+}
+
+// collate_pad_kernel with the source row of every frame taken from tmap (< 0: a masked, all-zero row)
+__global__ void collate_pad_aug_kernel(const float* __restrict__ packed, const int64_t* __restrict__ offsets,
+                                       const int32_t* __restrict__ lens, const int32_t* __restrict__ tmap,
+                                       float* __restrict__ out, int B, int t_max, int feat) {
+  const int64_t total = (int64_t)B * t_max * feat;
+  const int64_t row_elems = (int64_t)t_max * feat;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int b = (int)(i / row_elems);
+    const int64_t r = i - (int64_t)b * row_elems;
+    const int t = (int)(r / feat);
+    const int f = (int)(r - (int64_t)t * feat);
+    const int len = lens[b];
+    float v = 0.f;
+    if (t < len) {
+      const int m = tmap[offsets[b] + t];
+      if (m >= 0) v = packed[(offsets[b] + min(m, len - 1)) * feat + f];
+    }
+    out[i] = v;
+  }
+}
+}  // namespace
+
+extern "C" int lr_lip_crop_collate_aug_u8(const void* frames, const float* lmk, const int64_t* offsets,
+                                          const int32_t* lens, const float* clip_aug, const int32_t* tmap, void* out,
+                                          int B, int t_max, int H, int W, int S, int npts, int lo, int hi, float margin,
+                                          lr_stream_t stream) {
+  LR_CHECK_ARG(frames && lmk && offsets && lens && clip_aug && tmap && out);
+  LR_CHECK_ARG(B > 0 && t_max > 0 && H > 0 && W > 0 && S > 0);
+  LR_CHECK_ARG(npts > 0 && lo >= 0 && hi > lo && hi <= npts && margin >= 0.f);
+  LR_CHECK_ARG((int64_t)B * t_max <= INT32_MAX && (int64_t)S * S <= INT32_MAX / 3);
+  const int pairs = B * t_max;
+  const dim3 grid(pairs < 2048 ? pairs : 2048);   // 256 CUs x 8 workgroups; the rest by the grid stride
+  const unsigned char* f = (const unsigned char*)frames;
+  unsigned char* o = (unsigned char*)out;
+  const bool aligned = (reinterpret_cast<uintptr_t>(out) & 15) == 0;   // as lr_lip_crop_collate_u8
+  if (aligned && S % 16 == 0) {
+    LR_LAUNCH(lip_augment_collate_kernel<16>, grid, dim3(256), 0, stream, f, lmk, offsets, lens, clip_aug, tmap, o, B,
+              t_max, H, W, S, npts, lo, hi, margin);
+  } else if (aligned && S % 4 == 0) {
+    LR_LAUNCH(lip_augment_collate_kernel<4>, grid, dim3(256), 0, stream, f, lmk, offsets, lens, clip_aug, tmap, o, B,
+              t_max, H, W, S, npts, lo, hi, margin);
+  } else {
+    LR_LAUNCH(lip_augment_collate_kernel<1>, grid, dim3(256), 0, stream, f, lmk, offsets, lens, clip_aug, tmap, o, B,
+              t_max, H, W, S, npts, lo, hi, margin);
+  }
+  return lr_launch_status();
+}
+
+extern "C" int lr_collate_pad_aug_f32(const float* packed, const int64_t* offsets, const int32_t* lens,
+                                      const int32_t* tmap, float* out, int B, int t_max, int feat, lr_stream_t stream) {
+  LR_CHECK_ARG(packed && offsets && lens && tmap && out);
+  LR_CHECK_ARG(B > 0 && t_max > 0 && feat > 0);
+  const int64_t total = (int64_t)B * t_max * feat;
+  LR_LAUNCH(collate_pad_aug_kernel, dim3(grid_for(total, 256)), dim3(256), 0, stream, packed, offsets, lens, tmap, out, B,
+            t_max, feat);
+  return lr_launch_status();
+}
+
 // ---- instrumentation ----------------------------------------------------------------------------
 namespace {
 constexpr int kProfRing = 1024;

@@ -254,11 +254,17 @@ class BatchLoader(object):
     return iterate_batches(self.dataset, self.batch_size, self.collate_fn)
 
 
-def make_loader(dataset, batch_size, collate_fn, prefetch=0, **loader_args):
+def make_loader(dataset, batch_size, collate_fn, prefetch=0, augment=None, **loader_args):
   """prefetch=0: the plain BatchLoader over `collate_fn`.  prefetch=N > 0: a loader.PrefetchLoader of depth N that
-  yields the same batches (loader_args: device, pixels, size, margin, workers — what `collate_fn` was made with)."""
+  yields the same batches (loader_args: device, pixels, size, margin, workers — what `collate_fn` was made with).
+  augment: an augment.AugmentSpec for a TRAINING loader; it is applied inside the prefetch loader's collate launch,
+  so it needs prefetch > 0."""
+  if augment is not None and not prefetch:
+    raise ValueError("augment=%r needs the prefetch loader: pass prefetch=N > 0 (got prefetch=%r)" % (augment, prefetch))
   if not prefetch:
     return BatchLoader(dataset, batch_size, collate_fn)
+  if augment is not None:
+    loader_args["augment"] = augment
   from .loader import PrefetchLoader
   return PrefetchLoader(dataset, batch_size, depth=int(prefetch), **loader_args)
 

@@ -51,6 +51,10 @@ DEFAULTS = dict(  # train.py:134-167
     # --prefetch=N > 0: the three loaders are loader.PrefetchLoader of depth N (batch k+1 is gathered into pinned
     # memory, uploaded and collated on a copy stream while step k runs); 0 = the plain BatchLoader
     prefetch=0,
+    # --augment=flip=0.5,shift=0.08,zoom=0.1,tjitter=0.05,tmask=2x10: training-time clip augmentation of the TRAIN
+    # loader only (augment.AugmentSpec; applied inside the prefetch loader's collate launch, so it needs --prefetch);
+    # the per-epoch Train CER is scored on clean clips.  --augment_seed: the stream of draws (None = --seed)
+    augment="", augment_seed=None,
     # who scores the transcripts behind the edit-distance errors (greedy, --ctc_decoder=beam, --attn_decode=beam|joint):
     # host (the Python loops of train.greedy_cer / ctc_cer / attention_cer) or device (train.device_scores: the ids
     # never leave the GPU, lr_edit_distance scores them, one read per loader; the epoch summary then carries val_wer)
@@ -149,7 +153,19 @@ def parse_flags(argv, defaults=DEFAULTS):
     for name in ("enable_ctc", "ctc_only"):
       if name not in explicit:
         out[name] = True
+  augment_spec(out)
   return out
+
+
+def augment_spec(f):
+  """The AugmentSpec of the flags `f` (None without --augment).  ValueError for a policy that does not parse and for
+  --augment without --prefetch: the augmentation runs inside the prefetch loader's collate launch."""
+  from .augment import AugmentSpec
+  seed = f.get("augment_seed")
+  spec = AugmentSpec.parse(f.get("augment") or "", seed=f.get("seed", 0) if seed is None else seed)
+  if spec is not None and not f.get("prefetch"):
+    raise ValueError("--augment=%s needs --prefetch=N > 0 (got --prefetch=%r)" % (f["augment"], f.get("prefetch")))
+  return spec
 
 
 def init_models(char2idx, num_layers, frame_dim, hidden_size, char_dim, enable_ctc, rnn_type,
@@ -278,6 +294,7 @@ def run(**flags):
   from .optim import FlatParameters, FusedAdam
   f = dict(DEFAULTS)
   f.update(flags)
+  augment = augment_spec(f)
   if f["frontend"] != "none" or f["encoder"] != "rnn":
     # the build-defined regimes are encoder + CTC with greedy CER (parse_flags sets the same for flag files)
     f["enable_ctc"], f["ctc_only"] = flags.get("enable_ctc", True), flags.get("ctc_only", True)
@@ -301,8 +318,12 @@ def run(**flags):
     collate = make_pixel_collate_fn(device, size=f["crop_size"])
   else:
     collate = make_collate_fn(device)   # padded on the GPU (lr_collate_pad_f32); lengths stay on the host
+  # only the train loader is augmented; validation and test clips are served as they are
   train_loader, val_loader, test_loader = (make_loader(d, f["batch_size"], collate, prefetch=f["prefetch"], device=device,
-                                                       pixels=pixels, size=f["crop_size"]) for d in sets)
+                                                       pixels=pixels, size=f["crop_size"],
+                                                       augment=augment if d is sets[0] else None) for d in sets)
+  if augment is not None:
+    print("Augmenting the training clips: %s (seed %d)" % (augment, augment.seed))
   print("Initializing model")
   ctc_only = bool(f["ctc_only"])
   if pixels or f["encoder"] == "transformer":
@@ -375,7 +396,7 @@ def run(**flags):
     print(f'\tAVG CTC Loss: {ctc_loss}')
     val_cer = error_of(val_loader)
     val_scores = error_of.last_scores   # (--score=device: the validation pass's dict, before the next pass replaces it)
-    train_cer = error_of(train_loader)
+    train_cer = error_of(train_loader.plain() if augment is not None else train_loader)   # on clean clips
     encoder.save_best_model(val_cer, encoder_path)
     if not ctc_only:
       decoding_step.save_best_model(val_cer, decoder_path)

@@ -11,6 +11,11 @@ stream and off the step's critical path:
                 own stream, collates it there in ONE launch (lr_lip_crop_collate_u8 / lr_collate_pad_f32) and records
                 an event; the consumer's stream waits on that event (no host synchronisation).
 
+With `augment=AugmentSpec(...)` (augment.py) a worker also draws the batch's augmentation records into the slot — they
+ride the same upload — and the one launch is lr_lip_crop_collate_aug_u8 / lr_collate_pad_aug_f32, which applies them.
+Lengths, labels, batch order and batch shapes are those of the un-augmented loader; `plain()` iterates the same
+dataset, ring and stream with augmentation off (DESIGN.md "Clip augmentation").
+
 Rules (DESIGN.md "Prefetching loader"):
   * no HIP call on a worker thread — workers touch host memory only; every enqueue, event record and event query is
     issued by the iterating thread between two steps, never while a step is being captured into a hipGraph;
@@ -34,6 +39,9 @@ from . import _C
 MAX_WORKERS = 8         # a GPU job may use 16 CPUs; never sized by os.cpu_count()
 WAIT_SECONDS = 120.0    # upper bound of every blocking wait on the host
 _ALIGN = 256            # every region of a slot starts on a 256-byte boundary (vector loads, int64 offsets)
+DRAW_AHEAD = 16         # batches whose augmentation records ONE call of AugmentSpec.draw covers: a draw is some fifty
+                        # numpy calls, each of which hands the GIL over and takes it back from the thread that launches
+                        # the step, so the workers draw for many batches at once (DESIGN.md "Clip augmentation")
 
 
 def _align(n):
@@ -51,6 +59,7 @@ class PackedBatch(object):
 
   pixels:    frames u8 [rows][3][H][W] | lmk f32 [rows][68][3] | offsets i64 [B] | lens i32 [B]
   landmarks: rows f32 [rows][feat]                             | offsets i64 [B] | lens i32 [B]
+  augmented: ... | aug f32 [B][4] (pixels only) | tmap i32 [rows]     (AugmentSpec.draw's records)
   frame_lens / chars / char_lens: int64 numpy arrays, the values the plain collate functions return."""
 
   def __init__(self):
@@ -58,6 +67,8 @@ class PackedBatch(object):
     self.pixels = False
     self.B = self.t_max = self.rows = self.nbytes = 0
     self.frames_off = self.lmk_off = self.offsets_off = self.lens_off = 0
+    self.augmented = False
+    self.aug_off = self.tmap_off = 0
     self.H = self.W = self.feat = 0
     self.tail = ()
     self.frame_lens = self.chars = self.char_lens = None
@@ -76,6 +87,12 @@ class PackedBatch(object):
       return buf[self.offsets_off:self.offsets_off + B * 8].view(np.int64)
     if name == "lens":
       return buf[self.lens_off:self.lens_off + B * 4].view(np.int32)
+    if name == "aug":
+      assert self.augmented and self.pixels
+      return buf[self.aug_off:self.aug_off + B * 16].view(np.float32).reshape(B, 4)
+    if name == "tmap":
+      assert self.augmented
+      return buf[self.tmap_off:self.tmap_off + rows * 4].view(np.int32)
     raise KeyError(name)
 
 
@@ -89,9 +106,16 @@ def _pad_chars(captions):
   return chars, char_lens
 
 
-def pack_batch(samples, pixels, buf):
+def _aug_bytes(B, rows, pixels):
+  """Bytes of the augmentation regions behind `lens`."""
+  return (_align(B * 16) if pixels else 0) + _align(rows * 4)
+
+
+def pack_batch(samples, pixels, buf, augment=None, pass_no=0, indices=None, records=None):
   """Gather one batch into `buf` (1-D uint8 numpy array, a slot of the ring).  Host memory only.  Raises what the
-  plain collate raises for a malformed batch (AssertionError), before anything is written."""
+  plain collate raises for a malformed batch (AssertionError), before anything is written.  augment: an AugmentSpec,
+  whose draw for (pass_no, indices = the samples' dataset indices) follows `lens`; None: today's bytes.  records: that
+  draw's (clip, tmap) if the caller has it already (a record depends on seed, pass, index and length only)."""
   pb = PackedBatch()
   pb.pixels = bool(pixels)
   assert len(samples) > 0
@@ -124,6 +148,12 @@ def pack_batch(samples, pixels, buf):
   pb.B, pb.rows, pb.t_max = len(samples), rows, int(lens.max())
   pb.lens_off = pb.offsets_off + _align(pb.B * 8)
   pb.nbytes = pb.lens_off + _align(pb.B * 4)
+  if augment is not None:
+    assert indices is not None and len(indices) == len(samples), "an augmented batch needs its dataset indices"
+    pb.augmented = True
+    pb.aug_off = pb.nbytes
+    pb.tmap_off = pb.aug_off + (_align(pb.B * 16) if pixels else 0)
+    pb.nbytes = pb.aug_off + _aug_bytes(pb.B, rows, pixels)
   assert pb.nbytes <= buf.shape[0], "slot of %d bytes is too small for a batch of %d" % (buf.shape[0], pb.nbytes)
   offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
   frames = pb.region(buf, "frames")
@@ -137,27 +167,36 @@ def pack_batch(samples, pixels, buf):
       np.copyto(frames[lo:lo + n], pix[b].reshape(n, pb.feat), casting="unsafe")
   pb.region(buf, "offsets")[:] = offsets
   pb.region(buf, "lens")[:] = lens
+  if augment is not None:
+    clip, tmap = augment.draw(pass_no, indices, lens) if records is None else records
+    assert clip.shape == (pb.B, 4) and tmap.shape == (rows,)
+    if pixels:
+      pb.region(buf, "aug")[...] = clip       # (the landmark regime has no window to move: the map alone applies)
+    pb.region(buf, "tmap")[:] = tmap
   pb.frame_lens = lens
   pb.chars, pb.char_lens = _pad_chars(captions)
   return pb
 
 
-def _slot_bytes(dataset, plan, pixels):
+def _slot_bytes(dataset, plan, pixels, augment=False):
   """Bytes of the largest batch (the dataset is in memory): sizes only, the shape checks belong to pack_batch."""
   most = _ALIGN
   for lo, hi in plan:
-    a = b = 0
+    a = b = rows = 0
     for i in range(lo, hi):
       try:
         x = dataset[i][0]
         if pixels:
           a += int(np.asarray(x[0]).nbytes)
           b += int(np.asarray(x[1]).size) * 4
+          rows += len(x[0])
         else:
           a += int(np.asarray(x).size) * 4
+          rows += len(x)
       except Exception:     # a malformed sample: its batch raises when it is packed
         continue
-    most = max(most, _align(a) + _align(b) + _align((hi - lo) * 8) + _align((hi - lo) * 4))
+    most = max(most, _align(a) + _align(b) + _align((hi - lo) * 8) + _align((hi - lo) * 4) +
+               (_aug_bytes(hi - lo, rows, pixels) if augment else 0))
   return most
 
 
@@ -173,8 +212,11 @@ class _HostEpoch(object):
   """The workers of one pass over the dataset.  submit(slot) hands the next batch of the plan to a worker together
   with the slot it may fill; get(k) returns batch k's PackedBatch or re-raises its worker's exception."""
 
-  def __init__(self, stage):
+  def __init__(self, stage, augment=None, pass_no=0):
     self._dataset, self._plan, self._pixels = stage.dataset, stage.plan, stage.pixels
+    self._augment, self._pass_no = augment, int(pass_no)
+    self._draw_lock = threading.Lock()
+    self._drawn = {}                 # chunk of DRAW_AHEAD batches -> (first index, row starts, clip, tmap)
     self._bufs = stage._np
     self._tasks = queue.Queue()
     self._cv = threading.Condition()
@@ -194,13 +236,40 @@ class _HostEpoch(object):
       k, slot = task
       try:
         lo, hi = self._plan[k]
-        res = pack_batch([self._dataset[i] for i in range(lo, hi)], self._pixels, self._bufs[slot])
+        res = pack_batch([self._dataset[i] for i in range(lo, hi)], self._pixels, self._bufs[slot],
+                         augment=self._augment, pass_no=self._pass_no, indices=range(lo, hi),
+                         records=self._records(k) if self._augment is not None else None)
         res.index, res.slot = k, slot
       except BaseException as exc:   # handed to the consumer, which raises it at batch k
         res = exc
       with self._cv:
         self._results[k] = res
         self._cv.notify_all()
+
+  def _records(self, k):
+    """Batch k's (clip, tmap), cut out of ONE draw for its chunk of DRAW_AHEAD batches (made by the worker that needs
+    it first).  None if the chunk cannot be drawn (a malformed sample somewhere in it): the batch then draws for
+    itself, and the malformed batch raises when IT is packed."""
+    c = k // DRAW_AHEAD
+    with self._draw_lock:
+      got = self._drawn.get(c, False)
+      if got is False:
+        try:
+          b0, b1 = c * DRAW_AHEAD, min((c + 1) * DRAW_AHEAD, len(self._plan))
+          lo, hi = self._plan[b0][0], self._plan[b1 - 1][1]
+          lens = np.array([len(self._dataset[i][0][0]) if self._pixels else len(self._dataset[i][0])
+                           for i in range(lo, hi)], dtype=np.int64)
+          clip, tmap = self._augment.draw(self._pass_no, range(lo, hi), lens)
+          got = (lo, np.concatenate([[0], np.cumsum(lens)]), clip, tmap)
+        except Exception:
+          got = None
+        self._drawn = {c2: v for c2, v in self._drawn.items() if c2 >= c - 1}   # workers are a few batches apart
+        self._drawn[c] = got
+    if got is None:
+      return None
+    first, starts, clip, tmap = got
+    lo, hi = self._plan[k]
+    return clip[lo - first:hi - first], tmap[starts[lo - first]:starts[hi - first]]
 
   def submit(self, slot):
     if self._stop.is_set() or self.submitted >= len(self._plan):
@@ -243,14 +312,18 @@ class HostStage(object):
 
   alloc(nbytes) -> 1-D uint8 CPU tensor: pinned for the GPU path, plain `torch.empty` for host-only use.  Iterating
   the stage yields the PackedBatch of every batch in order; a batch's slot goes back to the workers when the consumer
-  asks for the next batch (PrefetchLoader drives the same workers but returns a slot only after its upload)."""
+  asks for the next batch (PrefetchLoader drives the same workers but returns a slot only after its upload).
 
-  def __init__(self, dataset, batch_size, pixels=False, depth=2, workers=2, alloc=None):
+  augment: an AugmentSpec; every augmented pass draws with the next pass number (0, 1, ...; `set_pass` pins it), so two
+  passes differ and a resumed run can repeat one.  A pass takes its number when it starts, completed or abandoned."""
+
+  def __init__(self, dataset, batch_size, pixels=False, depth=2, workers=2, alloc=None, augment=None):
     assert depth >= 1 and workers >= 1
     self.dataset, self.batch_size, self.pixels = dataset, int(batch_size), bool(pixels)
     self.depth, self.workers = int(depth), min(int(workers), MAX_WORKERS)
+    self.augment, self.pass_no = augment, 0
     self.plan = batch_plan(len(dataset), self.batch_size)
-    self.slot_bytes = _slot_bytes(dataset, self.plan, self.pixels)
+    self.slot_bytes = _slot_bytes(dataset, self.plan, self.pixels, augment is not None)
     alloc = alloc or _plain_alloc
     self.slots = [alloc(self.slot_bytes) for _ in range(self.depth + 1)]
     assert all(s.dtype == torch.uint8 and s.dim() == 1 and s.numel() >= self.slot_bytes and not s.is_cuda
@@ -261,10 +334,19 @@ class HostStage(object):
   def __len__(self):
     return len(self.plan)
 
-  def open(self):
-    """Start the workers of a new pass (the previous pass, if it was abandoned, is shut down first)."""
+  def set_pass(self, n):
+    """The number the next augmented pass draws with (resumption, tests)."""
+    self.pass_no = int(n)
+
+  def open(self, augmented=True):
+    """Start the workers of a new pass (the previous pass, if it was abandoned, is shut down first).  augmented=False:
+    a pass with augmentation off, which leaves the pass number alone."""
     self.close()
-    self._epoch = _HostEpoch(self)
+    if augmented and self.augment is not None:
+      self._epoch = _HostEpoch(self, self.augment, self.pass_no)
+      self.pass_no += 1
+    else:
+      self._epoch = _HostEpoch(self)
     return self._epoch
 
   def close(self):
@@ -316,7 +398,8 @@ class PrefetchLoader(object):
   Yields (frames f32 (B,Tmax,68,3) or clips u8 (B,Tmax,3,size,size) on `device`, frame_lens i64, chars i64 (B,Cmax)
   PAD=0, char_lens i64), the last three on the host (pinned).  Re-iterable; one pass at a time."""
 
-  def __init__(self, dataset, batch_size, device, pixels=False, size=96, margin=0.3, depth=2, workers=2, alloc=None):
+  def __init__(self, dataset, batch_size, device, pixels=False, size=96, margin=0.3, depth=2, workers=2, alloc=None,
+               augment=None):
     dev = torch.device(device)
     if dev.type != "cuda":
       raise _C.LipReadingHipError("collation runs on the MI355X only (no CPU fallback)")
@@ -326,8 +409,9 @@ class PrefetchLoader(object):
     self.pixels, self.size, self.margin = bool(pixels), int(size), float(margin)
     self.depth = int(depth)
     self._pinned = alloc is None
+    self.augment = augment
     self.host = HostStage(dataset, batch_size, pixels=pixels, depth=depth, workers=workers,
-                          alloc=alloc or _pinned_alloc)
+                          alloc=alloc or _pinned_alloc, augment=augment)
     with torch.cuda.device(dev):
       self._copy = torch.cuda.Stream(dev)
       # ragged device staging, one per slot: rewritten only by a later upload on the same stream
@@ -342,6 +426,18 @@ class PrefetchLoader(object):
   def close(self):
     self.host.close()
 
+  @property
+  def pass_no(self):
+    return self.host.pass_no
+
+  def set_pass(self, n):
+    self.host.set_pass(n)
+
+  def plain(self):
+    """An iterable over the same dataset, ring and stream with augmentation off (scoring the training set on clean
+    clips).  One pass at a time, as for the loader itself; it does not advance the pass number."""
+    return _PlainPasses(self)
+
   def _enqueue(self, pb):
     """Upload slot -> staging, collate into a fresh padded batch, record the event.  Iterating thread only."""
     L = _C.lib()
@@ -350,15 +446,26 @@ class PrefetchLoader(object):
       stage = self._stage[slot]
       stage[:pb.nbytes].copy_(self.host.slots[slot][:pb.nbytes], non_blocking=True)    # the batch's ONE upload
       base, s = stage.data_ptr(), self._copy.cuda_stream
-      if self.pixels:
+      if self.pixels and pb.augmented:
+        out = torch.empty((pb.B, pb.t_max, 3, self.size, self.size), dtype=torch.uint8, device=dev)
+        _C.check(L.lr_lip_crop_collate_aug_u8(base + pb.frames_off, base + pb.lmk_off, base + pb.offsets_off,
+                                              base + pb.lens_off, base + pb.aug_off, base + pb.tmap_off, out.data_ptr(),
+                                              pb.B, pb.t_max, pb.H, pb.W, self.size, 68, self._mouth.start,
+                                              self._mouth.stop, self.margin, s), "lr_lip_crop_collate_aug_u8")
+      elif self.pixels:
         out = torch.empty((pb.B, pb.t_max, 3, self.size, self.size), dtype=torch.uint8, device=dev)
         _C.check(L.lr_lip_crop_collate_u8(base + pb.frames_off, base + pb.lmk_off, base + pb.offsets_off,
                                           base + pb.lens_off, out.data_ptr(), pb.B, pb.t_max, pb.H, pb.W, self.size,
                                           68, self._mouth.start, self._mouth.stop, self.margin, s), "lr_lip_crop_collate_u8")
       else:
         out = torch.empty((pb.B, pb.t_max, pb.feat), dtype=torch.float32, device=dev)
-        _C.check(L.lr_collate_pad_f32(base + pb.frames_off, base + pb.offsets_off, base + pb.lens_off,
-                                      out.data_ptr(), pb.B, pb.t_max, pb.feat, s), "lr_collate_pad_f32")
+        if pb.augmented:
+          _C.check(L.lr_collate_pad_aug_f32(base + pb.frames_off, base + pb.offsets_off, base + pb.lens_off,
+                                            base + pb.tmap_off, out.data_ptr(), pb.B, pb.t_max, pb.feat, s),
+                   "lr_collate_pad_aug_f32")
+        else:
+          _C.check(L.lr_collate_pad_f32(base + pb.frames_off, base + pb.offsets_off, base + pb.lens_off,
+                                        out.data_ptr(), pb.B, pb.t_max, pb.feat, s), "lr_collate_pad_f32")
         out = out.reshape((pb.B, pb.t_max) + pb.tail)
       event = torch.cuda.Event()
       event.record(self._copy)
@@ -386,7 +493,10 @@ class PrefetchLoader(object):
       time.sleep(1e-4)
 
   def __iter__(self):
-    ep = self.host.open()
+    return self._passes(True)
+
+  def _passes(self, augmented):
+    ep = self.host.open(augmented)
     try:
       nb = len(self.host.plan)
       busy = list(range(len(self._pending)))     # slots not with a worker (an abandoned pass may have left events)
@@ -427,3 +537,16 @@ class PrefetchLoader(object):
       self.close()
     except Exception:
       pass
+
+
+class _PlainPasses(object):
+  """PrefetchLoader.plain(): the loader's batches with augmentation off."""
+
+  def __init__(self, loader):
+    self.loader = loader
+
+  def __len__(self):
+    return len(self.loader)
+
+  def __iter__(self):
+    return self.loader._passes(False)

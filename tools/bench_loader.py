@@ -4,6 +4,8 @@
 
   python tools/bench_loader.py                 # regimes R and X, one JSON document on stdout and profiles/loader_loop.json
   python tools/bench_loader.py --regimes X --batches 6 --repeats 5 --no-trace
+  python tools/bench_loader.py --augment flip=0.5,shift=0.08,zoom=0.1,tjitter=0.05,tmask=2x10
+                                               # the augmented loader beside the prefetched one: profiles/augment_loop.json
 
   R  landmarks -> BiGRU-256 + CTC, B = 32, hipGraphs on (as the driver has them)
   X  u8 frames 96x96 + landmarks -> mouth crop -> PixelLipReader (conv3d frontend, 2 x BiGRU-256) + CTC, B = 32, eager
@@ -38,6 +40,7 @@ if ROOT not in sys.path:
 import numpy as np  # noqa: E402
 
 T_FRAMES, N_LMK, VOCAB, LABEL_LEN = 75, 68, 64, 30
+SAME_BYTES_POLICY = "flip=0.5,shift=0.08,tjitter=0.05"     # augments, yet gathers and stores what the plain launch does
 
 
 def synthetic_dataset(regime, n_samples, hw=96, t_frames=T_FRAMES, seed=123456, distinct=8):
@@ -84,9 +87,10 @@ def _summary(ms):
 
 
 def time_arms(regime, dev, batch=32, n_batches=8, repeats=5, size=96, hw=96, depth=2, workers=2, hidden=256,
-              t_frames=T_FRAMES, log=None):
+              t_frames=T_FRAMES, log=None, augment=None):
   """ms per step of train()'s loop over the three arms.  Returns {"plain": {...}, "prefetch": {...}, "resident": {...}}
-  with median / min / max of ms_per_step over `repeats` epochs of `n_batches` steps."""
+  with median / min / max of ms_per_step over `repeats` epochs of `n_batches` steps.  augment: an AugmentSpec adds an
+  "augmented" arm beside "prefetch" — the same loader with the spec, every epoch a new pass of draws."""
   import torch
   from lipreading_amd import train as T
   from lipreading_amd.data import make_collate_fn, make_pixel_collate_fn
@@ -101,6 +105,10 @@ def time_arms(regime, dev, batch=32, n_batches=8, repeats=5, size=96, hw=96, dep
   prefetch = PrefetchLoader(ds, batch, dev, pixels=pixels, size=size, depth=depth, workers=workers)
   resident = [collate(ds[:batch])] * n_batches
   arms = (("plain", plain), ("prefetch", prefetch), ("resident", resident))
+  augmented = None
+  if augment is not None:
+    augmented = PrefetchLoader(ds, batch, dev, pixels=pixels, size=size, depth=depth, workers=workers, augment=augment)
+    arms = arms[:2] + (("augmented", augmented),) + arms[2:]
 
   host_s = {}
 
@@ -143,6 +151,8 @@ def time_arms(regime, dev, batch=32, n_batches=8, repeats=5, size=96, hw=96, dep
     if log:
       log("  %s repeat %d: " % (regime, r) + ", ".join("%s %.3f" % (n, ms[n][-1]) for n, _ in arms))
   prefetch.close()
+  if augmented is not None:
+    augmented.close()
   out = {name: _summary(v) for name, v in ms.items()}
   out["steps_per_epoch"], out["batch"], out["graphs"] = n_batches, batch, bool(graphs.enabled)
   out["timed_seconds_per_epoch"] = {n: statistics.median(v) * n_batches / 1e3 for n, v in ms.items()}
@@ -165,8 +175,21 @@ def _event_ms(fn, stream, reps):
   return out
 
 
-def time_kernel(dev, batch=32, size=96, hw=96, t_frames=T_FRAMES, reps=10):
-  """lr_lip_crop_collate_u8 beside the summed B per-sample lr_lip_crop_u8 launches it replaces (device events)."""
+def time_draw(spec, batch=32, t_frames=T_FRAMES, reps=50):
+  """Host milliseconds per batch inside AugmentSpec.draw (what a worker thread spends under the GIL)."""
+  lens = np.full(batch, t_frames)
+  spec.draw(0, np.arange(batch), lens)
+  ms = []
+  for r in range(reps):
+    t0 = time.perf_counter()
+    spec.draw(r, np.arange(batch) + r * batch, lens)
+    ms.append((time.perf_counter() - t0) * 1e3)
+  return dict(_summary(ms), batch=batch, frames=t_frames, policy=str(spec))
+
+
+def time_kernel(dev, batch=32, size=96, hw=96, t_frames=T_FRAMES, reps=10, augment=None):
+  """lr_lip_crop_collate_u8 beside the summed B per-sample lr_lip_crop_u8 launches it replaces (device events).
+  augment: an AugmentSpec adds lr_lip_crop_collate_aug_u8 on that spec's draw as a third alternated arm."""
   import torch
   from lipreading_amd import _C
   from lipreading_amd.landmarks import _mouth
@@ -195,14 +218,32 @@ def time_kernel(dev, batch=32, size=96, hw=96, t_frames=T_FRAMES, reps=10):
                                 t_frames, hw, hw, size, N_LMK, _mouth.start, _mouth.stop, 0.3, stream.cuda_stream),
                "lr_lip_crop_u8")
 
+  if augment is not None:
+    clip, tmap = augment.draw(0, np.arange(batch), np.full(batch, t_frames))
+    clip_d, tmap_d = torch.from_numpy(clip).to(dev), torch.from_numpy(tmap).to(dev)
+
+  def one_launch_augmented():
+    _C.check(L.lr_lip_crop_collate_aug_u8(frames.data_ptr(), lmk.data_ptr(), offsets.data_ptr(), lens.data_ptr(),
+                                          clip_d.data_ptr(), tmap_d.data_ptr(), out.data_ptr(), batch, t_frames, hw, hw,
+                                          size, N_LMK, _mouth.start, _mouth.stop, 0.3, stream.cuda_stream),
+             "lr_lip_crop_collate_aug_u8")
+
   _event_ms(one_launch, stream, 3), _event_ms(per_sample, stream, 3)
-  a, b = [], []
+  if augment is not None:
+    _event_ms(one_launch_augmented, stream, 3)
+  a, b, c = [], [], []
   for _ in range(reps):                       # alternated
     a += _event_ms(one_launch, stream, 1)
     b += _event_ms(per_sample, stream, 1)
+    if augment is not None:
+      c += _event_ms(one_launch_augmented, stream, 1)
   nbytes = out.numel() + frames.numel()
   res = {"collate_one_launch_ms": _summary(a), "per_sample_launches_ms": _summary(b),
          "bytes_written_plus_read": int(nbytes), "shape": [batch, t_frames, 3, size, size], "source_hw": [hw, hw]}
+  if augment is not None:
+    res["augmented_one_launch_ms"] = _summary(c)
+    res["policy"] = str(augment)
+    res["masked_frames"] = int((tmap < 0).sum())
   res["collate_GBps"] = nbytes / (res["collate_one_launch_ms"]["median"] * 1e-3) / 1e9
   return res
 
@@ -354,8 +395,13 @@ def parse_args(argv=None):
   ap.add_argument("--no-trace", action="store_true", help="skip the rocprofv3 run")
   ap.add_argument("--trace-timeout", type=int, default=240)
   ap.add_argument("--trace-child", action="store_true", help=argparse.SUPPRESS)
-  ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "loader_loop.json"))
+  ap.add_argument("--augment", default="", help="an augmentation policy (augment.AugmentSpec.parse): time the augmented "
+                  "loader and kernel beside the prefetched ones and write profiles/augment_loop.json")
+  ap.add_argument("--out", default=None, help="default: profiles/loader_loop.json (profiles/augment_loop.json with "
+                  "--augment)")
   args = ap.parse_args(argv)
+  if args.out is None:
+    args.out = os.path.join(ROOT, "profiles", "augment_loop.json" if args.augment else "loader_loop.json")
   args.regimes = [r for r in args.regimes.upper().split(",") if r]
   assert set(args.regimes) <= {"R", "X"} and args.regimes, "--regimes takes R and/or X"
   assert args.repeats >= 5, "at least five repeats per arm"
@@ -378,12 +424,23 @@ def main(argv=None):
   log = lambda s: print(s, file=sys.stderr, flush=True)
   doc = {"tool": "tools/bench_loader.py", "device": torch.cuda.get_device_name(0), "depth": args.depth,
          "workers": args.workers, "repeats": args.repeats, "regimes": {}}
+  from lipreading_amd.augment import AugmentSpec
+  spec = AugmentSpec.parse(args.augment, seed=123456)
   for regime in args.regimes:
     n_batches = args.batches or (2560 if regime == "R" else 256)
     log("regime %s: %d steps per epoch" % (regime, n_batches))
     doc["regimes"][regime] = time_arms(regime, dev, batch=args.batch, n_batches=n_batches, repeats=args.repeats,
-                                       size=args.size, depth=args.depth, workers=args.workers, log=log)
-  if "X" in args.regimes:
+                                       size=args.size, depth=args.depth, workers=args.workers, log=log, augment=spec)
+  if spec is not None:
+    # the kernel under the policy and under one that touches the same bytes per frame as the plain launch (no zoom,
+    # no masks), each beside its own alternated plain arm; and the host's share, the draws
+    doc["policy"] = str(spec)
+    doc["draw_host_ms_per_batch"] = time_draw(spec, batch=args.batch)
+    if "X" in args.regimes:
+      doc["kernel"] = {"policy": time_kernel(dev, batch=args.batch, size=args.size, augment=spec),
+                       "same_bytes": time_kernel(dev, batch=args.batch, size=args.size,
+                                                 augment=AugmentSpec.parse(SAME_BYTES_POLICY, seed=123456))}
+  elif "X" in args.regimes:
     doc["kernel"] = time_kernel(dev, batch=args.batch, size=args.size)
     slot = args.batch * T_FRAMES * (3 * 96 * 96 + N_LMK * 3 * 4)
     doc["upload"] = time_upload(dev, slot)
