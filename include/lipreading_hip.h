@@ -871,6 +871,56 @@ int lr_edit_distance(const int32_t* hyp, int64_t hyp_stride, const int32_t* hyp_
                      const int32_t* gate, void* workspace, size_t workspace_bytes, int B, int hyp_width,
                      int ref_width, lr_stream_t stream);
 
+/* ---- A6e (BUILD-DEFINED, no reference symbol): CTC forced alignment — when is each character and word spoken ---- */
+/* The reference has no aligner; the specification is this build's (lipreading_amd/csrc/lr_align.hip),
+ * the yardstick a NumPy restatement kept with the tests.  Per sample b, n = sizes[b] frames of fp32 log-probabilities
+ * and a target y[0..L) of class ids (L = target_lens[b], blank excluded).  States s = 0..2L, even = blank, odd s =
+ * y[(s-1)/2].  v[0][0] = lp[0][blank], v[0][1] = lp[0][y[0]], -inf elsewhere; for t >= 1 v[t][s] = best +
+ * lp[t][cls(s)], best over v[t-1][s] (code 0), v[t-1][s-1] (code 1, s >= 1), v[t-1][s-2] (code 2; s odd, s >= 3,
+ * cls(s) != cls(s-2)) IN THIS ORDER, a later candidate replacing an earlier one only if strictly greater.  All fp32:
+ * one add per cell and comparisons.  End state 0 if L == 0, else 2L if v[n-1][2L] > v[n-1][2L-1], else 2L-1; total =
+ * v[n-1][end]; the path is read backwards through the codes.
+ *   log_probs    element (b,t,c) at log_probs[b*stride_b + t*stride_t + c]; NaN is unspecified
+ *   sizes        [B] int32 or NULL (= T);  targets [B][target_stride] int32, ids past target_lens[b] are never read
+ *   class_roles  [C] int32 (0 transparent, 1 word character, 2 space, as lr_ctc_beam_lm_decode) or NULL: no word
+ *                outputs, the word pointers and n_words may then be NULL
+ *   frame_token  [B][T]: the token index a frame belongs to, -1 on blank frames and for t >= n
+ *   tok_start / tok_end / tok_logp  [B][target_stride]: token i holds the contiguous frames [start, end); logp = the fp32
+ *                sum of lp[t][y[i]] over them in ascending t
+ *   word_first / word_count / word_start / word_end / word_logp  [B][target_stride]: a word is a maximal run of
+ *                consecutive role-1 tokens: its first token, token count, tok_start[first], tok_end[last], and the fp32
+ *                sum of its tokens' tok_logp in order.  n_words [B].
+ *   total        [B] fp32;  status [B]: 0, LR_ALIGN_INFEASIBLE (total = -inf: no path spells the target in n frames),
+ *                LR_ALIGN_BAD_ID (an id inside its length outside [0, C) or equal to blank), LR_ALIGN_BAD_LENGTH
+ *                (sizes[b] outside [1, T] or target_lens[b] outside [0, target_stride]).
+ * Entries past L / n_words are -1 (integers) and 0 (floats).  A sample with a non-zero status reads nothing out of
+ * bounds and writes -1 / 0 everywhere, total = -inf and n_words = 0.
+ * Limits, from the arguments alone: target_stride <= max_label_len <= 256, T <= LR_ALIGN_MAX_T, else
+ * LR_ERR_UNSUPPORTED before any launch.  One launch, one sample per workgroup. */
+#define LR_ALIGN_MAX_T 2048
+#define LR_ALIGN_INFEASIBLE 1
+#define LR_ALIGN_BAD_ID (-1)
+#define LR_ALIGN_BAD_LENGTH (-2)
+
+/* Workspace lr_ctc_align needs; 0 for arguments it rejects.  16 bytes while the 2-bit back-pointer table
+ * (ceil(T / 16) dwords per state, states rounded up to 64) fits in LDS beside the sample's rows; B times that table
+ * otherwise. */
+size_t lr_ctc_align_workspace_bytes(int B, int T, int C, int max_label_len);
+
+/* What lr_ctc_align will launch for these sizes, decided on the host (no device call): plan [LR_ALIGN_PLAN_WORDS]
+ * int32 on the HOST = {1 for the one-wave kernel / 0 for the multi-wave one, threads per workgroup, 1 if the sample's
+ * rows are staged into LDS / 0 if they are read from global memory, 1 if the back-pointer table lies in LDS / 0 if in
+ * the workspace, dynamic LDS bytes}.  Same status as lr_ctc_align would give for the sizes. */
+#define LR_ALIGN_PLAN_WORDS 5
+int lr_ctc_align_plan(int B, int T, int C, int max_label_len, int32_t* plan);
+
+int lr_ctc_align(const float* log_probs, int64_t stride_b, int64_t stride_t, const int32_t* sizes,
+                 const int32_t* targets, int target_stride, const int32_t* target_lens, const int32_t* class_roles,
+                 int blank, int32_t* frame_token, int32_t* tok_start, int32_t* tok_end, float* tok_logp,
+                 int32_t* word_first, int32_t* word_count, int32_t* word_start, int32_t* word_end, float* word_logp,
+                 int32_t* n_words, float* total, int32_t* status, void* workspace, size_t workspace_bytes, int B, int T,
+                 int C, int max_label_len, lr_stream_t stream);
+
 /* ---- A8 (BUILD-DEFINED, no reference symbol): 3-D conv frontend on bf16 MFMA -------------- */
 /* The reference has no conv frontend (src/models/lipreader/model.py:122,153-156 are comments, the
  * `ced` configs are empty); BASELINE.json's north_star asks for one ("im2col + MFMA GEMM for the 3D

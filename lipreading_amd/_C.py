@@ -131,6 +131,10 @@ SIGNATURES = {
     "lr_edit_workspace_bytes": (c_size_t, [c_int] * 5),
     "lr_edit_distance": (c_int, [P, c_int64, P, c_int64, P, c_int64, P, c_int64, P, P, c_int, c_int, c_int, c_int,
                                  P, P, P, c_int, P, P, c_size_t, c_int, c_int, c_int, P]),
+    "lr_ctc_align_workspace_bytes": (c_size_t, [c_int] * 4),
+    "lr_ctc_align_plan": (c_int, [c_int] * 4 + [P]),
+    "lr_ctc_align": (c_int, [P, c_int64, c_int64, P, P, c_int, P, P, c_int] + [P] * 12 + [P, c_size_t] + [c_int] * 4 +
+                     [P]),
     "lr_clip_to_ndhwc_bf16": (c_int, [P, c_int, P, c_int64, c_int, c_int, P]),
     "lr_conv3d_pack_weights": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "lr_conv3d_pack_weights_multi": (c_int, [c_int] + [P] * 9 + [P]),

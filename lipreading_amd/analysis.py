@@ -94,3 +94,17 @@ def confusion_matrix(encoder, data_loader, device, char2idx, decoder=None, class
       if r in at and h in at:
         out[i, j] = conf[at[r], at[h]]
   return out
+
+
+def word_timings(encoder, data_loader, device, char2idx, fps=29.97):
+  """Per utterance of `data_loader`, in its order: [(word, start_seconds, end_seconds, mean log-probability per
+  frame)] from the forced alignment of the caption against the encoder's CTC head (train.align_loader, DESIGN.md
+  §19); None for an utterance that could not be aligned (a clip too short to spell its caption)."""
+  from . import train as T
+  out = []
+  for rec in T.align_loader(encoder, data_loader, device, char2idx, fps=fps):
+    if rec["status"] != 0:
+      out.append(None)
+    else:
+      out.append([(w, s / fps, e / fps, lp / max(e - s, 1)) for w, s, e, lp in rec["words"]])
+  return out

@@ -59,6 +59,10 @@ DEFAULTS = dict(  # train.py:134-167
     # host (the Python loops of train.greedy_cer / ctc_cer / attention_cer) or device (train.device_scores: the ids
     # never leave the GPU, lr_edit_distance scores them, one read per loader; the epoch summary then carries val_wer)
     score="host",
+    # --align=PATH ('' = off): after the last epoch, the forced alignment of every validation caption against the CTC
+    # head as it then stands (train.align_loader: lr_ctc_align) — one JSON object per line: utterance index, status,
+    # total, words and characters with their frame and second spans.  Needs a CTC head.
+    align="",
 )
 
 
@@ -154,6 +158,7 @@ def parse_flags(argv, defaults=DEFAULTS):
       if name not in explicit:
         out[name] = True
   augment_spec(out)
+  align_check(out)
   return out
 
 
@@ -166,6 +171,31 @@ def augment_spec(f):
   if spec is not None and not f.get("prefetch"):
     raise ValueError("--augment=%s needs --prefetch=N > 0 (got --prefetch=%r)" % (f["augment"], f.get("prefetch")))
   return spec
+
+
+def align_check(f):
+  """ValueError for --align without a CTC head (neither --enable_ctc nor a regime that is encoder + CTC)."""
+  if f.get("align") and not f.get("enable_ctc"):
+    raise ValueError("--align=%s needs a CTC head: --enable_ctc=True (or a CTC-only regime)" % f["align"])
+
+
+def write_alignments(path, encoder, loader, device, char2idx, fps=29.97):
+  """train.align_loader over `loader` as JSON lines in `path`: index, status, total, frames, and for words and chars
+  text, start / end (frames), start_s / end_s (seconds) and logp.  Returns dict(path, utterances, infeasible)."""
+  import json
+  from . import train as T
+
+  def spans(items):
+    return [dict(text=t, start=s, end=e, start_s=s / fps, end_s=e / fps, logp=lp) for t, s, e, lp in items]
+
+  n = infeasible = 0
+  with open(path, "w") as out:
+    for rec in T.align_loader(encoder, loader, device, char2idx, fps=fps):
+      out.write(json.dumps(dict(index=rec["index"], status=rec["status"], total=rec["total"], frames=rec["frames"],
+                                words=spans(rec["words"]), chars=spans(rec["chars"]))) + "\n")
+      n += 1
+      infeasible += rec["status"] == 1
+  return dict(path=path, utterances=n, infeasible=int(infeasible))
 
 
 def init_models(char2idx, num_layers, frame_dim, hidden_size, char_dim, enable_ctc, rnn_type,
@@ -298,6 +328,7 @@ def run(**flags):
   if f["frontend"] != "none" or f["encoder"] != "rnn":
     # the build-defined regimes are encoder + CTC with greedy CER (parse_flags sets the same for flag files)
     f["enable_ctc"], f["ctc_only"] = flags.get("enable_ctc", True), flags.get("ctc_only", True)
+  align_check(f)
   torch.manual_seed(f["seed"])
   rand = np.random.RandomState(seed=f["seed"])
   assert torch.cuda.is_available(), "the driver runs the HIP path: an MI355X is required (no CPU fallback)"
@@ -416,9 +447,14 @@ def run(**flags):
     if val_cer < best_val_cer:   # :339-341
       best_val_cer, best_idx = val_cer, epochs
     epochs += 1
-  return dict(history=history, weights_dir=weights_dir, seconds=time.time() - t0, epochs=epochs,
-              graph_captures=graphs.captures, graph_replays=graphs.replays, encoder=encoder,
-              decoding_step=decoding_step, char2idx=char2idx, loaders=(train_loader, val_loader, test_loader))
+  out = dict(history=history, weights_dir=weights_dir, seconds=time.time() - t0, epochs=epochs,
+             graph_captures=graphs.captures, graph_replays=graphs.replays, encoder=encoder,
+             decoding_step=decoding_step, char2idx=char2idx, loaders=(train_loader, val_loader, test_loader))
+  if f["align"]:
+    out["align"] = write_alignments(f["align"], encoder, val_loader, device, char2idx)
+    print("Aligned %(utterances)d validation utterances (%(infeasible)d too short for their caption): %(path)s"
+          % out["align"])
+  return out
 
 
 def main(argv=None):

@@ -893,3 +893,53 @@ def device_cer(encoder, data_loader, device, char2idx, decoder=None, decoding_st
   space-free edit distances / sum of space-free reference lengths, scored on the device (device_scores)."""
   return device_scores(encoder, data_loader, device, char2idx, decoder, decoding_step, beam_width, max_label_len,
                        ctc_weight, pre_beam, units=('char',))["cer"]
+
+
+# ---- forced alignment over a loader (lipreading_amd/align.py, DESIGN.md §19) -----------------------------------------
+
+def align_loader(encoder, data_loader, device, char2idx, fps=29.97):
+  """When is each character and word of every caption spoken, by the encoder's CTC head: a generator of one record per
+  utterance, in the loader's order — align.CTCAligner.records' dict (status, total, chars, words; frames as ints)
+  plus `index` (the running utterance number) and `frames` (the clip's length).
+
+  Per batch: the encoder, then one lr_ctc_align launch against the TRAINING targets — ctc.prepare_ctc_inputs' labels,
+  i.e. chars[:, 1:] with '<EOS>', which the head was trained to emit ('<EOS>' gets a span but belongs to no word) —
+  and one read.  The fault words are rolled and read as in greedy_cer: a batch whose one-launch recurrence timed out
+  is encoded again with recurrence='f32' before it is aligned."""
+  from .align import CTCAligner
+  from .analysis import need_ctc_head
+  from .decoder import ctc_labels
+  device = torch.device(device)
+  if device.type != "cuda":
+    raise _C.LipReadingHipError("forced alignment runs on the MI355X only (no CPU fallback)")
+  need_ctc_head(encoder)
+  aligner = CTCAligner(ctc_labels(char2idx), blank_index=0, fps=fps)
+  encoder.eval()
+  flag2 = torch.zeros(2, dtype=torch.int32, device=device)
+  index = 0
+  with torch.no_grad():
+    for frames, frame_lens, chars, char_lens in data_loader:
+      max_len = int(frame_lens.max()) if not frame_lens.is_cuda else None
+      _roll_faults(device)
+      frames_d, lens_d = frames.to(device), frame_lens.to(device)
+      labels_p1, lens32, label_lens32 = prepare_ctc_inputs(chars.to(device), lens_d, char_lens.to(device))
+
+      def aligned():
+        log_probs = encoder(frames_d, lens_d, max_len=max_len)[0]
+        return aligner.records(aligner.align_ids(log_probs, lens32, labels_p1, label_lens32), labels_p1, label_lens32)
+
+      recs = aligned()
+      # (records() has just synchronised: reading the flag costs no wait of its own)
+      if not bool(_fault_keep(flag2)):
+        inner = getattr(encoder, "encoder", encoder)   # (PixelLipReader wraps the VideoEncoder)
+        if hasattr(inner, "recurrence"):
+          saved, inner.recurrence = inner.recurrence, 'f32'
+          try:
+            recs = aligned()
+          finally:
+            inner.recurrence = saved
+      n = frame_lens.tolist()
+      for b, rec in enumerate(recs):
+        rec["index"], rec["frames"] = index, int(n[b])
+        index += 1
+        yield rec
