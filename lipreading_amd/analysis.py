@@ -8,24 +8,21 @@ from the decoded transcript's alignment on the device (confusion_matrix below); 
 """
 import torch
 
-from .data import BOS
+from .data import BOS, host_max_len
 
 # analysis.py:133-139: the 26 letters grouped by viseme (vowels and w / b p m / f v / alveolars / j / velars and x / h)
 VISEME_ORDER = list("aeiyouw" "bpm" "fv" "tdnszlr" "j" "kqcgx" "h")
 
 
 def encode_for_beam(encoder, frames, frame_lens, device, with_ctc=False):
-  """One encoder pass over the batch -> (hidden (B, T, Hd), frame_lens on the device, final_state), and with
-  with_ctc=True the CTC head's log-probs (B, T, V+1) of the same pass as a fourth item."""
+  """One encoder pass over the batch -> (hidden (B, T, Hd), frame_lens on the device, final_state, y): y is the CTC
+  head's log-probs (B, T, V+1) of the same pass with with_ctc=True, else None."""
   if with_ctc:
     need_ctc_head(encoder)
-  max_len = int(frame_lens.max()) if not frame_lens.is_cuda else None
   frame_lens_d = frame_lens.to(device)
-  out = encoder(frames.to(device), frame_lens_d, max_len=max_len)
+  out = encoder(frames.to(device), frame_lens_d, max_len=host_max_len(frame_lens))
   hidden, state = (out[1], out[2]) if encoder.enable_ctc else (out[0], out[1])
-  if with_ctc:
-    return hidden, frame_lens_d, state, out[0]
-  return hidden, frame_lens_d, state
+  return hidden, frame_lens_d, state, (out[0] if with_ctc else None)
 
 
 def need_ctc_head(encoder):
@@ -34,15 +31,23 @@ def need_ctc_head(encoder):
     raise ValueError("joint CTC/attention decoding (ctc_weight > 0) needs an encoder built with enable_ctc=True")
 
 
-def best_ids(decoding_step, hidden, frame_lens, state, beam_width, max_label_len, ctc_log_probs=None,
-             ctc_weight=0.0, pre_beam=None):
-  """The best hypothesis of every utterance as host lists of token ids (the final EOS included when reached);
-  with ctc_log_probs, of the joint CTC/attention search."""
+def best_beam(decoding_step, hidden, frame_lens, state, beam_width, max_label_len, ctc_log_probs=None,
+              ctc_weight=0.0, pre_beam=None):
+  """The best hypothesis of every utterance, left on the device: (ids (B, L) view, lens (B,) view) of beam slot 0.
+  With ctc_log_probs the joint CTC/attention search; without, beam_search gets no joint keyword at all."""
   joint = {} if ctc_log_probs is None else dict(ctc_log_probs=ctc_log_probs, ctc_weight=ctc_weight,
                                                  pre_beam=pre_beam)
   ids, lens, _ = decoding_step.beam_search(hidden, frame_lens, state, beam_width=beam_width,
                                            max_label_len=max_label_len, **joint)
-  ids, lens = ids[:, 0].cpu(), lens[:, 0].cpu()
+  return ids[:, 0], lens[:, 0]
+
+
+def best_ids(decoding_step, hidden, frame_lens, state, beam_width, max_label_len, ctc_log_probs=None,
+             ctc_weight=0.0, pre_beam=None):
+  """best_beam's hypotheses as host lists of token ids (the final EOS included when reached)."""
+  ids, lens = best_beam(decoding_step, hidden, frame_lens, state, beam_width, max_label_len, ctc_log_probs,
+                        ctc_weight, pre_beam)
+  ids, lens = ids.cpu(), lens.cpu()
   return [ids[b, :int(lens[b])].tolist() for b in range(ids.shape[0])]
 
 
@@ -57,13 +62,9 @@ def inference(encoder, decoding_step, frames, frame_lens, chars, char_lens, devi
   encoder.eval()
   decoding_step.eval()
   with torch.no_grad():
-    if ctc_weight > 0:
-      hidden, lens_d, state, y = encode_for_beam(encoder, frames, frame_lens, device, with_ctc=True)
-      best = best_ids(decoding_step, hidden, lens_d, state, beam_width, max_label_len, ctc_log_probs=y,
-                      ctc_weight=ctc_weight)
-    else:
-      hidden, lens_d, state = encode_for_beam(encoder, frames, frame_lens, device)
-      best = best_ids(decoding_step, hidden, lens_d, state, beam_width, max_label_len)
+    hidden, lens_d, state, y = encode_for_beam(encoder, frames, frame_lens, device, with_ctc=ctc_weight > 0)
+    best = best_ids(decoding_step, hidden, lens_d, state, beam_width, max_label_len, ctc_log_probs=y,
+                    ctc_weight=ctc_weight)
   outputs = [''.join(idx2char[int(i)] for i in [char2idx[BOS]] + h) for h in best]
   chars, char_lens = chars.cpu(), char_lens.cpu()
   gt = [''.join(idx2char[int(c)] for c in chars[i][:int(char_lens[i])]) for i in range(len(best))]

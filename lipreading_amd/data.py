@@ -26,6 +26,12 @@ def default_char2idx():
   return c2i
 
 
+def host_max_len(frame_lens):
+  """The batch's longest clip for the encoder's max_len=: read off the host copy the collate hands over, None when
+  the lengths live on the device (the encoder then pays that read itself)."""
+  return int(frame_lens.max()) if not frame_lens.is_cuda else None
+
+
 def pad_frames(seqs, device):
   """(len_i, ...) float sequences -> ((B, Tmax, ...) float32 on `device`, lens int64)."""
   assert len(seqs) > 0

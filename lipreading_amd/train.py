@@ -19,7 +19,7 @@ from .encoder import VideoEncoder as _VideoEncoder
 
 from . import _C
 from .ctc import ctc_loss_prepared, ctc_loss_with_status, prepare_ctc_inputs
-from .data import BOS, EOS, PAD
+from .data import BOS, EOS, PAD, host_max_len
 from .optim import FusedAdam
 
 
@@ -505,7 +505,7 @@ def train(encoder, decoding_step, data_loader, opt, device, char2idx,
   flag2 = torch.zeros(2, dtype=torch.int32, device=device) if device.type == "cuda" else None
   for frames, frame_lens, chars, char_lens in data_loader:
     _check_framing(chars, char_lens, frame_lens, char2idx, use_ctc)
-    max_len = int(frame_lens.max()) if not frame_lens.is_cuda else None
+    max_len = host_max_len(frame_lens)
     label_lens_host = (char_lens - 1).cpu()
     frames, chars = frames.to(device, non_blocking=True), chars.to(device, non_blocking=True)
     frame_lens_d, char_lens_d = frame_lens.to(device, non_blocking=True), char_lens.to(device, non_blocking=True)
@@ -577,7 +577,7 @@ def eval(encoder, decoding_step, data_loader, device, char2idx):
       _check_framing(chars, char_lens, frame_lens, char2idx, use_ctc, in_eval=True)
       if on_gpu:
         _roll_faults(device)   # a time-out in an earlier batch must not mark this one
-      max_len = int(frame_lens.max()) if not frame_lens.is_cuda else None
+      max_len = host_max_len(frame_lens)
       label_lens_host = (char_lens - 1).cpu()
       frames, chars = frames.to(device), chars.to(device)
       frame_lens_d = frame_lens.to(device)
@@ -619,81 +619,83 @@ def eval(encoder, decoding_step, data_loader, device, char2idx):
   return (dec_sum / count).item() if count_h else float('nan'), int(correct.item()), count_h, ctc_avg
 
 
+@contextlib.contextmanager
+def _step_kernels(encoder):
+  """Inside the block the encoder's recurrences run on the per-step kernels (recurrence='f32'), which cannot time out;
+  the saved mode comes back on the way out, also when the block raises.  Yields whether there was anything to switch:
+  an encoder without a `recurrence` attribute (TransformerVideoEncoder) is left untouched."""
+  inner = getattr(encoder, "encoder", encoder)   # (PixelLipReader wraps the VideoEncoder)
+  if not hasattr(inner, "recurrence"):
+    yield False
+    return
+  saved = inner.recurrence
+  inner.recurrence = 'f32'
+  try:
+    yield True
+  finally:
+    inner.recurrence = saved
+
+
+def _retried(encoder, flag2, run):
+  """run()'s result for one batch of an evaluation loop — the encoder and whatever consumes its output, ending in a
+  host read —, from the per-step kernels if a one-launch recurrence timed out under it.  `flag2` is the loop's
+  two-word export buffer on the device, None on a CPU device (nothing to roll or read there).
+
+  The fault words are rolled per batch, as eval() does: only THIS batch's time-out counts.  (Round 4 read
+  lr_rnn_pair_errors() here — pending + total, cleared by the read —, so one timed-out TRAINING step of the epoch
+  made the first validation batch look faulted and took the epoch's count away from whoever reads it next.)  The
+  word is read once, after run() has synchronised, so the read costs no wait of its own; when it is set, run()'s
+  output is garbage — and val_cer drives save_best_model and the annealing — so the batch is run again instead of
+  being scored, and the word is not read a second time."""
+  if flag2 is None:
+    return run()
+  _roll_faults(flag2.device)
+  out = run()
+  if not bool(_fault_keep(flag2)):
+    with _step_kernels(encoder) as switched:
+      if switched:
+        out = run()
+  return out
+
+
+def _host_cer(encoder, data_loader, device, char2idx, hypotheses):
+  """The host CER loop: sum of space-free edit distances / sum of space-free reference lengths over the loader.
+  hypotheses(frames, frame_lens) returns the batch's transcripts as strings without EOS, having read them back from
+  the device; it is called through _retried, so a batch whose recurrence timed out is transcribed again."""
+  from .decoder import _edit_distance
+  inv = {v: k for k, v in char2idx.items()}
+  encoder.eval()
+  dist, total = 0, 0
+  flag2 = torch.zeros(2, dtype=torch.int32, device=device) if torch.device(device).type == "cuda" else None
+  with torch.no_grad():
+    for frames, frame_lens, chars, char_lens in data_loader:
+      hyps = _retried(encoder, flag2, lambda: hypotheses(frames, frame_lens))
+      for b, hyp in enumerate(hyps):
+        ref = ''.join(inv[int(c)] for c in chars[b, 1:int(char_lens[b]) - 1]).replace(' ', '')  # strip BOS/EOS
+        dist += _edit_distance(hyp.replace(' ', ''), ref)
+        total += len(ref)
+  return dist / max(total, 1)
+
+
 def greedy_cer(encoder, data_loader, device, char2idx):
   """Character error rate of the CTC greedy path (decoder.py:64-73 on decoder.py:182-197
   output): sum of edit distances / sum of reference lengths.  The reference composes these
   only in its dead archived script (archive/train_model.py:351-357)."""
   from .decoder import GreedyDecoder, ctc_labels
-  labels = ctc_labels(char2idx)
-  dec = GreedyDecoder(labels, blank_index=0)
-  inv = {v: k for k, v in char2idx.items()}
-  encoder.eval()
-  dist, total = 0, 0
-  on_gpu = torch.device(device).type == "cuda"
-  flag2 = torch.zeros(2, dtype=torch.int32, device=device) if on_gpu else None
-  with torch.no_grad():
-    for frames, frame_lens, chars, char_lens in data_loader:
-      max_len = int(frame_lens.max()) if not frame_lens.is_cuda else None
-      if on_gpu:
-        # per batch, as eval() does: only THIS batch's time-out counts.  (Round 4 read lr_rnn_pair_errors() here —
-        # pending + total, cleared by the read —, so one timed-out TRAINING step of the epoch made the first
-        # validation batch look faulted and took the epoch's count away from whoever reads it next.)
-        _roll_faults(device)
-      log_probs, _, _ = encoder(frames.to(device), frame_lens.to(device), max_len=max_len)
-      strings, _ = dec.decode(log_probs, frame_lens.to(device))
-      # (decode() has just synchronised: reading the flag costs no wait of its own)
-      if on_gpu and not bool(_fault_keep(flag2)):
-        # The one-launch recurrence timed out: these strings are garbage, and val_cer drives save_best_model and the
-        # annealing — decode this batch again on the per-step kernels instead of scoring it
-        inner = getattr(encoder, "encoder", encoder)   # (PixelLipReader wraps the VideoEncoder)
-        if hasattr(inner, "recurrence"):
-          saved, inner.recurrence = inner.recurrence, 'f32'
-          try:
-            log_probs, _, _ = encoder(frames.to(device), frame_lens.to(device), max_len=max_len)
-            strings, _ = dec.decode(log_probs, frame_lens.to(device))
-          finally:
-            inner.recurrence = saved
-      for b in range(len(strings)):
-        ref = ''.join(inv[int(c)] for c in chars[b, 1:int(char_lens[b]) - 1])  # strip BOS/EOS
-        hyp = strings[b][0].replace(EOS, '')
-        dist += dec.cer(hyp, ref)
-        total += len(ref.replace(' ', ''))
-  return dist / max(total, 1)
+  return ctc_cer(encoder, data_loader, device, char2idx, GreedyDecoder(ctc_labels(char2idx), blank_index=0))
 
 
 def ctc_cer(encoder, data_loader, device, char2idx, decoder):
-  """greedy_cer's loop (time-out re-decode included) with any CTC decoder whose decode() returns the reference's
-  (strings, offsets) — e.g. decoder.BeamCTCDecoder(ctc_labels(char2idx), log_probs_input=True, ...); the best
-  hypothesis strings[b][0] is scored.  The encoder's output is log-probabilities: a BeamCTCDecoder here needs
+  """The host CER loop (_host_cer, time-out re-decode included) with any CTC decoder whose decode() returns the
+  reference's (strings, offsets) — e.g. decoder.BeamCTCDecoder(ctc_labels(char2idx), log_probs_input=True, ...); the
+  best hypothesis strings[b][0] is scored.  The encoder's output is log-probabilities: a BeamCTCDecoder here needs
   log_probs_input=True."""
-  inv = {v: k for k, v in char2idx.items()}
-  encoder.eval()
-  dist, total = 0, 0
-  on_gpu = torch.device(device).type == "cuda"
-  flag2 = torch.zeros(2, dtype=torch.int32, device=device) if on_gpu else None
-  with torch.no_grad():
-    for frames, frame_lens, chars, char_lens in data_loader:
-      max_len = int(frame_lens.max()) if not frame_lens.is_cuda else None
-      if on_gpu:
-        _roll_faults(device)
-      log_probs, _, _ = encoder(frames.to(device), frame_lens.to(device), max_len=max_len)
-      strings, _ = decoder.decode(log_probs, frame_lens.to(device))
-      if on_gpu and not bool(_fault_keep(flag2)):
-        # the one-launch recurrence timed out (see greedy_cer): decode this batch again on the per-step kernels
-        inner = getattr(encoder, "encoder", encoder)
-        if hasattr(inner, "recurrence"):
-          saved, inner.recurrence = inner.recurrence, 'f32'
-          try:
-            log_probs, _, _ = encoder(frames.to(device), frame_lens.to(device), max_len=max_len)
-            strings, _ = decoder.decode(log_probs, frame_lens.to(device))
-          finally:
-            inner.recurrence = saved
-      for b in range(len(strings)):
-        ref = ''.join(inv[int(c)] for c in chars[b, 1:int(char_lens[b]) - 1])  # strip BOS/EOS
-        hyp = strings[b][0].replace(EOS, '')
-        dist += decoder.cer(hyp, ref)
-        total += len(ref.replace(' ', ''))
-  return dist / max(total, 1)
+  def hypotheses(frames, frame_lens):
+    lens_d = frame_lens.to(device)
+    log_probs = encoder(frames.to(device), lens_d, max_len=host_max_len(frame_lens))[0]
+    return [s[0].replace(EOS, '') for s in decoder.decode(log_probs, lens_d)[0]]
+
+  return _host_cer(encoder, data_loader, device, char2idx, hypotheses)
 
 
 def attention_cer(encoder, decoding_step, data_loader, device, char2idx, beam_width=10, max_label_len=100,
@@ -701,46 +703,22 @@ def attention_cer(encoder, decoding_step, data_loader, device, char2idx, beam_wi
   """CER of the attention decoder's own transcripts: the best hypothesis of CharDecodingStep.beam_search (the
   reference's analysis.inference, with this build's deterministic rule) with EOS stripped, scored as greedy_cer
   scores the CTC head (sum of space-free edit distances / sum of space-free reference lengths).  A batch whose
-  encoder recurrence timed out is encoded again with recurrence='f32', as in greedy_cer.  ctc_weight > 0 runs the
-  joint CTC/attention search on the CTC head of the same encoder pass (re-encoded with it)."""
+  encoder recurrence timed out is encoded and searched again with recurrence='f32' (_retried).  ctc_weight > 0 runs
+  the joint CTC/attention search on the CTC head of the same encoder pass (re-encoded with it)."""
   from .analysis import best_ids, encode_for_beam, need_ctc_head
-  from .decoder import _edit_distance
-  joint = ctc_weight > 0
-  if joint:
+  if ctc_weight > 0:
     need_ctc_head(encoder)
   inv = {v: k for k, v in char2idx.items()}
   eos = char2idx[EOS]
-  encoder.eval()
   decoding_step.eval()
-  dist, total = 0, 0
-  on_gpu = torch.device(device).type == "cuda"
-  flag2 = torch.zeros(2, dtype=torch.int32, device=device) if on_gpu else None
-  with torch.no_grad():
-    for frames, frame_lens, chars, char_lens in data_loader:
-      if on_gpu:
-        _roll_faults(device)
-      enc_out = encode_for_beam(encoder, frames, frame_lens, device, with_ctc=joint)
-      if on_gpu and not bool(_fault_keep(flag2)):
-        # the one-launch recurrence timed out (see greedy_cer): encode this batch again on the per-step kernels
-        inner = getattr(encoder, "encoder", encoder)
-        if hasattr(inner, "recurrence"):
-          saved, inner.recurrence = inner.recurrence, 'f32'
-          try:
-            enc_out = encode_for_beam(encoder, frames, frame_lens, device, with_ctc=joint)
-          finally:
-            inner.recurrence = saved
-      hidden, lens_d, state = enc_out[:3]
-      if joint:
-        best = best_ids(decoding_step, hidden, lens_d, state, beam_width, max_label_len, ctc_log_probs=enc_out[3],
-                        ctc_weight=ctc_weight, pre_beam=pre_beam)
-      else:
-        best = best_ids(decoding_step, hidden, lens_d, state, beam_width, max_label_len)
-      for b, h in enumerate(best):
-        ref = ''.join(inv[int(c)] for c in chars[b, 1:int(char_lens[b]) - 1])  # strip BOS/EOS
-        hyp = ''.join(inv[int(i)] for i in h if i != eos)
-        dist += _edit_distance(hyp.replace(' ', ''), ref.replace(' ', ''))
-        total += len(ref.replace(' ', ''))
-  return dist / max(total, 1)
+
+  def hypotheses(frames, frame_lens):
+    hidden, lens_d, state, y = encode_for_beam(encoder, frames, frame_lens, device, with_ctc=ctc_weight > 0)
+    best = best_ids(decoding_step, hidden, lens_d, state, beam_width, max_label_len, ctc_log_probs=y,
+                    ctc_weight=ctc_weight, pre_beam=pre_beam)
+    return [''.join(inv[int(i)] for i in h if i != eos) for h in best]
+
+  return _host_cer(encoder, data_loader, device, char2idx, hypotheses)
 
 
 # ---- scoring on the device (lipreading_amd/scoring.py, DESIGN.md §17) -------------------------------------------------
@@ -767,7 +745,7 @@ class _DeviceScoring(object):
     from .decoder import GreedyDecoder, ctc_labels
     from .scoring import EditScorer
     self.encoder, self.device, self.decoding_step = encoder, torch.device(device), decoding_step
-    self.beam = dict(beam_width=beam_width, max_label_len=max_label_len)
+    self.beam = (beam_width, max_label_len)
     self.joint = decoding_step is not None and ctc_weight > 0
     self.ctc_weight, self.pre_beam = ctc_weight, pre_beam
     self.units, self.align = tuple(units), bool(align)
@@ -792,19 +770,16 @@ class _DeviceScoring(object):
 
   def hypotheses(self, frames, frame_lens, frame_lens_d):
     """One encoder pass and one search, all enqueued: (ids (B, W) int32 view, lens (B,) int32 view)."""
-    max_len = int(frame_lens.max()) if not frame_lens.is_cuda else None
     if self.decoding_step is None:
-      log_probs, _, _ = self.encoder(frames, frame_lens_d, max_len=max_len)
+      log_probs, _, _ = self.encoder(frames, frame_lens_d, max_len=host_max_len(frame_lens))
       got = self.decoder.decode_ids(log_probs, frame_lens_d)
       if len(got) == 3:
         return got[0], got[2]
       return got[0][:, 0], got[2][:, 0]       # the best hypothesis of (B, W, T) / (B, W)
-    from .analysis import encode_for_beam
-    enc_out = encode_for_beam(self.encoder, frames, frame_lens, self.device, with_ctc=self.joint)
-    hidden, lens_d, state = enc_out[:3]
-    joint = dict(ctc_log_probs=enc_out[3], ctc_weight=self.ctc_weight, pre_beam=self.pre_beam) if self.joint else {}
-    ids, lens, _ = self.decoding_step.beam_search(hidden, lens_d, state, **self.beam, **joint)
-    return ids[:, 0], lens[:, 0]
+    from .analysis import best_beam, encode_for_beam
+    hidden, lens_d, state, y = encode_for_beam(self.encoder, frames, frame_lens, self.device, with_ctc=self.joint)
+    return best_beam(self.decoding_step, hidden, lens_d, state, *self.beam, ctc_log_probs=y, ctc_weight=self.ctc_weight,
+                     pre_beam=self.pre_beam)
 
 
 def _device_batch(ctx, k, frames, frame_lens, frame_lens_d, chars_d, char_lens_d, gated=True):
@@ -851,20 +826,13 @@ def _device_score_run(encoder, data_loader, device, char2idx, decoder=None, deco
     again = set(i for i, g in enumerate(gated.tolist()) if g != 0)
     rescored = 0
     if again:
-      # a one-launch recurrence timed out in those batches (see greedy_cer): they were left out of the totals; encode
+      # a one-launch recurrence timed out in those batches (see _retried): they were left out of the totals; encode
       # just them again on the per-step kernels and score them — the host loops' immediate re-decode, deferred
-      inner = getattr(encoder, "encoder", encoder)   # (PixelLipReader wraps the VideoEncoder)
-      saved = getattr(inner, "recurrence", None)
-      if saved is not None:
-        inner.recurrence = 'f32'
-      try:
+      with _step_kernels(encoder):
         for k, batch in enumerate(data_loader):
           if k in again:
             _device_batch(ctx, k, *upload(batch), gated=False)
             rescored += 1
-      finally:
-        if saved is not None:
-          inner.recurrence = saved
       res = ctx.scorer.result()
   last_device_score_stats = {"batches": len(data_loader), "gated": len(again), "rescored": rescored}
   return res, ctx.scorer
@@ -904,8 +872,8 @@ def align_loader(encoder, data_loader, device, char2idx, fps=29.97):
 
   Per batch: the encoder, then one lr_ctc_align launch against the TRAINING targets — ctc.prepare_ctc_inputs' labels,
   i.e. chars[:, 1:] with '<EOS>', which the head was trained to emit ('<EOS>' gets a span but belongs to no word) —
-  and one read.  The fault words are rolled and read as in greedy_cer: a batch whose one-launch recurrence timed out
-  is encoded again with recurrence='f32' before it is aligned."""
+  and one read.  The fault words are rolled and read by _retried: a batch whose one-launch recurrence timed out is
+  encoded again with recurrence='f32' before it is aligned."""
   from .align import CTCAligner
   from .analysis import need_ctc_head
   from .decoder import ctc_labels
@@ -919,8 +887,7 @@ def align_loader(encoder, data_loader, device, char2idx, fps=29.97):
   index = 0
   with torch.no_grad():
     for frames, frame_lens, chars, char_lens in data_loader:
-      max_len = int(frame_lens.max()) if not frame_lens.is_cuda else None
-      _roll_faults(device)
+      max_len = host_max_len(frame_lens)
       frames_d, lens_d = frames.to(device), frame_lens.to(device)
       labels_p1, lens32, label_lens32 = prepare_ctc_inputs(chars.to(device), lens_d, char_lens.to(device))
 
@@ -928,18 +895,8 @@ def align_loader(encoder, data_loader, device, char2idx, fps=29.97):
         log_probs = encoder(frames_d, lens_d, max_len=max_len)[0]
         return aligner.records(aligner.align_ids(log_probs, lens32, labels_p1, label_lens32), labels_p1, label_lens32)
 
-      recs = aligned()
-      # (records() has just synchronised: reading the flag costs no wait of its own)
-      if not bool(_fault_keep(flag2)):
-        inner = getattr(encoder, "encoder", encoder)   # (PixelLipReader wraps the VideoEncoder)
-        if hasattr(inner, "recurrence"):
-          saved, inner.recurrence = inner.recurrence, 'f32'
-          try:
-            recs = aligned()
-          finally:
-            inner.recurrence = saved
       n = frame_lens.tolist()
-      for b, rec in enumerate(recs):
+      for b, rec in enumerate(_retried(encoder, flag2, aligned)):
         rec["index"], rec["frames"] = index, int(n[b])
         index += 1
         yield rec

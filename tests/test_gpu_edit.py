@@ -430,6 +430,74 @@ def test_a_gated_batch_is_rescored_once(dev, trained, monkeypatch):
   assert enc.recurrence == before
 
 
+@pytest.mark.parametrize("arm", ["greedy", "ctc_beam", "attention", "joint"])
+def test_every_host_loop_retries_a_timed_out_batch_once(dev, trained, monkeypatch, arm):
+  """greedy_cer, ctc_cer and attention_cer (plain and joint) share one retry: with the host-side reader of the fault
+  word answering 'timed out' for batch 1 (no fault on the GPU, as above), each reads the word once per batch, runs
+  exactly batch 1 again with recurrence='f32', restores the mode, and returns the CER of a by-hand loop that encodes
+  batch 1 on the per-step kernels."""
+  from lipreading_amd import analysis, train as T
+  from lipreading_amd import decoder as D
+  trained_enc, step, loader, c2i, raw = trained
+  inv = {v: k for k, v in c2i.items()}
+  attn = dict(beam_width=4, max_label_len=60, ctc_weight=0.3 if arm == "joint" else 0.0)
+  if arm in ("greedy", "ctc_beam"):
+    enc = raw                            # the untrained encoder: non-empty transcripts
+    ctc = (D.GreedyDecoder(D.ctc_labels(c2i), blank_index=0) if arm == "greedy" else
+           D.BeamCTCDecoder(D.ctc_labels(c2i), beam_width=16, cutoff_top_n=8, log_probs_input=True))
+    loop = ((lambda: T.greedy_cer(enc, loader, dev, c2i)) if arm == "greedy" else
+            (lambda: T.ctc_cer(enc, loader, dev, c2i, ctc)))
+  else:
+    enc = trained_enc
+    loop = lambda: T.attention_cer(enc, step, loader, dev, c2i, **attn)   # noqa: E731
+  before = enc.recurrence
+  assert before != 'f32'
+  seen = {"keep": 0, "modes": []}
+  real_keep, real_fwd = T._fault_keep, enc.forward
+
+  def keep(flag2):
+    k = real_keep(flag2)
+    seen["keep"] += 1
+    return torch.zeros_like(k) if seen["keep"] == 2 else k
+
+  def fwd(*a, **kw):
+    seen["modes"].append(enc.recurrence)
+    return real_fwd(*a, **kw)
+
+  monkeypatch.setattr(T, "_fault_keep", keep)
+  monkeypatch.setattr(enc, "forward", fwd)
+  got = loop()
+  n = len(loader)
+  assert seen["keep"] == n
+  assert seen["modes"] == [before, before, 'f32'] + [before] * (n - 2)
+  assert enc.recurrence == before
+  monkeypatch.undo()
+
+  dist = total = 0
+  enc.eval()
+  step.eval()
+  with torch.no_grad():
+    for k, (frames, frame_lens, chars, char_lens) in enumerate(loader):
+      enc.recurrence = 'f32' if k == 1 else before
+      try:
+        lens_d = frame_lens.to(dev)
+        out = enc(frames.to(dev), lens_d, max_len=int(frame_lens.max()))
+      finally:
+        enc.recurrence = before
+      if arm in ("greedy", "ctc_beam"):
+        hyps = [s[0].replace(EOS, '') for s in ctc.decode(out[0], lens_d)[0]]
+      else:
+        best = analysis.best_ids(step, out[1], lens_d, out[2], attn["beam_width"], attn["max_label_len"],
+                                 ctc_log_probs=out[0] if arm == "joint" else None, ctc_weight=attn["ctc_weight"])
+        hyps = [''.join(inv[i] for i in h if i != c2i[EOS]) for h in best]
+      for b, hyp in enumerate(hyps):
+        ref = ''.join(inv[int(c)] for c in chars[b, 1:int(char_lens[b]) - 1]).replace(' ', '')
+        dist += D._edit_distance(hyp.replace(' ', ''), ref)
+        total += len(ref)
+  print("%s: cer %r (%d / %d)" % (arm, got, dist, total))
+  assert total > 0 and got == dist / total
+
+
 def test_driver_error_with_device_scoring_equals_host_scoring(dev, trained):
   from lipreading_amd import driver
   from lipreading_amd.decoder import BeamCTCDecoder, ctc_labels
