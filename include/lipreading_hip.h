@@ -921,6 +921,56 @@ int lr_ctc_align(const float* log_probs, int64_t stride_b, int64_t stride_t, con
                  int32_t* n_words, float* total, int32_t* status, void* workspace, size_t workspace_bytes, int B, int T,
                  int C, int max_label_len, lr_stream_t stream);
 
+/* ---- A6f (BUILD-DEFINED, no reference symbol): CTC keyword spotting — where is each keyword spoken -------------- */
+/* The reference has no spotter; the specification is this build's (lipreading_amd/csrc/lr_spot.hip),
+ * the yardstick a NumPy restatement kept with the tests (tests/spot_cases.py).  Per sample b with n = sizes[b] frames
+ * and per keyword y[0..L) (L = kw_lens[k], blank excluded): m[t] = max_c lp[t][c], d[t][c] = lp[t][c] - m[t] (one fp32
+ * subtraction).  States j = 0..2L-2: even j is token y[j/2], odd j the blank BETWEEN two tokens; no leading or trailing
+ * blank.  Every state carries (v, st), (-inf, -1) before frame 0.  For t = 0..n-1 and every j, `best` is chosen among
+ * stay (v[t-1][j]), step (v[t-1][j-1], j >= 1), skip (v[t-1][j-2]; j even, j >= 2, y[j/2] != y[j/2-1]) and, for j = 0
+ * only, the fresh start (0.0f, t), IN THIS ORDER, a later candidate replacing an earlier one only if strictly greater;
+ * v[t][j] = best.v + d[t][cls(j)] (one fp32 add), st[t][j] = best.st, or -1 when v[t][j] is -inf.
+ *   log_probs   element (b,t,c) at log_probs[b*stride_b + t*stride_t + c]; a row needs one finite value; NaN and +inf
+ *               are unspecified but stay in bounds
+ *   sizes       [B] int32 or NULL (= T);  keywords [K][kw_stride] int32, ids past kw_lens[k] are never read
+ *   min_scores  [K] fp32 or NULL
+ *   end_score / end_start  [B][K][T] or both NULL: v and st of the last state per frame, -inf / -1 for t >= n
+ *   hit_score / hit_start / hit_end  [B][K][max_hits] in pick order, padded with -inf / -1 / -1;  n_hits [B][K].
+ *               Candidates are the frames t with a finite end_score[t] (>= min_scores[k] when given), spans
+ *               [end_start[t], t + 1).  Up to max_hits times: among the candidates whose span overlaps no span already
+ *               taken (s1 < e2 && s2 < e1) the greatest score, the smallest t on ties.
+ *   status      [B][K]: 0, LR_SPOT_BAD_LENGTH (sizes[b] outside [1, T] or kw_lens[k] outside [1, kw_stride]; judged
+ *               first), LR_SPOT_BAD_ID (an id inside the length outside [0, C) or equal to blank).  Such a pair reads
+ *               nothing out of bounds and writes the padding values everywhere, n_hits = 0.
+ * Limits, from the arguments alone: 1 <= kw_stride <= LR_SPOT_MAX_KW_LEN, T <= LR_SPOT_MAX_T, 1 <= max_hits <=
+ * LR_SPOT_MAX_HITS, K >= 1, else LR_ERR_UNSUPPORTED before any launch.  One launch. */
+#define LR_SPOT_MAX_KW_LEN 32
+#define LR_SPOT_MAX_T 2048
+#define LR_SPOT_MAX_HITS 16
+#define LR_SPOT_BAD_ID (-1)
+#define LR_SPOT_BAD_LENGTH (-2)
+
+/* Workspace lr_ctc_spot needs when end_score is NULL; 0 for arguments it rejects.  16 bytes while the end traces of the
+ * keywords a workgroup has in flight fit in LDS beside the sample's rows; B * K * T * 8 bytes otherwise.  `workspace`
+ * is touched, and has to be non-NULL, only in that last case: it may be NULL with end_score given or an answer of 16. */
+size_t lr_ctc_spot_workspace_bytes(int B, int T, int C, int K, int max_kw_len, int max_hits);
+
+/* What lr_ctc_spot will launch for these sizes, decided on the host (no device call): plan [LR_SPOT_PLAN_WORDS] int32
+ * on the HOST = {lanes of the segment a keyword of max_kw_len tokens takes (16 / 32 / 64), threads per workgroup,
+ * keywords of that length side by side in a wave, keyword groups (wave slots: one per wave) per workgroup, 1 if the sample's rows are
+ * staged into LDS as ratios / 0 if they are read from global memory with only m[t] in LDS, where the end trace lives
+ * without end_score (0 LDS, 1 workspace; with end_score it is the caller's buffer), dynamic LDS bytes, keywords per
+ * workgroup, the longest keyword of a 16-lane segment, the longest of a 32-lane segment, workgroups of the launch}.
+ * Same status as lr_ctc_spot would give for the sizes. */
+#define LR_SPOT_PLAN_WORDS 11
+int lr_ctc_spot_plan(int B, int T, int C, int K, int max_kw_len, int max_hits, int32_t* plan);
+
+int lr_ctc_spot(const float* log_probs, int64_t stride_b, int64_t stride_t, const int32_t* sizes,
+                const int32_t* keywords, int kw_stride, const int32_t* kw_lens, const float* min_scores, int blank,
+                int max_hits, float* hit_score, int32_t* hit_start, int32_t* hit_end, int32_t* n_hits, int32_t* status,
+                float* end_score, int32_t* end_start, void* workspace, size_t workspace_bytes, int B, int T, int C, int K,
+                lr_stream_t stream);
+
 /* ---- A8 (BUILD-DEFINED, no reference symbol): 3-D conv frontend on bf16 MFMA -------------- */
 /* The reference has no conv frontend (src/models/lipreader/model.py:122,153-156 are comments, the
  * `ced` configs are empty); BASELINE.json's north_star asks for one ("im2col + MFMA GEMM for the 3D

@@ -135,6 +135,10 @@ SIGNATURES = {
     "lr_ctc_align_plan": (c_int, [c_int] * 4 + [P]),
     "lr_ctc_align": (c_int, [P, c_int64, c_int64, P, P, c_int, P, P, c_int] + [P] * 12 + [P, c_size_t] + [c_int] * 4 +
                      [P]),
+    "lr_ctc_spot_workspace_bytes": (c_size_t, [c_int] * 6),
+    "lr_ctc_spot_plan": (c_int, [c_int] * 6 + [P]),
+    "lr_ctc_spot": (c_int, [P, c_int64, c_int64, P, P, c_int, P, P, c_int, c_int] + [P] * 7 + [P, c_size_t] +
+                    [c_int] * 4 + [P]),
     "lr_clip_to_ndhwc_bf16": (c_int, [P, c_int, P, c_int64, c_int, c_int, P]),
     "lr_conv3d_pack_weights": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "lr_conv3d_pack_weights_multi": (c_int, [c_int] + [P] * 9 + [P]),

@@ -109,3 +109,48 @@ def word_timings(encoder, data_loader, device, char2idx, fps=29.97):
     else:
       out.append([(w, s / fps, e / fps, lp / max(e - s, 1)) for w, s, e, lp in rec["words"]])
   return out
+
+
+def caption_contains(caption, keyword):
+  """Does `keyword` (a word or a phrase) occur in `caption` at word boundaries: with the caption's edge or a ' ' on
+  either side."""
+  at = caption.find(keyword)
+  while at >= 0:
+    end = at + len(keyword)
+    if (at == 0 or caption[at - 1] == ' ') and (end == len(caption) or caption[end] == ' '):
+      return True
+    at = caption.find(keyword, at + 1)
+  return False
+
+
+def keyword_counts(captions, hits, keywords):
+  """Per keyword, at utterance level: dict(keyword, utterances (captions that contain it), hit (of those, how many have
+  a hit of it), false_hits (hits of it on utterances whose caption does not contain it)).  `hits[i]` is utterance i's
+  list of spot records (their `index` names the keyword).  Counts only: rates are the caller's."""
+  out = [dict(keyword=kw, utterances=0, hit=0, false_hits=0) for kw in keywords]
+  for caption, found in zip(captions, hits):
+    per = [0] * len(out)
+    for h in found:
+      per[h["index"]] += 1
+    for k, kw in enumerate(keywords):
+      if caption_contains(caption, kw):
+        out[k]["utterances"] += 1
+        out[k]["hit"] += per[k] > 0
+      else:
+        out[k]["false_hits"] += per[k]
+  return out
+
+
+def keyword_report(encoder, data_loader, device, char2idx, keywords, **spotter_kw):
+  """keyword_counts of train.spot_loader's hits against the loader's own captions (BOS and EOS
+  stripped), both taken from ONE walk of the loader: a shuffling loader is counted right and pays its decode once."""
+  from . import train as T
+  inv = {v: k for k, v in char2idx.items()}
+  keywords = list(keywords)
+  captions, hits = [], []
+  walk = T.spot_batches(encoder, data_loader, device, char2idx, keywords, **spotter_kw)
+  for (_, _, chars, char_lens), spotted in walk:
+    for b in range(len(char_lens)):
+      captions.append(''.join(inv[int(c)] for c in chars[b, 1:int(char_lens[b]) - 1]))
+    hits.extend(spotted)
+  return keyword_counts(captions, hits, keywords)

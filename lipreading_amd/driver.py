@@ -63,6 +63,12 @@ DEFAULTS = dict(  # train.py:134-167
     # head as it then stands (train.align_loader: lr_ctc_align) — one JSON object per line: utterance index, status,
     # total, words and characters with their frame and second spans.  Needs a CTC head.
     align="",
+    # --spot=PATH ('' = off) with --keywords=a,b,c (or a file, one keyword per line): after the last epoch, where each
+    # keyword is spoken in every validation utterance by the CTC head as it then stands (train.spot_loader:
+    # lr_ctc_spot) — one JSON object per line: utterance index, frames, hits with their frame and second spans, score
+    # and confidence.  --spot_confidence=p in (0, 1] (0 = no threshold) keeps spans whose per-character confidence is
+    # at least p; --spot_max_hits spans per (utterance, keyword).  Needs a CTC head.
+    spot="", keywords="", spot_confidence=0.0, spot_max_hits=4,
 )
 
 
@@ -159,6 +165,7 @@ def parse_flags(argv, defaults=DEFAULTS):
         out[name] = True
   augment_spec(out)
   align_check(out)
+  spot_check(out)
   return out
 
 
@@ -177,6 +184,53 @@ def align_check(f):
   """ValueError for --align without a CTC head (neither --enable_ctc nor a regime that is encoder + CTC)."""
   if f.get("align") and not f.get("enable_ctc"):
     raise ValueError("--align=%s needs a CTC head: --enable_ctc=True (or a CTC-only regime)" % f["align"])
+
+
+def spot_check(f):
+  """ValueError for --spot without a CTC head or without --keywords, and for thresholds outside their ranges."""
+  if not f.get("spot"):
+    return
+  if not f.get("enable_ctc"):
+    raise ValueError("--spot=%s needs a CTC head: --enable_ctc=True (or a CTC-only regime)" % f["spot"])
+  if not f.get("keywords"):
+    raise ValueError("--spot=%s needs --keywords=a,b,c or --keywords=FILE" % f["spot"])
+  if not 0.0 <= float(f.get("spot_confidence") or 0.0) <= 1.0:
+    raise ValueError("--spot_confidence must be 0 (no threshold) or a confidence up to 1, got %r"
+                     % (f["spot_confidence"],))
+  if not 1 <= int(f.get("spot_max_hits", 4)) <= 16:
+    raise ValueError("--spot_max_hits must be in [1, 16], got %r" % (f["spot_max_hits"],))
+
+
+def read_keywords(text):
+  """--keywords: a comma-separated list, or a file with one keyword per line.  Text with a comma in it is always a
+  list; without one it is a file if it names one, else a single keyword.  Blanks around a keyword are dropped (blanks
+  inside a phrase stay); empty entries and lines are skipped."""
+  if "," not in text and os.path.isfile(text):
+    with open(text) as f:
+      words = f.read().splitlines()
+  else:
+    words = text.split(",")
+  words = [w.strip() for w in words if w.strip()]
+  if not words:
+    raise ValueError("--keywords=%s names no keyword" % text)
+  return words
+
+
+def write_spots(path, encoder, loader, device, char2idx, keywords, min_confidence=None, max_hits=4, fps=29.97):
+  """train.spot_loader over `loader` as JSON lines in `path`: index, frames, hits (keyword, start / end in frames,
+  start_s / end_s in seconds, score, confidence).  Returns dict(path, utterances, keywords, hits)."""
+  import json
+  from . import train as T
+  n = total = 0
+  with open(path, "w") as out:
+    for rec in T.spot_loader(encoder, loader, device, char2idx, keywords, fps=fps, max_hits=max_hits,
+                             min_confidence=min_confidence):
+      found = [dict(keyword=h["keyword"], start=h["start"], end=h["end"], start_s=h["start"] / fps,
+                    end_s=h["end"] / fps, score=h["score"], confidence=h["confidence"]) for h in rec["hits"]]
+      out.write(json.dumps(dict(index=rec["index"], frames=rec["frames"], hits=found)) + "\n")
+      n += 1
+      total += len(found)
+  return dict(path=path, utterances=n, keywords=len(keywords), hits=total)
 
 
 def write_alignments(path, encoder, loader, device, char2idx, fps=29.97):
@@ -329,6 +383,7 @@ def run(**flags):
     # the build-defined regimes are encoder + CTC with greedy CER (parse_flags sets the same for flag files)
     f["enable_ctc"], f["ctc_only"] = flags.get("enable_ctc", True), flags.get("ctc_only", True)
   align_check(f)
+  spot_check(f)
   torch.manual_seed(f["seed"])
   rand = np.random.RandomState(seed=f["seed"])
   assert torch.cuda.is_available(), "the driver runs the HIP path: an MI355X is required (no CPU fallback)"
@@ -454,6 +509,11 @@ def run(**flags):
     out["align"] = write_alignments(f["align"], encoder, val_loader, device, char2idx)
     print("Aligned %(utterances)d validation utterances (%(infeasible)d too short for their caption): %(path)s"
           % out["align"])
+  if f["spot"]:
+    out["spot"] = write_spots(f["spot"], encoder, val_loader, device, char2idx, read_keywords(f["keywords"]),
+                              min_confidence=f["spot_confidence"] or None, max_hits=f["spot_max_hits"])
+    print("Spotted %(keywords)d keywords in %(utterances)d validation utterances (%(hits)d hits): %(path)s"
+          % out["spot"])
   return out
 
 

@@ -900,3 +900,47 @@ def align_loader(encoder, data_loader, device, char2idx, fps=29.97):
         rec["index"], rec["frames"] = index, int(n[b])
         index += 1
         yield rec
+
+
+# ---- keyword spotting over a loader (lipreading_amd/spot.py) ------------------------------------------
+
+def spot_batches(encoder, data_loader, device, char2idx, keywords, **spotter_kw):
+  """spot_loader's walk, batch by batch: a generator of (the loader's batch, KeywordSpotter.spot's answer for it), so
+  that a caller who also wants the captions (analysis.keyword_report) takes them from the same walk."""
+  from .analysis import need_ctc_head
+  from .decoder import ctc_labels
+  from .spot import KeywordSpotter
+  device = torch.device(device)
+  if device.type != "cuda":
+    raise _C.LipReadingHipError("keyword spotting runs on the MI355X only (no CPU fallback)")
+  need_ctc_head(encoder)
+  spotter = KeywordSpotter(ctc_labels(char2idx), keywords, blank_index=0, **spotter_kw)
+  encoder.eval()
+  flag2 = torch.zeros(2, dtype=torch.int32, device=device)
+  with torch.no_grad():
+    for batch in data_loader:
+      frames, frame_lens = batch[0], batch[1]
+      max_len = host_max_len(frame_lens)
+      frames_d, lens_d = frames.to(device), frame_lens.to(device)
+
+      def spotted():
+        log_probs = encoder(frames_d, lens_d, max_len=max_len)[0]
+        return spotter.spot(log_probs, lens_d)
+
+      yield batch, _retried(encoder, flag2, spotted)
+
+
+def spot_loader(encoder, data_loader, device, char2idx, keywords, **spotter_kw):
+  """Where is each of `keywords` spoken in every utterance of `data_loader`, by the encoder's CTC head: a generator of
+  one record per utterance, in the loader's order — dict(index (the running utterance number), frames (the clip's
+  length), hits (spot.KeywordSpotter.records' list: keyword, index, start, end, score, confidence)).  `spotter_kw` goes
+  to KeywordSpotter (fps, max_hits, min_confidence).
+
+  Per batch: the encoder, then one lr_ctc_spot launch and one read, through _retried exactly as align_loader — a batch
+  whose one-launch recurrence timed out is encoded again with recurrence='f32' before it is spotted."""
+  index = 0
+  for batch, spotted in spot_batches(encoder, data_loader, device, char2idx, keywords, **spotter_kw):
+    n = batch[1].tolist()
+    for b, found in enumerate(spotted):
+      yield dict(index=index, frames=int(n[b]), hits=found)
+      index += 1
