@@ -548,6 +548,29 @@ int lr_decoder_joint_beam_search(int mode, int attn_type, const lr_decoder_param
                                  size_t workspace_bytes, int B, int T, int Hd, int Cd, int V, int A,
                                  lr_stream_t stream);
 
+/* Word language model fusion: the joint search above with the ARPA word model of lr_ctc_beam_lm_decode, each
+ * hypothesis scored (1 - ctc_weight) * attention + ctc_weight * CTC + the sum of alpha * lm(word | context) + beta
+ * over its completed words, and kept inside the model's vocabulary letter by letter.  Rule and structure:
+ * lipreading_amd/csrc/lr_attn_beam.hip.  Arguments as lr_decoder_joint_beam_search, plus
+ *   lm                   the blob lr_ctc_beam_lm_pack wrote, on the device, packed for the C = V + 1 CTC classes (class
+ *                        v + 1 = token v): one blob serves lr_ctc_beam_lm_decode and this search
+ *   class_roles          [C] int32 on the device (0 transparent, 1 word character, 2 space)
+ *   alpha, beta          the model's weight and the per-word bonus, as in lr_ctc_beam_lm_decode
+ *   ctc_lp               may be NULL exactly when ctc_weight == 0 (no CTC term is computed: attention + model)
+ * At ctc_weight = 0 the result is NOT lr_decoder_beam_search's: the model's terms reorder candidates, so pre_beam
+ * matters there too.  Limits: those of the joint search and V + 1 <= 256 (else LR_ERR_UNSUPPORTED, workspace query 0);
+ * non-finite alpha or beta, or a NULL lm or class_roles, is LR_ERR_INVALID_ARG. */
+size_t lr_decoder_lm_beam_workspace_bytes(int mode, int attn_type, int num_layers, int B, int K, int Lmax, int T,
+                                          int Hd, int Cd, int V, int A, int C, int pre_beam);
+int lr_decoder_lm_beam_search(int mode, int attn_type, const lr_decoder_params* params_host,
+                              const lr_decoder_upper* upper_host, const float* enc, const int32_t* enc_lens,
+                              const float* h0, const float* c0, const float* ctc_lp, int64_t stride_b,
+                              int64_t stride_t, int C, int blank, double ctc_weight, int pre_beam, const void* lm,
+                              const int32_t* class_roles, float alpha, float beta, int bos, int eos, int pad,
+                              int beam_width, int max_label_len, int poll_every, int32_t* out_ids, int32_t* out_lens,
+                              float* out_scores, int32_t* rounds_host, void* workspace, size_t workspace_bytes, int B,
+                              int T, int Hd, int Cd, int V, int A, lr_stream_t stream);
+
 /* The decoder loss of the train loop (train_better_model.py:62,65): over the R = B*L (sample, step) rows,
  * -sum_r log_probs[r][label_r] for label_r != ignore_index (F.nll_loss(ignore_index=PAD, reduction='sum') summed
  * over the steps) divided by the number of such rows ((labels != PAD).sum()).  labels: int64, row (b, i) at

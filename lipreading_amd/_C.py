@@ -105,6 +105,10 @@ SIGNATURES = {
     "lr_decoder_joint_beam_search": (c_int, [c_int, c_int, P, P, P, P, P, P, P, c_int64, c_int64, c_int, c_int,
                                              c_double, c_int] + [c_int] * 6 + [P, P, P, P, P, c_size_t] +
                                     [c_int] * 6 + [P]),
+    "lr_decoder_lm_beam_workspace_bytes": (c_size_t, [c_int] * 13),
+    "lr_decoder_lm_beam_search": (c_int, [c_int, c_int, P, P, P, P, P, P, P, c_int64, c_int64, c_int, c_int,
+                                          c_double, c_int, P, P, c_float, c_float] + [c_int] * 6 +
+                                  [P, P, P, P, P, c_size_t] + [c_int] * 6 + [P]),
     "lr_ctc_prepare_i64": (c_int, [P, c_int64, P, P, P, P, P, c_int, c_int, P]),
     "lr_nll_mean_forward": (c_int, [P, P, c_int64, c_int, c_int, P, c_int, c_int, P]),
     "lr_nll_forward3": (c_int, [P, P, c_int64, c_int, c_int, P, c_int, c_int, P]),

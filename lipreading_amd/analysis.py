@@ -32,30 +32,34 @@ def need_ctc_head(encoder):
 
 
 def best_beam(decoding_step, hidden, frame_lens, state, beam_width, max_label_len, ctc_log_probs=None,
-              ctc_weight=0.0, pre_beam=None):
+              ctc_weight=0.0, pre_beam=None, lm=None):
   """The best hypothesis of every utterance, left on the device: (ids (B, L) view, lens (B,) view) of beam slot 0.
-  With ctc_log_probs the joint CTC/attention search; without, beam_search gets no joint keyword at all."""
+  With ctc_log_probs the joint CTC/attention search; without, beam_search gets no joint keyword at all.  `lm` (a
+  lm.WordLM) adds the word language model to either; without one beam_search gets no such keyword."""
   joint = {} if ctc_log_probs is None else dict(ctc_log_probs=ctc_log_probs, ctc_weight=ctc_weight,
                                                  pre_beam=pre_beam)
+  if lm is not None:
+    joint.update(lm=lm, pre_beam=pre_beam)
   ids, lens, _ = decoding_step.beam_search(hidden, frame_lens, state, beam_width=beam_width,
                                            max_label_len=max_label_len, **joint)
   return ids[:, 0], lens[:, 0]
 
 
 def best_ids(decoding_step, hidden, frame_lens, state, beam_width, max_label_len, ctc_log_probs=None,
-             ctc_weight=0.0, pre_beam=None):
+             ctc_weight=0.0, pre_beam=None, lm=None):
   """best_beam's hypotheses as host lists of token ids (the final EOS included when reached)."""
   ids, lens = best_beam(decoding_step, hidden, frame_lens, state, beam_width, max_label_len, ctc_log_probs,
-                        ctc_weight, pre_beam)
+                        ctc_weight, pre_beam, lm)
   ids, lens = ids.cpu(), lens.cpu()
   return [ids[b, :int(lens[b])].tolist() for b in range(ids.shape[0])]
 
 
 def inference(encoder, decoding_step, frames, frame_lens, chars, char_lens, device, char2idx, beam_width=5,
-              max_label_len=100, ctc_weight=0.0):
+              max_label_len=100, ctc_weight=0.0, lm=None):
   """analysis.py:12-66.  Returns (outputs, gt): outputs[i] = '<BOS>' + the best hypothesis's characters (with
   '<EOS>' if it reached one), gt[i] = chars[i][:char_lens[i]] joined.  ctc_weight > 0 runs the joint CTC/attention
-  search on the CTC head of the same encoder pass (the encoder needs enable_ctc)."""
+  search on the CTC head of the same encoder pass (the encoder needs enable_ctc); `lm` (a lm.WordLM over
+  decoder.ctc_labels(char2idx)) adds the word language model to the search."""
   if ctc_weight > 0:
     need_ctc_head(encoder)
   idx2char = {val: key for key, val in char2idx.items()}
@@ -64,7 +68,7 @@ def inference(encoder, decoding_step, frames, frame_lens, chars, char_lens, devi
   with torch.no_grad():
     hidden, lens_d, state, y = encode_for_beam(encoder, frames, frame_lens, device, with_ctc=ctc_weight > 0)
     best = best_ids(decoding_step, hidden, lens_d, state, beam_width, max_label_len, ctc_log_probs=y,
-                    ctc_weight=ctc_weight)
+                    ctc_weight=ctc_weight, lm=lm)
   outputs = [''.join(idx2char[int(i)] for i in [char2idx[BOS]] + h) for h in best]
   chars, char_lens = chars.cpu(), char_lens.cpu()
   gt = [''.join(idx2char[int(c)] for c in chars[i][:int(char_lens[i])]) for i in range(len(best))]

@@ -235,14 +235,20 @@ def _joint_args(y, ctc_weight, pre_beam, K, V, enc, enc_lens):
     raise ValueError("ctc_log_probs needs a contiguous class dimension (stride 1), got strides %s" % (y.stride(),))
   if isinstance(ctc_weight, bool) or not isinstance(ctc_weight, (int, float)) or not 0.0 <= ctc_weight <= 1.0:
     raise ValueError("ctc_weight must be a number in [0, 1], got %r" % (ctc_weight,))
+  P = _pre_beam(pre_beam, K, V)
+  lens = enc_lens.detach().cpu() if torch.is_tensor(enc_lens) else torch.as_tensor(enc_lens)
+  if lens.numel() != enc.shape[0] or bool((lens < 1).any()) or bool((lens > enc.shape[1]).any()):
+    raise ValueError("encoder_lens must hold B values in [1, T] for the joint search")
+  return float(ctc_weight), P
+
+
+def _pre_beam(pre_beam, K, V):
+  """The joint and language-model searches' candidates per hypothesis: the default, or `pre_beam` checked."""
   lo, hi = min(K, V - 2), min(64, V - 2)
   P = min(V - 2, -(-3 * K // 2)) if pre_beam is None else pre_beam
   if isinstance(P, bool) or not isinstance(P, int) or not lo <= P <= hi:
     raise ValueError("pre_beam must be an int in [%d, %d], got %r" % (lo, hi, P))
-  lens = enc_lens.detach().cpu() if torch.is_tensor(enc_lens) else torch.as_tensor(enc_lens)
-  if lens.numel() != enc.shape[0] or bool((lens < 1).any()) or bool((lens > enc.shape[1]).any()):
-    raise ValueError("encoder_lens must hold B values in [1, T] for the joint search")
-  return float(ctc_weight), int(P)
+  return int(P)
 
 
 class CharDecodingStep(nn.Module):
@@ -345,7 +351,7 @@ class CharDecodingStep(nn.Module):
     return lp, sampled, final_state
 
   def beam_search(self, encoder_hidden_states, encoder_lens, previous_state, beam_width=10, max_label_len=100,
-                  poll_every=8, ctc_log_probs=None, ctc_weight=0.0, pre_beam=None):
+                  poll_every=8, ctc_log_probs=None, ctc_weight=0.0, pre_beam=None, lm=None):
     """Deterministic beam search through this decoder for every utterance of the batch at once, entirely on the
     device (lr_decoder_beam_search; the rule is in lipreading_amd/csrc/lr_attn_beam.hip and DESIGN.md §14; the
     reference's analysis.py:12-66 inference() does it one utterance at a time with sampled candidates).
@@ -360,7 +366,12 @@ class CharDecodingStep(nn.Module):
     the class dimension must be contiguous) the search is the joint CTC/attention one (lr_decoder_joint_beam_search,
     DESIGN.md §15): each hypothesis is scored (1 - ctc_weight) * attention + ctc_weight * CTC prefix log-probability,
     over `pre_beam` candidates per hypothesis (default min(V - 2, ceil(1.5 K))), and the scores returned are the
-    joint ones.  ctc_weight = 0 gives the attention-only result."""
+    joint ones.  ctc_weight = 0 gives the attention-only result.
+
+    With `lm` (a lipreading_amd.lm.WordLM packed for decoder.ctc_labels(self.char2idx)) the search also adds the word
+    language model's terms and keeps every hypothesis inside the model's vocabulary (lr_decoder_lm_beam_search,
+    DESIGN.md §21).  Without `ctc_log_probs` it then runs at ctc_weight = 0: attention plus the model, still over
+    `pre_beam` candidates per hypothesis (that result is not the plain search's)."""
     K, Lmax = beam_width, max_label_len
     if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= 32:
       raise ValueError("beam_width must be an int in [1, 32], got %r" % (K,))
@@ -368,6 +379,12 @@ class CharDecodingStep(nn.Module):
       raise ValueError("max_label_len must be an int in [1, 65535], got %r" % (Lmax,))
     if isinstance(poll_every, bool) or not isinstance(poll_every, int) or poll_every < 1:
       raise ValueError("poll_every must be a positive int, got %r" % (poll_every,))
+    if lm is not None:
+      from .decoder import ctc_labels
+      if list(getattr(lm, "labels", ())) != ctc_labels(self.char2idx) or getattr(lm, "blank_index", None) != 0:
+        raise ValueError("lm must be a WordLM packed for decoder.ctc_labels(char2idx) with blank_index 0")
+      if ctc_log_probs is None:
+        lam, P = 0.0, _pre_beam(pre_beam, K, self.vocab_size)
     states = list(previous_state) if isinstance(previous_state, tuple) else [previous_state]
     for t in [encoder_hidden_states] + states:
       if not (torch.is_tensor(t) and t.is_cuda):
@@ -391,6 +408,10 @@ class CharDecodingStep(nn.Module):
     V, Cd = self.vocab_size, self.char_dim
     A = max(int(self.attn_hidden_size), 0)
     at = _ATT_CODE[self.attention_type]
+    if lm is not None:
+      y = ctc_log_probs.detach() if ctc_log_probs is not None else None
+      return self._lm_beam_search(L_, mode, at, pstruct, ustruct, NL, enc, enc_lens, h0, c0, y, lam, P, lm, K, Lmax,
+                                  poll_every, A)
     if ctc_log_probs is not None:
       return self._joint_beam_search(L_, mode, at, pstruct, ustruct, NL, enc, enc_lens, h0, c0, ctc_log_probs.detach(),
                                      lam, P, K, Lmax, poll_every, A)
@@ -436,6 +457,34 @@ class CharDecodingStep(nn.Module):
                                              c2i[PAD], K, Lmax, poll_every, ids.data_ptr(), lens.data_ptr(),
                                              scores.data_ptr(), ctypes.byref(rounds), ws.data_ptr(), wbytes, B, T,
                                              Hd, Cd, V, A, _C.stream_handle()), "lr_decoder_joint_beam_search")
+    self.beam_rounds = int(rounds.value)
+    return ids, lens, scores
+
+  def _lm_beam_search(self, L_, mode, at, pstruct, ustruct, NL, enc, enc_lens, h0, c0, y, lam, P, lm, K, Lmax,
+                      poll_every, A):
+    """beam_search's call with a word language model (arguments already checked); y = None runs at lam = 0."""
+    dev = enc.device
+    B, T, Hd = enc.shape
+    V, Cd = self.vocab_size, self.char_dim
+    wbytes = L_.lr_decoder_lm_beam_workspace_bytes(mode, at, NL, B, K, Lmax, T, Hd, Cd, V, A, V + 1, P)
+    if wbytes == 0:
+      raise ValueError("beam search with a language model does not support this shape (B=%d, K=%d, max_label_len=%d, "
+                       "V=%d (at most 255), Hd=%d, T=%d, pre_beam=%d)" % (B, K, Lmax, V, Hd, T, P))
+    blob, roles = lm.tensors(dev)
+    ws = torch.empty(wbytes, dtype=torch.uint8, device=dev)
+    ids = torch.empty((B, K, Lmax + 1), dtype=torch.int32, device=dev)
+    lens = torch.empty((B, K), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, K), dtype=torch.float32, device=dev)
+    rounds = ctypes.c_int32(0)
+    c2i = self.char2idx
+    sb, st = (y.stride(0), y.stride(1)) if y is not None else (0, 0)
+    _C.check(L_.lr_decoder_lm_beam_search(mode, at, ctypes.byref(pstruct),
+                                          ctypes.byref(ustruct) if ustruct is not None else None, enc.data_ptr(),
+                                          enc_lens.data_ptr(), h0.data_ptr(), _C.ptr(c0), _C.ptr(y), sb, st, V + 1, 0,
+                                          lam, P, blob.data_ptr(), roles.data_ptr(), lm.alpha, lm.beta, c2i[BOS],
+                                          c2i[EOS], c2i[PAD], K, Lmax, poll_every, ids.data_ptr(), lens.data_ptr(),
+                                          scores.data_ptr(), ctypes.byref(rounds), ws.data_ptr(), wbytes, B, T, Hd, Cd,
+                                          V, A, _C.stream_handle()), "lr_decoder_lm_beam_search")
     self.beam_rounds = int(rounds.value)
     return ids, lens, scores
 

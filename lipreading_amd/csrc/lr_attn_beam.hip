@@ -83,8 +83,40 @@
 // the select kernel reads only cand.  The CTC log-probs are read in place through (stride_b, stride_t).
 // Extra limits: C = V + 1, blank = 0, lambda in [0, 1] (else LR_ERR_INVALID_ARG); the P range above and
 // T <= 65535 (LR_ERR_UNSUPPORTED).  Precondition: 1 <= enc_lens[b] <= T (the kernels clamp it to stay in bounds).
+//
+// ---- Word language model fusion (lr_decoder_lm_beam_search) ----
+// Everything in the joint specification holds; the following is added.  Inputs beyond the joint search's: the packed
+// model of lr_ctc_beam_lm_pack (lr_lm_dev.h), class_roles[C] as in lr_ctc_beam_lm_decode (0 transparent, 1 word
+// character, 2 space; a token's role is role[v + 1]: a blob packed for decoder.ctc_labels serves both searches), and
+// alpha, beta as in BeamCTCDecoder.
+//   * State.  A hypothesis also carries its language-model sum l in float64 (0 at the start), the trie node of its
+//     current word (root at the start), that node's word id, the last order - 1 completed word ids (<s>-padded) and the
+//     cached term alpha * lm(word | ctx) + beta of its current word: float64, from lm_score's fp32 value; 0 at the
+//     root; a node that is only a prefix (word id -1) gives OOV = -1000.
+//   * Dictionary.  For an unfinished hypothesis a word-character token whose class is not a child of the current trie
+//     node is not a candidate: it is excluded before the top-P scan, as PAD and BOS are, so a row still lists its P
+//     best remaining tokens, or all of them when fewer than P remain.
+//   * Terms.  A space candidate adds the cached term when the current word is non-empty; the word id (-1 stays -1)
+//     shifts into the context and the node returns to the root.  A leading or repeated space adds nothing.  An EOS
+//     candidate also adds the cached term of a non-empty current word (the CTC search's End rule).  Any other
+//     transparent token (UNK) drops the current run unscored and leaves the context unchanged.  A hypothesis finished
+//     by the length cap keeps l as it is: its unfinished word is not scored.
+//   * Score.  s = (1 - lambda) a + lambda c + l (s = c + l at lambda = 1; s = a + l at lambda = 0, where no CTC term
+//     is computed and ctc_lp may be NULL).  Sorting, structural zeros, the finished rule and the outputs are unchanged.
+//   * At lambda = 0 the result is no longer the plain search's: the terms reorder candidates across rows, so P matters.
+// Structure.  joint_score_kernel<true> loads the row's node once, probes the trie for each word-character token a lane
+// owns (the exclusion of the scan) and forms each candidate's l' from the cached term: no lookup.
+// beam_select_kernel<true, true> loads the K parents' language-model state into LDS before it writes any row (rows
+// are updated in place), then gives each survivor its new state: a word character costs one trie probe and one
+// lm_score, a space shifts the context; a carried-over row keeps its state.  No global synchronisation: the hash
+// probes end at the first empty slot of tables packed at load <= 1/2 (pass only blobs the packer produced).
+// Extra limits: V + 1 <= 256 (the trie key holds the class in 8 bits; LR_ERR_UNSUPPORTED, workspace query 0);
+// non-finite alpha or beta, or a NULL blob or roles pointer: LR_ERR_INVALID_ARG.
+#include <type_traits>
+
 #include "lr_common.h"
 #include "lr_decoder_dev.h"
+#include "lr_lm_dev.h"
 
 namespace {
 
@@ -104,6 +136,7 @@ inline int gates_of(int mode) { return mode == LR_RNN_GRU ? 3 : (mode == LR_RNN_
 struct Sizes {
   int B, K, LH, T, Hd, Cd, V, A, G, type, NL;   // LH = Lmax + 1: history capacity
   int P;                                         // joint search: pre-beam size (0: the attention-only search)
+  int LM;                                        // 1: with a word language model (its state is allocated)
 };
 
 // ---- workspace layout, in 4-byte words ------------------------------------------------------------------------
@@ -113,6 +146,7 @@ struct Ws {
   size_t score, len, fin, live, next_in, parent, hist, ustate, ctr, gemm, total;
   size_t hp_slot, gemm_bytes;
   size_t sa, sc, ent_tok, ent_s, ent_a, ent_c, gam, cand;   // joint search only (empty when P == 0)
+  size_t lm_l, lm_node, lm_word, lm_term, lm_ctx, ent_l;    // language model only (empty when LM == 0)
 };
 
 Ws ws_layout(const Sizes& z) {
@@ -172,6 +206,13 @@ Ws ws_layout(const Sizes& z) {
   w.ent_c = take(2 * RP);
   w.gam = take(4 * RT);                // double2 (gamma^n, gamma^b) [R][T]: each row's CTC arrays
   w.cand = take(4 * RT * z.P);         // double2 [R][T][P]: each candidate's arrays, this round
+  const size_t RL = z.LM ? R : 0;
+  w.lm_l = take(2 * RL);               // double: language-model sum l
+  w.lm_node = take(RL);                // trie node of the current word, and the word id it spells
+  w.lm_word = take(RL);
+  w.lm_term = take(2 * RL);            // double: cached term of the current word
+  w.lm_ctx = take(RL * kLmMaxCtx);     // the last order - 1 completed word ids
+  w.ent_l = take(z.LM ? 2 * RP : 0);   // double [R][P]: each entry's l'
   w.total = o;
   return w;
 }
@@ -196,6 +237,9 @@ bool joint_ok(int K, int T, int V, int C, int P) {
   const int hi = V - 2 < 64 ? V - 2 : 64, lo = K < V - 2 ? K : V - 2;
   return C == V + 1 && P >= lo && P <= hi && T <= BEAM_JOINT_MAX_T;
 }
+
+// the fusion's own limit: the trie key holds the class v + 1 in 8 bits
+bool lm_ok(int V) { return V + 1 <= 256; }
 
 // dst[b*K + k][:] = src[b][:] for every k (the start state of every row of utterance b)
 __global__ void beam_bcast_kernel(const float* __restrict__ src, float* __restrict__ dst, int K, int Hd) {
@@ -232,17 +276,23 @@ __device__ __forceinline__ bool ranks_before(S sa, int ia, S sb, int ib) {
   return sa > sb || (sa == sb && ia < ib);
 }
 
-// One wave's scan of one row's lp [V]: the n tokens with the largest lp, PAD and BOS excluded, by lp descending
-// with ties to the lower id.  emit(c, v, lp) runs on every lane for c = 0 .. n-1 (all lanes hold the same values).
-template <typename F>
+struct ExcludeNone {
+  __device__ __forceinline__ bool operator()(int) const { return false; }
+};
+
+// One wave's scan of one row's lp [V]: the n tokens with the largest lp, PAD, BOS and every v with excluded(v)
+// left out, by lp descending with ties to the lower id.  emit(c, v, lp) runs on every lane for c = 0 .. n-1 (all lanes
+// hold the same values); it stops early when fewer than n tokens remain.
+template <typename F, typename X = ExcludeNone>
 __device__ __forceinline__ void wave_topn(const float* __restrict__ row, int lane, int V, int pad, int bos, int n,
-                                          F&& emit) {
+                                          F&& emit, X&& excluded = X()) {
   float val[VPL];
   unsigned avail = 0;
 #pragma unroll
   for (int i = 0; i < VPL; ++i) {
     const int v = lane + 64 * i;
-    const bool ok = v < V && v != pad && v != bos;
+    bool ok = v < V && v != pad && v != bos;
+    if constexpr (!std::is_same<typename std::decay<X>::type, ExcludeNone>::value) ok = ok && !excluded(v);
     val[i] = ok ? row[v] : LR_NEG_INF;
     if (ok) avail |= 1u << i;
   }
@@ -258,7 +308,7 @@ __device__ __forceinline__ void wave_topn(const float* __restrict__ row, int lan
       const int oi = __shfl_xor(bi, d, 64);
       if (ranks_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
     }
-    if (bi == 0x7fffffff) break;   // (uniform) fewer than n tokens left: cannot happen with n <= V - 2
+    if (bi == 0x7fffffff) break;   // (uniform) fewer than n tokens left: only with an exclusion (n <= V - 2)
     if ((bi & 63) == lane) avail &= ~(1u << (bi >> 6));
     emit(c, bi, bv);
   }
@@ -278,6 +328,24 @@ struct JointState {
   int T, P, ctc;            // ctc: lambda > 0 (the CTC terms are computed and carried)
 };
 
+// The language model's state (lr_decoder_lm_beam_search); unused by the instantiations without one.
+struct LmState {
+  const uint8_t* blob;      // the packed model (lr_lm_dev.h)
+  const int32_t* roles;     // [C] kRole*; token v has role roles[v + 1]
+  float alpha, beta;
+  int C;
+  double* l;                // [R] each row's language-model sum
+  int32_t* node;            // [R] trie node of the current word (0: the root, no current word)
+  int32_t* word;            // [R] the word id that node spells (-1: only a prefix)
+  double* term;             // [R] alpha * lm(word | ctx) + beta of the current word, 0 at the root
+  int32_t* ctx;             // [R][kLmMaxCtx] the last order - 1 completed word ids, oldest first
+  double* ent_l;            // [R][P] the round's list: l'
+};
+
+__device__ __forceinline__ int token_role(const LmState& lm, int v) {
+  return v + 1 < lm.C ? lm.roles[v + 1] : kRoleTransparent;
+}
+
 __device__ __forceinline__ int utt_frames(const int32_t* enc_lens, int b, int T) {
   const int t = enc_lens[b];
   return t < 1 ? 1 : (t > T ? T : t);   // a precondition (1 <= enc_lens[b] <= T); clamped to stay in bounds
@@ -288,13 +356,16 @@ __device__ __forceinline__ int utt_frames(const int32_t* enc_lens, int b, int T)
 // contributes itself); e is also the entry's place in the list, so the stable sort is a sort by (score desc, e).
 // JOINT: the list was built by joint_score_kernel (Kc = P, score = the joint score s); the new rows also take
 // their entry's a and c and, when the CTC terms are carried, their candidate's CTC arrays.
-template <bool JOINT>
+// LM (with JOINT): the new rows also take their entry's l and their language-model state, computed here from the
+// parent's (held in LDS: a parent's row may be overwritten by an earlier slot).
+template <bool JOINT, bool LM = false>
 __global__ __launch_bounds__(SEL_THREADS) void beam_select_kernel(
     const float* __restrict__ lp, double* __restrict__ score, int32_t* __restrict__ len, int32_t* __restrict__ fin,
     int32_t* __restrict__ live, int32_t* __restrict__ next_in, int32_t* __restrict__ parent,
     int32_t* __restrict__ hist, int32_t* __restrict__ ustate, int32_t* __restrict__ ctr, int32_t* __restrict__ out_ids,
     int32_t* __restrict__ out_lens, float* __restrict__ out_scores, int K, int Kc, int V, int LH, int bos, int eos,
-    int pad, JointState js) {
+    int pad, JointState js, LmState lm) {
+  static_assert(JOINT || !LM, "the language model rides on the joint search's list");
   constexpr int NEMAX = JOINT ? BEAM_MAX_K * 64 : BEAM_MAX_K * BEAM_MAX_K;
   __shared__ double e_score[NEMAX];
   __shared__ int e_tok[NEMAX];   // token; -1 = a finished hypothesis carried over; -2 = no entry
@@ -302,6 +373,8 @@ __global__ __launch_bounds__(SEL_THREADS) void beam_select_kernel(
   __shared__ int o_len[BEAM_MAX_K], o_state[BEAM_MAX_K];   // o_state: 0 empty slot, 1 unfinished, 2 finished
   __shared__ int sel[BEAM_MAX_K];
   __shared__ int n_sel, all_fin;
+  __shared__ int p_node[LM ? BEAM_MAX_K : 1], p_word[LM ? BEAM_MAX_K : 1], p_ctx[LM ? BEAM_MAX_K : 1][kLmMaxCtx];
+  __shared__ double p_term[LM ? BEAM_MAX_K : 1];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int32_t* u = ustate + (int64_t)b * U_WORDS;
   if (u[U_DONE]) return;   // (uniform) every hypothesis finished: a round changes nothing
@@ -311,6 +384,12 @@ __global__ __launch_bounds__(SEL_THREADS) void beam_select_kernel(
     if (tid < K) {
       o_len[tid] = len[r0 + tid];
       sel[tid] = -1;
+      if constexpr (LM) {
+        p_node[tid] = lm.node[r0 + tid];
+        p_word[tid] = lm.word[r0 + tid];
+        p_term[tid] = lm.term[r0 + tid];
+        for (int q = 0; q < kLmMaxCtx; ++q) p_ctx[tid][q] = lm.ctx[(int64_t)(r0 + tid) * kLmMaxCtx + q];
+      }
     }
     if (tid == 0) n_sel = 0;
     for (int e = tid; e < NE; e += SEL_THREADS) {
@@ -398,6 +477,32 @@ __global__ __launch_bounds__(SEL_THREADS) void beam_select_kernel(
         js.sa[r] = js.ent_a[(int64_t)r0 * Kc + e];
         js.sc[r] = js.ent_c[(int64_t)r0 * Kc + e];
       }
+      if constexpr (LM) {
+        lm.l[r] = lm.ent_l[(int64_t)r0 * Kc + e];
+        const int role = tok < 0 ? -1 : token_role(lm, tok);
+        int node = 0, word = -1;
+        double term = 0.0;
+        int ctx[kLmMaxCtx];
+        for (int q = 0; q < kLmMaxCtx; ++q) ctx[q] = p_ctx[k][q];
+        if (tok < 0) {
+          // a finished hypothesis carried over keeps its state
+          node = p_node[k]; word = p_word[k]; term = p_term[k];
+        } else if (role == kRoleWord && tok != eos) {
+          // the word stays in the dictionary (the score kernel excluded the others); score the new current word once
+          const LmView L = lm_view(lm.blob);
+          const int2 ch = lm_trie_find(L, p_node[k], tok + 1);
+          node = ch.x; word = ch.y;
+          term = (double)lm.alpha * (double)lm_score(L, ctx, ch.y) + (double)lm.beta;
+        } else if (role == kRoleSpace && tok != eos && p_node[k] != 0) {
+          // a space completes a non-empty word: it joins the context (a transparent token drops the run instead)
+          const int m = reinterpret_cast<const LmHeader*>(lm.blob)->order - 1;
+          for (int q = 0; q < m; ++q) ctx[q] = q + 1 < m ? p_ctx[k][q + 1] : p_word[k];
+        }
+        lm.node[r] = node;
+        lm.word[r] = word;
+        lm.term[r] = term;
+        for (int q = 0; q < kLmMaxCtx; ++q) lm.ctx[(int64_t)r * kLmMaxCtx + q] = ctx[q];
+      }
       len[r] = nl;
       fin[r] = f;
       live[r] = 1;
@@ -443,6 +548,9 @@ __device__ __forceinline__ double log_add(double x, double y) {
 // arrays gam[r][t] are the same address for every lane of the row), writes its arrays to cand[r][t][c] (lanes of
 // one t side by side) and its entry (token, s', a', c').  With ctc == 0 (lambda = 0) s' = a' and nothing of the
 // CTC terms is computed.  A candidate whose c' is -inf (a structural zero) is dropped when lambda > 0.
+// LM: word-character tokens that leave the dictionary are excluded from the scan (a row may then list fewer than P:
+// the lanes past them write "no entry"), and each entry takes l' = l plus the row's cached term for a space or EOS.
+template <bool LM>
 __global__ __launch_bounds__(64) void joint_score_kernel(
     const float* __restrict__ lp, const double* __restrict__ score, const int32_t* __restrict__ len,
     const int32_t* __restrict__ fin, const int32_t* __restrict__ live, const int32_t* __restrict__ next_in,
@@ -450,7 +558,7 @@ __global__ __launch_bounds__(64) void joint_score_kernel(
     const double* __restrict__ sa, const double* __restrict__ sc, const double2* __restrict__ gam,
     int32_t* __restrict__ ent_tok, double* __restrict__ ent_s, double* __restrict__ ent_a, double* __restrict__ ent_c,
     double2* __restrict__ cand, const int32_t* __restrict__ enc_lens, double lambda, int ctc, int K, int P, int V,
-    int T, int blank, int bos, int eos, int pad) {
+    int T, int blank, int bos, int eos, int pad, LmState lm) {
   const int r = blockIdx.x, b = r / K, lane = threadIdx.x;
   if (ustate[(int64_t)b * U_WORDS + U_DONE]) return;   // (uniform)
   const int64_t e0 = (int64_t)r * P;
@@ -462,16 +570,31 @@ __global__ __launch_bounds__(64) void joint_score_kernel(
         ent_s[e0] = score[r];
         ent_a[e0] = sa[r];
         ent_c[e0] = sc[r];
+        if constexpr (LM) lm.ent_l[e0] = lm.l[r];
       }
     }
     return;
   }
-  int tok = 0;
+  int tok = LM ? -2 : 0;   // LM: a lane the scan does not reach holds no entry
   float l = 0.f;
-  wave_topn(lp + (int64_t)r * V, lane, V, pad, bos, P, [&](int c, int v, float x) {
-    if (lane == c) { tok = v; l = x; }
-  });
+  if constexpr (LM) {
+    const LmView L = lm_view(lm.blob);
+    const int node = lm.node[r];
+    wave_topn(lp + (int64_t)r * V, lane, V, pad, bos, P, [&](int c, int v, float x) {
+      if (lane == c) { tok = v; l = x; }
+    }, [&](int v) { return v != eos && token_role(lm, v) == kRoleWord && lm_trie_find(L, node, v + 1).x < 0; });
+  } else {
+    wave_topn(lp + (int64_t)r * V, lane, V, pad, bos, P, [&](int c, int v, float x) {
+      if (lane == c) { tok = v; l = x; }
+    });
+  }
   if (lane >= P) return;
+  if constexpr (LM) {
+    if (tok < 0) {
+      ent_tok[e0 + lane] = -2;
+      return;
+    }
+  }
   const double a = sa[r] + (double)l;
   double c = 0.0, s = a;
   if (ctc) {
@@ -502,6 +625,12 @@ __global__ __launch_bounds__(64) void joint_score_kernel(
     c = tok == eos ? log_add(gn, gb) : psi;
     s = lambda == 1.0 ? c : (1.0 - lambda) * a + lambda * c;
   }
+  if constexpr (LM) {
+    // a space or EOS completes the current word: its cached term (0 at the root) joins l
+    const double l1 = lm.l[r] + (tok == eos || token_role(lm, tok) == kRoleSpace ? lm.term[r] : 0.0);
+    s += l1;
+    lm.ent_l[e0 + lane] = l1;
+  }
   ent_tok[e0 + lane] = ctc && c == -__builtin_inf() ? -2 : tok;
   ent_s[e0 + lane] = s;
   ent_a[e0 + lane] = a;
@@ -523,6 +652,18 @@ __global__ void joint_init_kernel(const float* __restrict__ y, int64_t stride_b,
     acc += (double)y[(int64_t)b * stride_b + (int64_t)t * stride_t + blank];
     gam[(int64_t)r * T + t] = make_double2(-__builtin_inf(), acc);
   }
+}
+
+// the start rows' language-model state: l = 0, the trie's root, the context all <s>
+__global__ void lm_init_kernel(LmState lm, int R) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  const int bos = reinterpret_cast<const LmHeader*>(lm.blob)->bos;
+  lm.l[r] = 0.0;
+  lm.node[r] = 0;
+  lm.word[r] = -1;
+  lm.term[r] = 0.0;
+  for (int q = 0; q < kLmMaxCtx; ++q) lm.ctx[(int64_t)r * kLmMaxCtx + q] = bos;
 }
 
 struct StatePtrs {
@@ -568,6 +709,15 @@ extern "C" size_t lr_decoder_joint_beam_workspace_bytes(int mode, int attn_type,
   return ws_layout(z).total * 4;
 }
 
+extern "C" size_t lr_decoder_lm_beam_workspace_bytes(int mode, int attn_type, int num_layers, int B, int K, int Lmax,
+                                                     int T, int Hd, int Cd, int V, int A, int C, int pre_beam) {
+  if (!sizes_ok(mode, attn_type, num_layers, B, K, Lmax, T, Hd, Cd, V, A) || !joint_ok(K, T, V, C, pre_beam) ||
+      !lm_ok(V))
+    return 0;
+  const Sizes z = {B, K, Lmax + 1, T, Hd, Cd, V, A, gates_of(mode), attn_type, num_layers, pre_beam, 1};
+  return ws_layout(z).total * 4;
+}
+
 namespace {
 
 // The joint search's inputs beyond lr_decoder_beam_search's (NULL: the attention-only search).
@@ -578,11 +728,19 @@ struct JointArgs {
   double lambda;
 };
 
+// The language model's inputs beyond the joint search's (NULL: no language model).
+struct LmInputs {
+  const uint8_t* blob;
+  const int32_t* roles;
+  float alpha, beta;
+};
+
 int beam_search_impl(int mode, int attn_type, const lr_decoder_params* p, const lr_decoder_upper* up,
                      const float* enc, const int32_t* enc_lens, const float* h0, const float* c0, int bos, int eos,
                      int pad, int beam_width, int max_label_len, int poll_every, int32_t* out_ids, int32_t* out_lens,
                      float* out_scores, int32_t* rounds_host, void* workspace, size_t workspace_bytes, int B, int T,
-                     int Hd, int Cd, int V, int A, hipStream_t stream, const JointArgs* jt) {
+                     int Hd, int Cd, int V, int A, hipStream_t stream, const JointArgs* jt,
+                     const LmInputs* lmi = nullptr) {
   const int NL = up ? up->num_layers : 1;
   const int K = beam_width, Lmax = max_label_len;
   if (!sizes_ok(mode, attn_type, NL, B, K, Lmax, T, Hd, Cd, V, A)) {
@@ -600,7 +758,7 @@ int beam_search_impl(int mode, int attn_type, const lr_decoder_params* p, const 
                eos != pad);
   if (attn_type == ATT_GENERAL || attn_type == ATT_1LNN) LR_CHECK_ARG(p->attn_w1 && p->attn_b1);
   if (attn_type == ATT_CONCAT) LR_CHECK_ARG(p->attn_w1 && p->attn_b1 && p->attn_w2 && p->attn_b2);
-  const Sizes z = {B, K, Lmax + 1, T, Hd, Cd, V, A, gates_of(mode), attn_type, NL, jt ? jt->P : 0};
+  const Sizes z = {B, K, Lmax + 1, T, Hd, Cd, V, A, gates_of(mode), attn_type, NL, jt ? jt->P : 0, lmi ? 1 : 0};
   const Ws w = ws_layout(z);
   if (workspace_bytes < w.total * 4) return LR_ERR_WORKSPACE;
   float* base = (float*)workspace;
@@ -654,6 +812,13 @@ int beam_search_impl(int mode, int attn_type, const lr_decoder_params* p, const 
           (const double2*)(base + w.cand), enc_lens, T, jt->P, ctc};
     LR_LAUNCH(joint_init_kernel, dim3((R + 255) / 256), dim3(256), 0, stream, jt->y, jt->stride_b, jt->stride_t,
               enc_lens, js.sa, js.sc, js.gam, B, K, T, jt->blank, ctc);
+    LR_TRY(lr_launch_status());
+  }
+  LmState lms = {};
+  if (lmi) {
+    lms = {lmi->blob, lmi->roles, lmi->alpha, lmi->beta, jt->C, (double*)(base + w.lm_l), I(w.lm_node), I(w.lm_word),
+           (double*)(base + w.lm_term), I(w.lm_ctx), (double*)(base + w.ent_l)};
+    LR_LAUNCH(lm_init_kernel, dim3((R + 255) / 256), dim3(256), 0, stream, lms, R);
     LR_TRY(lr_launch_status());
   }
   LR_TRY(lr_sgemm_impl(0, 1, V, GH, Cd, 1.f, p->emb, Cd, p->w_ih, Cd, 0.f, base + w.EW, GH, base + w.biasf[0], 0, 0,
@@ -735,18 +900,30 @@ int beam_search_impl(int mode, int attn_type, const lr_decoder_params* p, const 
     if (!jt) {
       LR_LAUNCH(beam_select_kernel<false>, dim3(B), dim3(SEL_THREADS), 0, stream, (const float*)lp,
                 (double*)(base + w.score), I(w.len), I(w.fin), I(w.live), I(w.next_in), I(w.parent), I(w.hist),
-                I(w.ustate), ctr, out_ids, out_lens, out_scores, K, Kc, V, LH, bos, eos, pad, js);
-    } else {
-      LR_LAUNCH(joint_score_kernel, dim3(R), dim3(64), 0, stream, (const float*)lp, (const double*)(base + w.score),
-                (const int32_t*)I(w.len), (const int32_t*)I(w.fin), (const int32_t*)I(w.live),
-                (const int32_t*)I(w.next_in), (const int32_t*)I(w.ustate), jt->y, jt->stride_b, jt->stride_t,
+                I(w.ustate), ctr, out_ids, out_lens, out_scores, K, Kc, V, LH, bos, eos, pad, js, lms);
+    } else if (!lmi) {
+      LR_LAUNCH(joint_score_kernel<false>, dim3(R), dim3(64), 0, stream, (const float*)lp,
+                (const double*)(base + w.score), (const int32_t*)I(w.len), (const int32_t*)I(w.fin),
+                (const int32_t*)I(w.live), (const int32_t*)I(w.next_in), (const int32_t*)I(w.ustate), jt->y,
+                jt->stride_b, jt->stride_t,
                 (const double*)js.sa, (const double*)js.sc, (const double2*)js.gam, I(w.ent_tok),
                 (double*)(base + w.ent_s), (double*)(base + w.ent_a), (double*)(base + w.ent_c),
-                (double2*)(base + w.cand), enc_lens, jt->lambda, ctc, K, jt->P, V, T, jt->blank, bos, eos, pad);
+                (double2*)(base + w.cand), enc_lens, jt->lambda, ctc, K, jt->P, V, T, jt->blank, bos, eos, pad, lms);
       LR_TRY(lr_launch_status());
       LR_LAUNCH(beam_select_kernel<true>, dim3(B), dim3(SEL_THREADS), 0, stream, (const float*)lp,
                 (double*)(base + w.score), I(w.len), I(w.fin), I(w.live), I(w.next_in), I(w.parent), I(w.hist),
-                I(w.ustate), ctr, out_ids, out_lens, out_scores, K, jt->P, V, LH, bos, eos, pad, js);
+                I(w.ustate), ctr, out_ids, out_lens, out_scores, K, jt->P, V, LH, bos, eos, pad, js, lms);
+    } else {
+      LR_LAUNCH(joint_score_kernel<true>, dim3(R), dim3(64), 0, stream, (const float*)lp,
+                (const double*)(base + w.score), (const int32_t*)I(w.len), (const int32_t*)I(w.fin),
+                (const int32_t*)I(w.live), (const int32_t*)I(w.next_in), (const int32_t*)I(w.ustate), jt->y,
+                jt->stride_b, jt->stride_t, (const double*)js.sa, (const double*)js.sc, (const double2*)js.gam,
+                I(w.ent_tok), (double*)(base + w.ent_s), (double*)(base + w.ent_a), (double*)(base + w.ent_c),
+                (double2*)(base + w.cand), enc_lens, jt->lambda, ctc, K, jt->P, V, T, jt->blank, bos, eos, pad, lms);
+      LR_TRY(lr_launch_status());
+      LR_LAUNCH((beam_select_kernel<true, true>), dim3(B), dim3(SEL_THREADS), 0, stream, (const float*)lp,
+                (double*)(base + w.score), I(w.len), I(w.fin), I(w.live), I(w.next_in), I(w.parent), I(w.hist),
+                I(w.ustate), ctr, out_ids, out_lens, out_scores, K, jt->P, V, LH, bos, eos, pad, js, lms);
     }
     LR_TRY(lr_launch_status());
     LR_LAUNCH(beam_reorder_kernel, dim3(R, NL), dim3(256), 0, stream, sp, (const int32_t*)I(w.parent),
@@ -807,4 +984,29 @@ extern "C" int lr_decoder_joint_beam_search(int mode, int attn_type, const lr_de
   return beam_search_impl(mode, attn_type, p, up, enc, enc_lens, h0, c0, bos, eos, pad, beam_width, max_label_len,
                           poll_every, out_ids, out_lens, out_scores, rounds_host, workspace, workspace_bytes, B, T, Hd,
                           Cd, V, A, (hipStream_t)stream, &jt);
+}
+
+extern "C" int lr_decoder_lm_beam_search(int mode, int attn_type, const lr_decoder_params* p,
+                                         const lr_decoder_upper* up, const float* enc, const int32_t* enc_lens,
+                                         const float* h0, const float* c0, const float* ctc_lp, int64_t stride_b,
+                                         int64_t stride_t, int C, int blank, double ctc_weight, int pre_beam,
+                                         const void* lm, const int32_t* class_roles, float alpha, float beta, int bos,
+                                         int eos, int pad, int beam_width, int max_label_len, int poll_every,
+                                         int32_t* out_ids, int32_t* out_lens, float* out_scores, int32_t* rounds_host,
+                                         void* workspace, size_t workspace_bytes, int B, int T, int Hd, int Cd, int V,
+                                         int A, lr_stream_t stream) {
+  const int NL = up ? up->num_layers : 1;
+  if (sizes_ok(mode, attn_type, NL, B, beam_width, max_label_len, T, Hd, Cd, V, A)) {
+    LR_CHECK_ARG(C == V + 1 && blank == 0);
+    LR_CHECK_ARG(ctc_weight >= 0.0 && ctc_weight <= 1.0);   // false for NaN
+    LR_CHECK_ARG(isfinite(alpha) && isfinite(beta));
+    if (!joint_ok(beam_width, T, V, C, pre_beam) || !lm_ok(V)) return LR_ERR_UNSUPPORTED;
+    LR_CHECK_ARG(lm && class_roles);
+    LR_CHECK_ARG((ctc_lp || ctc_weight == 0.0) && stride_b >= 0 && stride_t >= 0);   // no CTC term at weight 0
+  }
+  const JointArgs jt = {ctc_lp, stride_b, stride_t, C, blank, pre_beam, ctc_weight};
+  const LmInputs lmi = {static_cast<const uint8_t*>(lm), class_roles, alpha, beta};
+  return beam_search_impl(mode, attn_type, p, up, enc, enc_lens, h0, c0, bos, eos, pad, beam_width, max_label_len,
+                          poll_every, out_ids, out_lens, out_scores, rounds_host, workspace, workspace_bytes, B, T, Hd,
+                          Cd, V, A, (hipStream_t)stream, &jt, &lmi);
 }

@@ -48,6 +48,9 @@ DEFAULTS = dict(  # train.py:134-167
     # CER of the joint CTC/attention beam search, the CTC head's prefix probability weighted by --attn_ctc_weight;
     # needs --enable_ctc)
     attn_decode="teacher", attn_beam_width=10, attn_max_label_len=100, attn_ctc_weight=0.3,
+    # --attn_lm_path (an ARPA file, '' = none) adds a word language model to the --attn_decode=beam|joint search
+    # (lm.WordLM), weighted by --attn_lm_alpha, plus --attn_lm_beta per word
+    attn_lm_path="", attn_lm_alpha=0.0, attn_lm_beta=0.0,
     # --prefetch=N > 0: the three loaders are loader.PrefetchLoader of depth N (batch k+1 is gathered into pinned
     # memory, uploaded and collated on a copy stream while step k runs); 0 = the plain BatchLoader
     prefetch=0,
@@ -150,6 +153,8 @@ def parse_flags(argv, defaults=DEFAULTS):
     raise SystemExit("--attn_decode must be teacher, beam or joint")
   if out.get("attn_decode") == "joint" and not out.get("enable_ctc"):
     raise SystemExit("--attn_decode=joint needs --enable_ctc (the CTC head's log-probs)")
+  if out.get("attn_lm_path") and out.get("attn_decode") not in ("beam", "joint"):
+    raise SystemExit("--attn_lm_path needs --attn_decode=beam or joint")
   if not 0.0 <= float(out.get("attn_ctc_weight", 0.3)) <= 1.0:
     raise SystemExit("--attn_ctc_weight must be in [0, 1]")
   if not 1 <= int(out.get("attn_beam_width", 10)) <= 32:
@@ -337,6 +342,11 @@ def make_error_of(f, encoder, decoding_step, ctc_decoder, device, char2idx):
   (cer, wer, ...); the teacher-forced mismatch rate is not an edit distance and is untouched."""
   from . import train as T
   on_device = f.get("score", "host") == "device"
+  with_lm = {}   # the keyword reaches the searches only with a model
+  if f.get("attn_lm_path") and decoding_step is not None and f["attn_decode"] in ("beam", "joint"):
+    from .decoder import ctc_labels
+    from .lm import WordLM
+    with_lm = dict(lm=WordLM(f["attn_lm_path"], ctc_labels(char2idx), alpha=f["attn_lm_alpha"], beta=f["attn_lm_beta"]))
 
   def scored(loader, **how):
     error_of.last_scores = T.device_scores(encoder, loader, device, char2idx, **how)
@@ -353,17 +363,17 @@ def make_error_of(f, encoder, decoding_step, ctc_decoder, device, char2idx):
     if on_device and f["attn_decode"] in ("beam", "joint"):
       return scored(loader, decoding_step=decoding_step, beam_width=f["attn_beam_width"],
                     max_label_len=f["attn_max_label_len"],
-                    ctc_weight=f["attn_ctc_weight"] if f["attn_decode"] == "joint" else 0.0)
+                    ctc_weight=f["attn_ctc_weight"] if f["attn_decode"] == "joint" else 0.0, **with_lm)
     if decoding_step is None:
       if ctc_decoder is not None:
         return T.ctc_cer(encoder, loader, device, char2idx, ctc_decoder)
       return T.greedy_cer(encoder, loader, device, char2idx)
     if f["attn_decode"] == "beam":
       return T.attention_cer(encoder, decoding_step, loader, device, char2idx, beam_width=f["attn_beam_width"],
-                             max_label_len=f["attn_max_label_len"])
+                             max_label_len=f["attn_max_label_len"], **with_lm)
     if f["attn_decode"] == "joint":
       return T.attention_cer(encoder, decoding_step, loader, device, char2idx, beam_width=f["attn_beam_width"],
-                             max_label_len=f["attn_max_label_len"], ctc_weight=f["attn_ctc_weight"])
+                             max_label_len=f["attn_max_label_len"], ctc_weight=f["attn_ctc_weight"], **with_lm)
     _, correct, count, _ = T.eval(encoder, decoding_step, loader, device, char2idx)
     return _cer(correct, count)
   error_of.last_scores = None

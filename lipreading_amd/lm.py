@@ -1,4 +1,5 @@
-"""ARPA n-gram language models for BeamCTCDecoder (the reference's `lm_path`, handed to ctcdecode's KenLM scorer).
+"""ARPA n-gram language models for BeamCTCDecoder (the reference's `lm_path`, handed to ctcdecode's KenLM scorer) and,
+as WordLM, for the attention decoder's beam searches (CharDecodingStep.beam_search(lm=...)).
 
 KenLM is not part of this build.  Its `lmplz` writes ARPA text by default, so this module reads ARPA (plain or
 gzip) into the arrays lr_ctc_beam_lm_pack takes; the device blob's layout is owned by lr_ctc_beam.hip.  KenLM's
@@ -6,6 +7,7 @@ binary formats are not read.
 """
 import ctypes
 import gzip
+import math
 
 import numpy as np
 
@@ -200,3 +202,37 @@ def pack(model, labels, blank_index):
                                  vp(model.log10_backoff), bos, len(dw), vp(dw), vp(off), vp(cl), len(labels)),
            "lr_ctc_beam_lm_pack")
   return out, roles
+
+
+class WordLM(object):
+  """An ARPA word model read, checked and packed once for a label list, for CharDecodingStep.beam_search(lm=...):
+  `labels` are the CTC classes' (decoder.ctc_labels(char2idx): the decoder's token v is class v + 1, so one packed
+  model serves BeamCTCDecoder and the attention searches), `alpha` weighs the model's log-probabilities and `beta` is
+  added per word, as in BeamCTCDecoder.  ValueError for labels without a ' ' or with repeated one-character labels, or
+  for non-finite weights; NotImplementedError for a path that is not ARPA."""
+
+  def __init__(self, path, labels, alpha=0.0, beta=0.0, blank_index=0):
+    if not is_arpa_path(path):
+      raise kenlm_binary_error(path)
+    alpha, beta = float(alpha), float(beta)
+    if not (math.isfinite(alpha) and math.isfinite(beta)):
+      raise ValueError("alpha and beta must be finite")
+    self.labels, self.blank_index = list(labels), int(blank_index)
+    if not 0 <= self.blank_index < len(self.labels):
+      raise ValueError("blank_index %d outside the %d labels" % (blank_index, len(self.labels)))
+    class_roles(self.labels, self.blank_index)   # the label checks come before the file is read
+    self.alpha, self.beta = alpha, beta
+    self.model = read_arpa(path)
+    self.blob, self.roles = pack(self.model, self.labels, self.blank_index)
+    self._dev = {}   # device -> (blob, roles) tensors, uploaded once per device
+
+  def tensors(self, dev):
+    """The packed model and the class roles on `dev`: one host->device copy each, the first time."""
+    import torch
+    dev = torch.device(dev)
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    got = self._dev.get(key)
+    if got is None:
+      got = self._dev[key] = (torch.from_numpy(self.blob).to(dev),
+                              torch.tensor(self.roles, dtype=torch.int32, device=dev))
+    return got

@@ -699,12 +699,13 @@ def ctc_cer(encoder, data_loader, device, char2idx, decoder):
 
 
 def attention_cer(encoder, decoding_step, data_loader, device, char2idx, beam_width=10, max_label_len=100,
-                  ctc_weight=0.0, pre_beam=None):
+                  ctc_weight=0.0, pre_beam=None, lm=None):
   """CER of the attention decoder's own transcripts: the best hypothesis of CharDecodingStep.beam_search (the
   reference's analysis.inference, with this build's deterministic rule) with EOS stripped, scored as greedy_cer
   scores the CTC head (sum of space-free edit distances / sum of space-free reference lengths).  A batch whose
   encoder recurrence timed out is encoded and searched again with recurrence='f32' (_retried).  ctc_weight > 0 runs
-  the joint CTC/attention search on the CTC head of the same encoder pass (re-encoded with it)."""
+  the joint CTC/attention search on the CTC head of the same encoder pass (re-encoded with it); `lm`
+  (a lm.WordLM over decoder.ctc_labels(char2idx)) adds the word language model to the search."""
   from .analysis import best_ids, encode_for_beam, need_ctc_head
   if ctc_weight > 0:
     need_ctc_head(encoder)
@@ -715,7 +716,7 @@ def attention_cer(encoder, decoding_step, data_loader, device, char2idx, beam_wi
   def hypotheses(frames, frame_lens):
     hidden, lens_d, state, y = encode_for_beam(encoder, frames, frame_lens, device, with_ctc=ctc_weight > 0)
     best = best_ids(decoding_step, hidden, lens_d, state, beam_width, max_label_len, ctc_log_probs=y,
-                    ctc_weight=ctc_weight, pre_beam=pre_beam)
+                    ctc_weight=ctc_weight, pre_beam=pre_beam, lm=lm)
     return [''.join(inv[int(i)] for i in h if i != eos) for h in best]
 
   return _host_cer(encoder, data_loader, device, char2idx, hypotheses)
@@ -741,13 +742,13 @@ class _DeviceScoring(object):
   """What a device_scores call carries from batch to batch."""
 
   def __init__(self, encoder, device, char2idx, decoder, decoding_step, beam_width, max_label_len, ctc_weight, pre_beam,
-               units, align, n_batches):
+               units, align, n_batches, lm=None):
     from .decoder import GreedyDecoder, ctc_labels
     from .scoring import EditScorer
     self.encoder, self.device, self.decoding_step = encoder, torch.device(device), decoding_step
     self.beam = (beam_width, max_label_len)
     self.joint = decoding_step is not None and ctc_weight > 0
-    self.ctc_weight, self.pre_beam = ctc_weight, pre_beam
+    self.ctc_weight, self.pre_beam, self.lm = ctc_weight, pre_beam, lm
     self.units, self.align = tuple(units), bool(align)
     inv = {v: k for k, v in char2idx.items()}
     if decoding_step is None:
@@ -779,7 +780,7 @@ class _DeviceScoring(object):
     from .analysis import best_beam, encode_for_beam
     hidden, lens_d, state, y = encode_for_beam(self.encoder, frames, frame_lens, self.device, with_ctc=self.joint)
     return best_beam(self.decoding_step, hidden, lens_d, state, *self.beam, ctc_log_probs=y, ctc_weight=self.ctc_weight,
-                     pre_beam=self.pre_beam)
+                     pre_beam=self.pre_beam, lm=self.lm)
 
 
 def _device_batch(ctx, k, frames, frame_lens, frame_lens_d, chars_d, char_lens_d, gated=True):
@@ -799,7 +800,7 @@ def _device_batch(ctx, k, frames, frame_lens, frame_lens_d, chars_d, char_lens_d
 
 
 def _device_score_run(encoder, data_loader, device, char2idx, decoder=None, decoding_step=None, beam_width=10,
-                      max_label_len=100, ctc_weight=0.0, pre_beam=None, units=('char', 'word'), align=False):
+                      max_label_len=100, ctc_weight=0.0, pre_beam=None, units=('char', 'word'), align=False, lm=None):
   global last_device_score_stats
   device = torch.device(device)
   if device.type != "cuda":
@@ -808,7 +809,7 @@ def _device_score_run(encoder, data_loader, device, char2idx, decoder=None, deco
     from .analysis import need_ctc_head
     need_ctc_head(encoder)
   ctx = _DeviceScoring(encoder, device, char2idx, decoder, decoding_step, beam_width, max_label_len, ctc_weight, pre_beam,
-                       units, align, len(data_loader))
+                       units, align, len(data_loader), lm=lm)
   ctx.scorer.reset()
   encoder.eval()
   if decoding_step is not None:
@@ -839,28 +840,29 @@ def _device_score_run(encoder, data_loader, device, char2idx, decoder=None, deco
 
 
 def device_scores(encoder, data_loader, device, char2idx, decoder=None, decoding_step=None, beam_width=10,
-                  max_label_len=100, ctc_weight=0.0, pre_beam=None, units=('char', 'word'), align=False):
+                  max_label_len=100, ctc_weight=0.0, pre_beam=None, units=('char', 'word'), align=False, lm=None):
   """greedy_cer / ctc_cer / attention_cer's evaluation with the scoring on the device: the dict of
   scoring.EditScorer.result() — cer, wer, distance, ref_len, pairs, ... (hits / sub / ins / dele with align=True).
 
   decoder=None, decoding_step=None: the CTC head's greedy path (greedy_cer).  decoder = a BeamCTCDecoder over
   ctc_labels(char2idx): its best hypothesis (ctc_cer).  decoding_step: the attention decoder's beam search
-  (attention_cer; beam_width, max_label_len, and ctc_weight > 0 with pre_beam for the joint search).
+  (attention_cer; beam_width, max_label_len, and ctc_weight > 0 with pre_beam for the joint search; `lm`, a
+  lm.WordLM, adds the word language model to that search).
 
   Per batch nothing is read back.  A recurrence time-out is handled as in the host loops, but without their per-batch
   read: the device-side fault word gates the batch out of the totals (lr_edit_distance's `gate`), a device vector
   records which batches were gated, and after the last batch one read covers the totals and that vector; only if some
   batch was gated is the loader walked again and just those batches re-encoded with recurrence='f32' and scored."""
   return _device_score_run(encoder, data_loader, device, char2idx, decoder, decoding_step, beam_width, max_label_len,
-                           ctc_weight, pre_beam, units, align)[0]
+                           ctc_weight, pre_beam, units, align, lm)[0]
 
 
 def device_cer(encoder, data_loader, device, char2idx, decoder=None, decoding_step=None, beam_width=10,
-               max_label_len=100, ctc_weight=0.0, pre_beam=None):
+               max_label_len=100, ctc_weight=0.0, pre_beam=None, lm=None):
   """The same float as greedy_cer (no decoder), ctc_cer (`decoder`) or attention_cer (`decoding_step`): sum of
   space-free edit distances / sum of space-free reference lengths, scored on the device (device_scores)."""
   return device_scores(encoder, data_loader, device, char2idx, decoder, decoding_step, beam_width, max_label_len,
-                       ctc_weight, pre_beam, units=('char',))["cer"]
+                       ctc_weight, pre_beam, units=('char',), lm=lm)["cer"]
 
 
 # ---- forced alignment over a loader (lipreading_amd/align.py, DESIGN.md §19) -----------------------------------------

@@ -4,12 +4,15 @@ restatement of tests/test_attn_beam_cpu.py (one oracle call per round over an ut
 reference's inference() walks one utterance at a time).
 
   python tools/bench_attn_beam.py [--iters 10] [--cpu-utts 4] [--poll 8] [--ctc-weight W [--pre-beam P]]
+                                  [--lm PATH [--lm-alpha A] [--lm-beta B]]
 
 B = 32, T = 75, K = 10, Lmax = 100, V = 64, the three shipped decoder shapes (randomly initialised, so most
 hypotheses run to the cap: the worst case of Lmax + 1 rounds).  One JSON line per row and a table at the end.
 --ctc-weight W > 0 times the joint CTC/attention search (lr_decoder_joint_beam_search) on the seeded,
 peaked, model-like CTC frames of tools/bench_beam.py, with P = --pre-beam candidates per hypothesis (default
 min(V - 2, ceil(1.5 K))); the CPU column is then skipped.  W = 0 (the default) keeps today's rows exactly.
+--lm PATH (an ARPA file) times the search with a word language model (lr_decoder_lm_beam_search) over
+ctc_labels() of the fallback vocabulary, at --ctc-weight W (0: attention plus the model, no CTC frames).
 """
 import argparse
 import json
@@ -40,6 +43,9 @@ def main():
   ap.add_argument("--poll", type=int, default=8)
   ap.add_argument("--ctc-weight", type=float, default=0.0)
   ap.add_argument("--pre-beam", type=int, default=None)
+  ap.add_argument("--lm", default=None, help="ARPA word language model")
+  ap.add_argument("--lm-alpha", type=float, default=0.5)
+  ap.add_argument("--lm-beta", type=float, default=0.0)
   a = ap.parse_args()
   import numpy as np
   import torch
@@ -53,6 +59,11 @@ def main():
   torch.set_num_threads(min(16, os.cpu_count() or 1))
   dev = torch.device("cuda:0")
   c2i = default_char2idx()
+  lm = None
+  if a.lm:
+    from lipreading_amd.decoder import ctc_labels
+    from lipreading_amd.lm import WordLM
+    lm = WordLM(a.lm, ctc_labels(c2i), alpha=a.lm_alpha, beta=a.lm_beta)
   rows = []
   for name, rnn_type, attn, Hd, Cd in SHAPES:
     torch.manual_seed(0)
@@ -70,6 +81,8 @@ def main():
       from tools.bench_beam import peaked
       y = torch.tensor(np.log(peaked(np.random.default_rng(0))), device=dev)
       joint = dict(ctc_log_probs=y, ctc_weight=a.ctc_weight, pre_beam=a.pre_beam)
+    if lm is not None:
+      joint.update(lm=lm, pre_beam=a.pre_beam)
     for _ in range(2):
       dec.beam_search(encd, lensd, prevd, beam_width=K, max_label_len=LMAX, poll_every=a.poll, **joint)
     torch.cuda.synchronize()
@@ -92,6 +105,8 @@ def main():
                launches_per_round=launches_per_round(attn) + (1 if joint else 0),
                cpu_f32_ms_per_batch=round(cpu_ms, 1) if joint == {} else None, cpu_utts_timed=n if not joint else 0,
                poll_every=a.poll)
+    if lm is not None:
+      row.update(lm=os.path.basename(a.lm), lm_alpha=a.lm_alpha, lm_beta=a.lm_beta)
     if joint:
       row.update(ctc_weight=a.ctc_weight, pre_beam=a.pre_beam if a.pre_beam is not None else min(V - 2, -(-3 * K // 2)))
     print(json.dumps(row), flush=True)
