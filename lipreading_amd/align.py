@@ -20,6 +20,7 @@ There is no host fall-back: CPU tensors raise LipReadingHipError.
 import torch
 
 from . import _C
+from . import _host
 from . import lm
 
 INFEASIBLE, BAD_ID, BAD_LENGTH = 1, -1, -2   # LR_ALIGN_* (include/lipreading_hip.h)
@@ -37,27 +38,17 @@ class CTCAligner(object):
     self.blank_index, self.fps = int(blank_index), float(fps)
     # without a ' ' label nothing separates words: no word outputs
     self.roles = lm.class_roles(self.labels, self.blank_index) if ' ' in self.labels else None
-    self._class_of = {}
-    for i, l in enumerate(self.labels):
-      if len(l) == 1 and i != self.blank_index:
-        self._class_of.setdefault(l, i)
-    self._roles_dev = {}   # device -> roles tensor, uploaded once per device
-    self._ws = {}          # device -> the largest workspace asked for so far
+    self._class_of = _host.char_classes(self.labels, self.blank_index)
+    self._roles_dev = _host.PerDevice()     # the roles tensor, uploaded once per device
+    self._ws = _host.GrowingWorkspace()
 
   def seconds(self, frame):
     return frame / self.fps
 
-  def _key(self, dev):
-    return (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
-
   def _roles(self, dev):
     if self.roles is None:
       return None
-    key = self._key(dev)
-    got = self._roles_dev.get(key)
-    if got is None:
-      got = self._roles_dev[key] = torch.tensor(self.roles, dtype=torch.int32, device=dev)
-    return got
+    return self._roles_dev.get(dev, lambda d: torch.tensor(self.roles, dtype=torch.int32, device=d))
 
   def align_ids(self, log_probs, sizes, targets, target_lens):
     """One launch, nothing read back: log_probs (B, T, C) fp32 on the GPU (any batch / time strides with unit class
@@ -69,26 +60,18 @@ class CTCAligner(object):
     device: call it from one stream at a time."""
     _C.require_cuda(log_probs, sizes, targets, target_lens)
     L = _C.lib()
-    if log_probs.dim() != 3:
-      raise ValueError("log_probs must be (batch, frames, classes), got %s" % (tuple(log_probs.shape),))
-    lp = log_probs if log_probs.dtype == torch.float32 else log_probs.float()
-    if lp.stride(2) != 1 or lp.stride(0) < 0 or lp.stride(1) < 0:
-      lp = lp.contiguous()
+    lp = _host.log_probs_3d(log_probs, len(self.labels), "log_probs")
     B, T, C = lp.shape
-    if C > len(self.labels):
-      raise KeyError("log_probs has %d classes but only %d labels" % (C, len(self.labels)))
     if targets.dim() != 2 or targets.shape[0] != B or target_lens.dim() != 1 or target_lens.shape[0] != B:
       raise ValueError("targets must be (%d, width) and target_lens (%d,), got %s and %s"
                        % (B, B, tuple(targets.shape), tuple(target_lens.shape)))
-    if sizes is not None and (sizes.dim() != 1 or sizes.shape[0] != B):
-      raise ValueError("sizes must be (%d,), got %s" % (B, tuple(sizes.shape)))
+    sz = _host.int32_vector(sizes, B, "sizes")
+    tl = _host.int32_vector(target_lens, B, "target_lens")
     dev = lp.device
     tg = targets if targets.dtype == torch.int32 else targets.to(torch.int32)
     if tg.shape[1] == 0:
       tg = tg.new_zeros((B, 1))
     tg = tg.contiguous()
-    tl = (target_lens if target_lens.dtype == torch.int32 else target_lens.to(torch.int32)).contiguous()
-    sz = None if sizes is None else (sizes if sizes.dtype == torch.int32 else sizes.to(torch.int32)).contiguous()
     W = tg.shape[1]
     nbytes = L.lr_ctc_align_workspace_bytes(B, T, C, W) if B > 0 and self.blank_index < C else 0
     if nbytes == 0:
@@ -97,25 +80,19 @@ class CTCAligner(object):
                        % (B, T, C, W, self.blank_index, MAX_T, MAX_LABEL_LEN))
     # One workspace per device, grown to the largest shape seen (the back-pointer table when it does not fit in LDS).
     # Calls on ONE stream at a time: two streams aligning concurrently on a device would share the table.
-    key = self._key(dev)
-    ws = self._ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-      ws = self._ws[key] = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    ws = self._ws.get(dev, nbytes)
     roles = self._roles(dev)
-    ints = torch.empty((6 if roles is not None else 2, B, W), dtype=torch.int32, device=dev)
-    flts = torch.empty((2, B, W), dtype=torch.float32, device=dev)
+    # (each output's view is made once: its pointer goes to the kernel and the view itself into the dict)
+    ints = torch.empty((6 if roles is not None else 2, B, W), dtype=torch.int32, device=dev).unbind(0)
+    flts = torch.empty((2, B, W), dtype=torch.float32, device=dev).unbind(0)
     frame_token = torch.empty((B, T), dtype=torch.int32, device=dev)
-    per = torch.empty((2, B), dtype=torch.int32, device=dev)   # status, n_words
+    per = torch.empty((2, B), dtype=torch.int32, device=dev).unbind(0)   # status, n_words
     total = torch.empty((B,), dtype=torch.float32, device=dev)
-    wp = [ints[2 + i].data_ptr() for i in range(4)] + [flts[1].data_ptr(), per[1].data_ptr()] \
-        if roles is not None else [None] * 6
-    with torch.cuda.device(dev):
-      _C.check(L.lr_ctc_align(lp.data_ptr(), lp.stride(0), lp.stride(1), _C.ptr(sz), tg.data_ptr(), W, tl.data_ptr(),
-                              _C.ptr(roles), self.blank_index, frame_token.data_ptr(), ints[0].data_ptr(),
-                              ints[1].data_ptr(), flts[0].data_ptr(), wp[0], wp[1], wp[2], wp[3], wp[4], wp[5],
-                              total.data_ptr(), per[0].data_ptr(), ws.data_ptr(), nbytes, B, T, C, W,
-                              _C.stream_handle()),
-               "lr_ctc_align")
+    wp = [t.data_ptr() for t in ints[2:] + (flts[1], per[1])] if roles is not None else [None] * 6
+    _host.launch(dev, "lr_ctc_align", L.lr_ctc_align, lp.data_ptr(), lp.stride(0), lp.stride(1), _C.ptr(sz),
+                 tg.data_ptr(), W, tl.data_ptr(), _C.ptr(roles), self.blank_index, frame_token.data_ptr(),
+                 ints[0].data_ptr(), ints[1].data_ptr(), flts[0].data_ptr(), *wp, total.data_ptr(), per[0].data_ptr(),
+                 ws.data_ptr(), nbytes, B, T, C, W)
     out = dict(frame_token=frame_token, tok_start=ints[0], tok_end=ints[1], tok_logp=flts[0], total=total,
                status=per[0])
     if roles is not None:

@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _C
+from . import _host
 from .data import BOS, EOS, PAD
 from .encoder import _RNNParams, _direct_grads, _notify
 
@@ -402,89 +403,53 @@ class CharDecodingStep(nn.Module):
     if h0.shape != (self.num_layers, B, Hd):
       raise ValueError("previous_state must be (num_layers, B, hidden), got %s" % (tuple(h0.shape),))
     enc_lens = encoder_lens.to(device=dev, dtype=torch.int32).contiguous()
+    run = (mode, enc, enc_lens, h0, c0, K, Lmax, poll_every)
+    if lm is None and ctc_log_probs is None:
+      return self._run_beam_search(
+          L_.lr_decoder_beam_search, L_.lr_decoder_beam_workspace_bytes, (),
+          "beam search does not support this shape (B=%d, K=%d, max_label_len=%d, V=%d, Hd=%d)" % (B, K, Lmax, V, Hd),
+          (), *run)
+    # the CTC block: frames (None with a model alone, which runs at lam = 0), strides, classes, blank, weight, pre-beam
+    y = ctc_log_probs.detach() if ctc_log_probs is not None else None
+    sb, st = (y.stride(0), y.stride(1)) if y is not None else (0, 0)
+    ctc = (_C.ptr(y), sb, st, V + 1, 0, lam, P)
+    if lm is None:
+      return self._run_beam_search(
+          L_.lr_decoder_joint_beam_search, L_.lr_decoder_joint_beam_workspace_bytes, (V + 1, P),
+          "joint beam search does not support this shape (B=%d, K=%d, max_label_len=%d, V=%d, Hd=%d, T=%d, pre_beam=%d)"
+          % (B, K, Lmax, V, Hd, T, P), ctc, *run)
+    blob, roles = lm.tensors(dev)
+    return self._run_beam_search(
+        L_.lr_decoder_lm_beam_search, L_.lr_decoder_lm_beam_workspace_bytes, (V + 1, P),
+        "beam search with a language model does not support this shape (B=%d, K=%d, max_label_len=%d, V=%d (at most "
+        "255), Hd=%d, T=%d, pre_beam=%d)" % (B, K, Lmax, V, Hd, T, P),
+        ctc + (blob.data_ptr(), roles.data_ptr(), lm.alpha, lm.beta), *run)
+
+  def _run_beam_search(self, search, workspace_bytes, extra, unsupported, middle, mode, enc, enc_lens, h0, c0, K, Lmax,
+                       poll_every):
+    """The one tail of beam_search's three searches (arguments already checked): `search` is the C entry point,
+    `workspace_bytes` its query, which takes `extra` after the common shape, `unsupported` the message for a shape it
+    refuses, and `middle` the arguments that stand between c0 and bos."""
+    dev = enc.device
+    B, T, Hd = enc.shape
     params = self._params()
     pstruct = _C.DecoderParams(*[_C.ptr(p) for p in params[:13]], self.output_mask.data_ptr())
     ustruct, NL = _upper_struct(params[13:], None)
-    V, Cd = self.vocab_size, self.char_dim
-    A = max(int(self.attn_hidden_size), 0)
     at = _ATT_CODE[self.attention_type]
-    if lm is not None:
-      y = ctc_log_probs.detach() if ctc_log_probs is not None else None
-      return self._lm_beam_search(L_, mode, at, pstruct, ustruct, NL, enc, enc_lens, h0, c0, y, lam, P, lm, K, Lmax,
-                                  poll_every, A)
-    if ctc_log_probs is not None:
-      return self._joint_beam_search(L_, mode, at, pstruct, ustruct, NL, enc, enc_lens, h0, c0, ctc_log_probs.detach(),
-                                     lam, P, K, Lmax, poll_every, A)
-    wbytes = L_.lr_decoder_beam_workspace_bytes(mode, at, NL, B, K, Lmax, T, Hd, Cd, V, A)
+    Cd, V, A = self.char_dim, self.vocab_size, max(int(self.attn_hidden_size), 0)
+    wbytes = workspace_bytes(mode, at, NL, B, K, Lmax, T, Hd, Cd, V, A, *extra)
     if wbytes == 0:
-      raise ValueError("beam search does not support this shape (B=%d, K=%d, max_label_len=%d, V=%d, Hd=%d)"
-                       % (B, K, Lmax, V, Hd))
+      raise ValueError(unsupported)
     ws = torch.empty(wbytes, dtype=torch.uint8, device=dev)
     ids = torch.empty((B, K, Lmax + 1), dtype=torch.int32, device=dev)
     lens = torch.empty((B, K), dtype=torch.int32, device=dev)
     scores = torch.empty((B, K), dtype=torch.float32, device=dev)
     rounds = ctypes.c_int32(0)
     c2i = self.char2idx
-    _C.check(L_.lr_decoder_beam_search(mode, at, ctypes.byref(pstruct),
-                                       ctypes.byref(ustruct) if ustruct is not None else None, enc.data_ptr(),
-                                       enc_lens.data_ptr(), h0.data_ptr(), _C.ptr(c0), c2i[BOS], c2i[EOS], c2i[PAD],
-                                       K, Lmax, poll_every, ids.data_ptr(), lens.data_ptr(), scores.data_ptr(),
-                                       ctypes.byref(rounds), ws.data_ptr(), wbytes, B, T, Hd, Cd, V, A,
-                                       _C.stream_handle()), "lr_decoder_beam_search")
-    self.beam_rounds = int(rounds.value)
-    return ids, lens, scores
-
-  def _joint_beam_search(self, L_, mode, at, pstruct, ustruct, NL, enc, enc_lens, h0, c0, y, lam, P, K, Lmax,
-                         poll_every, A):
-    """beam_search's joint CTC/attention call (arguments already checked)."""
-    dev = enc.device
-    B, T, Hd = enc.shape
-    V, Cd = self.vocab_size, self.char_dim
-    wbytes = L_.lr_decoder_joint_beam_workspace_bytes(mode, at, NL, B, K, Lmax, T, Hd, Cd, V, A, V + 1, P)
-    if wbytes == 0:
-      raise ValueError("joint beam search does not support this shape (B=%d, K=%d, max_label_len=%d, V=%d, Hd=%d, "
-                       "T=%d, pre_beam=%d)" % (B, K, Lmax, V, Hd, T, P))
-    ws = torch.empty(wbytes, dtype=torch.uint8, device=dev)
-    ids = torch.empty((B, K, Lmax + 1), dtype=torch.int32, device=dev)
-    lens = torch.empty((B, K), dtype=torch.int32, device=dev)
-    scores = torch.empty((B, K), dtype=torch.float32, device=dev)
-    rounds = ctypes.c_int32(0)
-    c2i = self.char2idx
-    _C.check(L_.lr_decoder_joint_beam_search(mode, at, ctypes.byref(pstruct),
-                                             ctypes.byref(ustruct) if ustruct is not None else None, enc.data_ptr(),
-                                             enc_lens.data_ptr(), h0.data_ptr(), _C.ptr(c0), y.data_ptr(),
-                                             y.stride(0), y.stride(1), V + 1, 0, lam, P, c2i[BOS], c2i[EOS],
-                                             c2i[PAD], K, Lmax, poll_every, ids.data_ptr(), lens.data_ptr(),
-                                             scores.data_ptr(), ctypes.byref(rounds), ws.data_ptr(), wbytes, B, T,
-                                             Hd, Cd, V, A, _C.stream_handle()), "lr_decoder_joint_beam_search")
-    self.beam_rounds = int(rounds.value)
-    return ids, lens, scores
-
-  def _lm_beam_search(self, L_, mode, at, pstruct, ustruct, NL, enc, enc_lens, h0, c0, y, lam, P, lm, K, Lmax,
-                      poll_every, A):
-    """beam_search's call with a word language model (arguments already checked); y = None runs at lam = 0."""
-    dev = enc.device
-    B, T, Hd = enc.shape
-    V, Cd = self.vocab_size, self.char_dim
-    wbytes = L_.lr_decoder_lm_beam_workspace_bytes(mode, at, NL, B, K, Lmax, T, Hd, Cd, V, A, V + 1, P)
-    if wbytes == 0:
-      raise ValueError("beam search with a language model does not support this shape (B=%d, K=%d, max_label_len=%d, "
-                       "V=%d (at most 255), Hd=%d, T=%d, pre_beam=%d)" % (B, K, Lmax, V, Hd, T, P))
-    blob, roles = lm.tensors(dev)
-    ws = torch.empty(wbytes, dtype=torch.uint8, device=dev)
-    ids = torch.empty((B, K, Lmax + 1), dtype=torch.int32, device=dev)
-    lens = torch.empty((B, K), dtype=torch.int32, device=dev)
-    scores = torch.empty((B, K), dtype=torch.float32, device=dev)
-    rounds = ctypes.c_int32(0)
-    c2i = self.char2idx
-    sb, st = (y.stride(0), y.stride(1)) if y is not None else (0, 0)
-    _C.check(L_.lr_decoder_lm_beam_search(mode, at, ctypes.byref(pstruct),
-                                          ctypes.byref(ustruct) if ustruct is not None else None, enc.data_ptr(),
-                                          enc_lens.data_ptr(), h0.data_ptr(), _C.ptr(c0), _C.ptr(y), sb, st, V + 1, 0,
-                                          lam, P, blob.data_ptr(), roles.data_ptr(), lm.alpha, lm.beta, c2i[BOS],
-                                          c2i[EOS], c2i[PAD], K, Lmax, poll_every, ids.data_ptr(), lens.data_ptr(),
-                                          scores.data_ptr(), ctypes.byref(rounds), ws.data_ptr(), wbytes, B, T, Hd, Cd,
-                                          V, A, _C.stream_handle()), "lr_decoder_lm_beam_search")
+    _host.launch(dev, search.__name__, search, mode, at, ctypes.byref(pstruct),
+                 ctypes.byref(ustruct) if ustruct is not None else None, enc.data_ptr(), enc_lens.data_ptr(),
+                 h0.data_ptr(), _C.ptr(c0), *middle, c2i[BOS], c2i[EOS], c2i[PAD], K, Lmax, poll_every, ids.data_ptr(),
+                 lens.data_ptr(), scores.data_ptr(), ctypes.byref(rounds), ws.data_ptr(), wbytes, B, T, Hd, Cd, V, A)
     self.beam_rounds = int(rounds.value)
     return ids, lens, scores
 

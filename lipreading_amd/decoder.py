@@ -11,11 +11,10 @@ search ctcdecode runs on CPU threads after `probs.cpu()` (decoder.py:139) runs o
 (lr_ctc_beam_decode: prefix beam search) with one device->host copy.  An ARPA `lm_path` adds ctcdecode's word
 language model (lr_ctc_beam_lm_decode; the reader is lipreading_amd/lm.py).
 """
-import math
-
 import torch
 
 from . import _C
+from . import _host
 from . import lm
 
 
@@ -90,68 +89,41 @@ class BeamCTCDecoder(Decoder):
     self.cutoff_prob = float(cutoff_prob)
     self.beam_width = int(beam_width)
     self.log_probs_input = bool(log_probs_input)
-    self.lm = None
+    self.lm = self._word_lm = None
     if lm_path is not None:
-      alpha, beta = float(alpha), float(beta)
-      if not (math.isfinite(alpha) and math.isfinite(beta)):
-        raise ValueError("alpha and beta must be finite")
-      self.alpha, self.beta = alpha, beta
-      lm.class_roles(labels, blank_index)   # the label checks come before the file is read
-      self.lm = lm.read_arpa(lm_path)
-      self._lm_blob, self._lm_roles = lm.pack(self.lm, labels, blank_index)
-      self._lm_dev = {}   # device -> (blob, roles) tensors, uploaded once per device
+      # WordLM checks the weights, then the labels, then reads, packs and (once per device) uploads the file
+      self._word_lm = lm.WordLM(lm_path, labels, alpha=alpha, beta=beta, blank_index=blank_index)
+      self.lm, self.alpha, self.beta = self._word_lm.model, self._word_lm.alpha, self._word_lm.beta
 
   def decode_ids(self, probs, sizes=None):
     """Device part: probs (B,T,C) -> (ids (B,W,T) int32, offsets (B,W,T) int32, lens (B,W) int32,
     scores (B,W) fp32 = -log P, ascending) on the GPU.  Entries past lens are -1."""
     _C.require_cuda(probs, sizes)
     L = _C.lib()
-    if probs.dtype != torch.float32:
-      probs = probs.float()
-    if probs.stride(2) != 1:
-      probs = probs.contiguous()
+    probs = _host.log_probs_3d(probs, len(self.labels), "probs")
     B, T, C = probs.shape
-    if C > len(self.labels):
-      raise KeyError("probs has %d classes but only %d labels" % (C, len(self.labels)))
     W, n = self.beam_width, self.cutoff_top_n
     dev = probs.device
     ids = torch.empty((B, W, T), dtype=torch.int32, device=dev)
     off = torch.empty((B, W, T), dtype=torch.int32, device=dev)
     lens = torch.empty((B, W), dtype=torch.int32, device=dev)
     scores = torch.empty((B, W), dtype=torch.float32, device=dev)
-    sz = None if sizes is None else sizes.to(device=dev, dtype=torch.int32).contiguous()
+    sz = _host.int32_vector(sizes, B, "sizes", device=dev)
     nbytes = L.lr_ctc_beam_workspace_bytes(B, T, C, W, n)
     if nbytes == 0:
       raise _C.LipReadingHipError("lr_ctc_beam_decode: unsupported shape B=%d T=%d C=%d beam_width=%d "
                                   "cutoff_top_n=%d" % (B, T, C, W, n))
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    if self.lm is not None:
-      if C > len(self._lm_roles):
-        raise KeyError("probs has %d classes but only %d labels" % (C, len(self._lm_roles)))
-      blob, roles = self._lm_tensors(dev)
-      _C.check(L.lr_ctc_beam_lm_decode(probs.data_ptr(), probs.stride(0), probs.stride(1), _C.ptr(sz),
-                                       int(self.log_probs_input), n, self.cutoff_prob, W, self.blank_index,
-                                       blob.data_ptr(), roles.data_ptr(), self.alpha, self.beta, ids.data_ptr(),
-                                       off.data_ptr(), lens.data_ptr(), scores.data_ptr(), ws.data_ptr(), nbytes,
-                                       B, T, C, _C.stream_handle()),
-               "lr_ctc_beam_lm_decode")
-      return ids, off, lens, scores
-    _C.check(L.lr_ctc_beam_decode(probs.data_ptr(), probs.stride(0), probs.stride(1), _C.ptr(sz),
-                                  int(self.log_probs_input), n, self.cutoff_prob, W, self.blank_index,
-                                  ids.data_ptr(), off.data_ptr(), lens.data_ptr(), scores.data_ptr(),
-                                  ws.data_ptr(), nbytes, B, T, C, _C.stream_handle()),
-             "lr_ctc_beam_decode")
+    head = (probs.data_ptr(), probs.stride(0), probs.stride(1), _C.ptr(sz), int(self.log_probs_input), n,
+            self.cutoff_prob, W, self.blank_index)
+    tail = (ids.data_ptr(), off.data_ptr(), lens.data_ptr(), scores.data_ptr(), ws.data_ptr(), nbytes, B, T, C)
+    if self._word_lm is not None:
+      blob, roles = self._word_lm.tensors(dev)
+      _host.launch(dev, "lr_ctc_beam_lm_decode", L.lr_ctc_beam_lm_decode,
+                   *head, blob.data_ptr(), roles.data_ptr(), self.alpha, self.beta, *tail)
+    else:
+      _host.launch(dev, "lr_ctc_beam_decode", L.lr_ctc_beam_decode, *head, *tail)
     return ids, off, lens, scores
-
-  def _lm_tensors(self, dev):
-    """The packed model and the class roles on `dev`: one host->device copy each, the first time."""
-    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
-    got = self._lm_dev.get(key)
-    if got is None:
-      blob = torch.from_numpy(self._lm_blob).to(dev)
-      roles = torch.tensor(self._lm_roles, dtype=torch.int32, device=dev)
-      got = self._lm_dev[key] = (blob, roles)
-    return got
 
   def decode(self, probs, sizes=None):
     """decoder.py:128-143: probs (B,T,C) -> (strings, offsets); strings[b] holds beam_width strings, best
@@ -178,35 +150,26 @@ class GreedyDecoder(Decoder):
     first = {}
     canon = [first.setdefault(c, i) for i, c in enumerate(labels)]
     self._canon = canon if canon != list(range(len(labels))) else None
-    self._canon_dev = {}
+    self._canon_dev = _host.PerDevice()   # the map, uploaded once per device
 
   def decode_ids(self, probs, sizes=None):
     """Device part: returns (ids (B,T) int32, offsets (B,T) int32, lens (B,) int32) on the GPU."""
     _C.require_cuda(probs, sizes)
     L = _C.lib()
-    if probs.dtype != torch.float32:
-      probs = probs.float()
-    if probs.stride(2) != 1:
-      probs = probs.contiguous()
+    probs = _host.log_probs_3d(probs, len(self.labels), "probs")
     B, T, C = probs.shape
-    if C > len(self.labels):
-      raise KeyError("probs has %d classes but only %d labels" % (C, len(self.labels)))
     dev = probs.device
     ids = torch.empty((B, T), dtype=torch.int32, device=dev)
     off = torch.empty((B, T), dtype=torch.int32, device=dev)
     lens = torch.empty((B,), dtype=torch.int32, device=dev)
-    sz = None if sizes is None else sizes.to(device=dev, dtype=torch.int32).contiguous()
+    sz = _host.int32_vector(sizes, B, "sizes", device=dev)
     cmap = None
     if self._canon is not None:
-      cmap = self._canon_dev.get(dev)
-      if cmap is None:
-        cmap = torch.tensor(self._canon, dtype=torch.int32, device=dev)
-        self._canon_dev[dev] = cmap
+      cmap = self._canon_dev.get(dev, lambda d: torch.tensor(self._canon, dtype=torch.int32, device=d))
     blank = self.blank_index if self._canon is None else self._canon[self.blank_index]
-    _C.check(L.lr_ctc_greedy_decode(probs.data_ptr(), probs.stride(0), probs.stride(1),
-                                    _C.ptr(sz), _C.ptr(cmap), ids.data_ptr(), off.data_ptr(),
-                                    lens.data_ptr(), B, T, C, blank, _C.stream_handle()),
-             "lr_ctc_greedy_decode")
+    _host.launch(dev, "lr_ctc_greedy_decode", L.lr_ctc_greedy_decode, probs.data_ptr(), probs.stride(0),
+                 probs.stride(1), _C.ptr(sz), _C.ptr(cmap), ids.data_ptr(), off.data_ptr(), lens.data_ptr(), B, T, C,
+                 blank)
     return ids, off, lens
 
   def decode(self, probs, sizes=None):

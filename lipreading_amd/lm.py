@@ -10,6 +10,9 @@ import gzip
 import math
 
 import numpy as np
+import torch
+
+from . import _host
 
 MAX_ORDER = 6                   # KenLM's default maximum; lr_ctc_beam_lm_pack's limit
 KENLM_MAGIC = b"mmap lm "       # the start of every KenLM binary file (lm/binary_format.cc)
@@ -224,15 +227,9 @@ class WordLM(object):
     self.alpha, self.beta = alpha, beta
     self.model = read_arpa(path)
     self.blob, self.roles = pack(self.model, self.labels, self.blank_index)
-    self._dev = {}   # device -> (blob, roles) tensors, uploaded once per device
+    self._dev = _host.PerDevice()   # (blob, roles) tensors, uploaded once per device
 
   def tensors(self, dev):
     """The packed model and the class roles on `dev`: one host->device copy each, the first time."""
-    import torch
-    dev = torch.device(dev)
-    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
-    got = self._dev.get(key)
-    if got is None:
-      got = self._dev[key] = (torch.from_numpy(self.blob).to(dev),
-                              torch.tensor(self.roles, dtype=torch.int32, device=dev))
-    return got
+    return self._dev.get(dev, lambda d: (torch.from_numpy(self.blob).to(d),
+                                         torch.tensor(self.roles, dtype=torch.int32, device=d)))

@@ -19,6 +19,7 @@ There is no host fall-back: CPU tensors raise LipReadingHipError, a shape past t
 import torch
 
 from . import _C
+from . import _host
 from .data import EOS
 
 CHARS, WORDS, CHARS_ALIGN = 0, 1, 2   # LR_EDIT_* (include/lipreading_hip.h)
@@ -56,19 +57,18 @@ class EditScorer(object):
     self.labels, self.drop = list(labels), tuple(drop)
     self.symbols, self._off, self._sym, self.space_sym, self.max_spelling = spelling_table(self.labels, self.drop)
     self.K = len(self.symbols)
-    self._dev = {}   # device -> (spell_off, spell_sym, totals, conf), uploaded / allocated once per device
-    self._last = None
+    self._dev = _host.PerDevice()   # (spell_off, spell_sym, totals, conf), uploaded / allocated once per device
+    self._last = None               # the state of the device that scored last
+
+  def _make_state(self, dev):
+    return (torch.tensor(self._off, dtype=torch.int32, device=dev),
+            torch.tensor(self._sym or [0], dtype=torch.int32, device=dev),
+            torch.zeros(16, dtype=torch.int64, device=dev),
+            torch.zeros((self.K + 1, self.K + 1), dtype=torch.int64, device=dev))
 
   def _state(self, dev):
-    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
-    got = self._dev.get(key)
-    if got is None:
-      got = self._dev[key] = (torch.tensor(self._off, dtype=torch.int32, device=dev),
-                              torch.tensor(self._sym or [0], dtype=torch.int32, device=dev),
-                              torch.zeros(16, dtype=torch.int64, device=dev),
-                              torch.zeros((self.K + 1, self.K + 1), dtype=torch.int64, device=dev))
-    self._last = key
-    return got
+    self._last = self._dev.get(dev, self._make_state)
+    return self._last
 
   @staticmethod
   def _rows(ids, what):
@@ -81,12 +81,6 @@ class EditScorer(object):
     if ids.stride(1) != 1 or ids.stride(0) < 0:
       ids = ids.contiguous()
     return ids
-
-  @staticmethod
-  def _lens(lens, B, what):
-    if lens.dim() != 1 or lens.shape[0] != B:
-      raise ValueError("%s must be (%d,), got %s" % (what, B, tuple(lens.shape)))
-    return lens if lens.dtype == torch.int32 else lens.to(torch.int32)
 
   def score(self, hyp_ids, hyp_lens, ref_ids, ref_lens, unit='char', align=False, gate=None):
     """One launch: hyp_ids (B, Wh) / ref_ids (B, Wr) integer class ids on the GPU (any row stride: `ids[:, 0]` of a
@@ -105,7 +99,9 @@ class EditScorer(object):
     B = hyp.shape[0]
     if ref.shape[0] != B:
       raise ValueError("%d hypotheses against %d references" % (B, ref.shape[0]))
-    hl, rl = self._lens(hyp_lens, B, "hyp_lens"), self._lens(ref_lens, B, "ref_lens")
+    # (the kernel takes the lengths' strides: `lens[:, 0]` of a beam search goes in as it is)
+    hl = _host.int32_vector(hyp_lens, B, "hyp_lens", strided=True)
+    rl = _host.int32_vector(ref_lens, B, "ref_lens", strided=True)
     if gate is not None and (gate.dtype != torch.int32 or gate.numel() < 1):
       raise ValueError("gate must be an int32 tensor with at least one element")
     dev = hyp.device
@@ -119,16 +115,13 @@ class EditScorer(object):
     off, sym, totals, conf = self._state(dev)
     out = torch.empty((B, len(OUT_FIELDS)), dtype=torch.int32, device=dev)
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-      _C.check(L.lr_edit_distance(hyp.data_ptr(), hyp.stride(0), hl.data_ptr(), hl.stride(0), ref.data_ptr(),
-                                  ref.stride(0), rl.data_ptr(), rl.stride(0), off.data_ptr(), sym.data_ptr(),
-                                  len(self.labels), self.max_spelling, self.space_sym, mode, out.data_ptr(),
-                                  totals.data_ptr(), conf.data_ptr(), self.K, _C.ptr(gate), ws.data_ptr(), nbytes,
-                                  B, Wh, Wr, _C.stream_handle()),
-               "lr_edit_distance")
+    _host.launch(dev, "lr_edit_distance", L.lr_edit_distance, hyp.data_ptr(), hyp.stride(0), hl.data_ptr(),
+                 hl.stride(0), ref.data_ptr(), ref.stride(0), rl.data_ptr(), rl.stride(0), off.data_ptr(),
+                 sym.data_ptr(), len(self.labels), self.max_spelling, self.space_sym, mode, out.data_ptr(),
+                 totals.data_ptr(), conf.data_ptr(), self.K, _C.ptr(gate), ws.data_ptr(), nbytes, B, Wh, Wr)
     return {name: out[:, i] for i, name in enumerate(OUT_FIELDS)}
 
-  def _key(self):
+  def _scored(self):
     if self._last is None:
       raise _C.LipReadingHipError("EditScorer: nothing was scored yet (the totals live on the GPU that scored)")
     return self._last
@@ -136,7 +129,7 @@ class EditScorer(object):
   def read(self, extra=None):
     """The one device->host read: (result dict, `extra` on the host) — `extra`, an optional int64 device vector,
     rides on the same copy."""
-    _, _, totals, _ = self._dev[self._key()]
+    _, _, totals, _ = self._scored()
     host = (totals if extra is None else torch.cat((totals, extra.to(torch.int64).reshape(-1)))).cpu()
     t = host[:16].tolist()
     c, w = dict(zip(TOTAL_FIELDS, t[:8])), dict(zip(TOTAL_FIELDS, t[8:]))
@@ -154,7 +147,7 @@ class EditScorer(object):
   def confusion(self):
     """((K+1, K+1) int64 device tensor, symbols): conf[r][h] counts reference symbol r aligned to hypothesis symbol h
     (hits on the diagonal), conf[r][K] deletions, conf[K][h] insertions, accumulated by the align=True calls."""
-    return self._dev[self._key()][3].clone(), list(self.symbols)
+    return self._scored()[3].clone(), list(self.symbols)
 
   def reset(self):
     for _, _, totals, conf in self._dev.values():

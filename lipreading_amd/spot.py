@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _C
+from . import _host
 
 BAD_ID, BAD_LENGTH = -1, -2                       # LR_SPOT_* (include/lipreading_hip.h)
 MAX_T, MAX_KW_LEN, MAX_HITS = 2048, 32, 16        # LR_SPOT_MAX_T, LR_SPOT_MAX_KW_LEN, LR_SPOT_MAX_HITS
@@ -41,10 +42,7 @@ class KeywordSpotter(object):
       raise ValueError("min_confidence must be in (0, 1], got %r" % (min_confidence,))
     self.blank_index, self.fps, self.max_hits = int(blank_index), float(fps), int(max_hits)
     self.min_confidence = None if min_confidence is None else float(min_confidence)
-    class_of = {}
-    for i, l in enumerate(self.labels):
-      if len(l) == 1 and i != self.blank_index:
-        class_of.setdefault(l, i)
+    class_of = _host.char_classes(self.labels, self.blank_index)
     self.keywords = list(keywords)
     if not self.keywords:
       raise ValueError("at least one keyword")
@@ -68,27 +66,19 @@ class KeywordSpotter(object):
     # outputs back into the caller's order
     self._order = np.argsort(self.lengths, kind="stable")
     self._sorted = bool((self._order == np.arange(K)).all())
-    self._dev = {}   # device -> (ids, lengths, min_scores, inverse order), uploaded once per device
-    self._ws = {}    # device -> the largest workspace asked for so far
+    self._dev = _host.PerDevice()   # (ids, lengths, min_scores, inverse order), uploaded once per device
+    self._ws = _host.GrowingWorkspace()
 
   def seconds(self, frame):
     return frame / self.fps
 
-  def _key(self, dev):
-    return (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
-
-  def _tables(self, dev):
-    key = self._key(dev)
-    got = self._dev.get(key)
-    if got is None:
-      o = self._order
-      inv = np.empty_like(o)
-      inv[o] = np.arange(len(o))
-      up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-      got = self._dev[key] = (up(self.ids[o]), up(self.lengths[o]),
-                              None if self.min_scores is None else up(self.min_scores[o]),
-                              None if self._sorted else up(inv.astype(np.int64)))
-    return got
+  def _upload(self, dev):
+    o = self._order
+    inv = np.empty_like(o)
+    inv[o] = np.arange(len(o))
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    return (up(self.ids[o]), up(self.lengths[o]), None if self.min_scores is None else up(self.min_scores[o]),
+            None if self._sorted else up(inv.astype(np.int64)))
 
   def spot_ids(self, log_probs, sizes=None, trace=False):
     """One launch, nothing read back: log_probs (B, T, C) fp32 on the GPU (any batch / time strides with unit class
@@ -99,16 +89,9 @@ class KeywordSpotter(object):
     one stream at a time."""
     _C.require_cuda(log_probs, sizes)
     L = _C.lib()
-    if log_probs.dim() != 3:
-      raise ValueError("log_probs must be (batch, frames, classes), got %s" % (tuple(log_probs.shape),))
-    lp = log_probs if log_probs.dtype == torch.float32 else log_probs.float()
-    if lp.stride(2) != 1 or lp.stride(0) < 0 or lp.stride(1) < 0:
-      lp = lp.contiguous()
+    lp = _host.log_probs_3d(log_probs, len(self.labels), "log_probs")
     B, T, C = lp.shape
-    if C > len(self.labels):
-      raise KeyError("log_probs has %d classes but only %d labels" % (C, len(self.labels)))
-    if sizes is not None and (sizes.dim() != 1 or sizes.shape[0] != B):
-      raise ValueError("sizes must be (%d,), got %s" % (B, tuple(sizes.shape)))
+    sz = _host.int32_vector(sizes, B, "sizes")
     K, W = self.ids.shape
     H = self.max_hits
     nbytes = L.lr_ctc_spot_workspace_bytes(B, T, C, K, W, H) if B > 0 and self.blank_index < C else 0
@@ -117,26 +100,19 @@ class KeywordSpotter(object):
                        "most %d frames, %d tokens a keyword and %d hits; at least one sample, two classes and the "
                        "blank among them)" % (B, T, C, K, W, H, self.blank_index, MAX_T, MAX_KW_LEN, MAX_HITS))
     dev = lp.device
-    sz = None if sizes is None else (sizes if sizes.dtype == torch.int32 else sizes.to(torch.int32)).contiguous()
-    ids, lens, thr, inv = self._tables(dev)
-    key = self._key(dev)
-    ws = self._ws.get(key)
-    if trace:
-      nbytes = 16   # (the trace goes straight into end_score / end_start)
-    if ws is None or ws.numel() < nbytes:
-      ws = self._ws[key] = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    ids, lens, thr, inv = self._dev.get(dev, self._upload)
+    # (the trace goes straight into end_score / end_start)
+    ws = self._ws.get(dev, 16 if trace else nbytes)
     # one int32 buffer per shape, so that putting the keywords back in order is one gather each: the scores ride along
     # bit for bit
     hit = torch.empty((3, B, K, H), dtype=torch.int32, device=dev)     # score bits, start, end
     per = torch.empty((2, B, K), dtype=torch.int32, device=dev)        # n_hits, status
     end = torch.empty((2, B, K, T), dtype=torch.int32, device=dev) if trace else None
-    with torch.cuda.device(dev):
-      _C.check(L.lr_ctc_spot(lp.data_ptr(), lp.stride(0), lp.stride(1), _C.ptr(sz), ids.data_ptr(), W, lens.data_ptr(),
-                             _C.ptr(thr), self.blank_index, H, hit[0].data_ptr(), hit[1].data_ptr(), hit[2].data_ptr(),
-                             per[0].data_ptr(), per[1].data_ptr(), end[0].data_ptr() if trace else None,
-                             end[1].data_ptr() if trace else None, ws.data_ptr(), ws.numel(), B, T, C, K,
-                             _C.stream_handle()),
-               "lr_ctc_spot")
+    _host.launch(dev, "lr_ctc_spot", L.lr_ctc_spot, lp.data_ptr(), lp.stride(0), lp.stride(1), _C.ptr(sz),
+                 ids.data_ptr(), W, lens.data_ptr(), _C.ptr(thr), self.blank_index, H, hit[0].data_ptr(),
+                 hit[1].data_ptr(), hit[2].data_ptr(), per[0].data_ptr(), per[1].data_ptr(),
+                 end[0].data_ptr() if trace else None, end[1].data_ptr() if trace else None, ws.data_ptr(), ws.numel(),
+                 B, T, C, K)
     if inv is not None:
       hit, per = hit.index_select(2, inv), per.index_select(2, inv)
       if trace:
