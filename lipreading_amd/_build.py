@@ -102,7 +102,8 @@ def build_library(force=False, verbose=False):
     for p in glob.glob(os.path.join(OBJ_DIR, "*.stamp")):
       os.remove(p)
   srcs = sources()
-  with ThreadPoolExecutor(max_workers=min(len(srcs), max(1, (os.cpu_count() or 2)))) as pool:
+  # a GPU job may use 16 CPUs, while os.cpu_count() there is the whole host's
+  with ThreadPoolExecutor(max_workers=min(len(srcs), os.cpu_count() or 2, 16)) as pool:
     objs = list(pool.map(lambda s: _compile_one(s, verbose), srcs))
   cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objs
   if verbose:

@@ -23,8 +23,8 @@ from . import _C
 from . import _host
 from . import lm
 
-INFEASIBLE, BAD_ID, BAD_LENGTH = 1, -1, -2   # LR_ALIGN_* (include/lipreading_hip.h)
-MAX_T, MAX_LABEL_LEN = 2048, 256             # LR_ALIGN_MAX_T, the label limit of lr_ctc_nll
+INFEASIBLE, BAD_ID, BAD_LENGTH = _C.LR_ALIGN_INFEASIBLE, _C.LR_ALIGN_BAD_ID, _C.LR_ALIGN_BAD_LENGTH
+MAX_T, MAX_LABEL_LEN = _C.LR_ALIGN_MAX_T, 256   # 256: the label limit of lr_ctc_nll (the header names no constant)
 
 
 class CTCAligner(object):

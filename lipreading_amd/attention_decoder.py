@@ -18,11 +18,10 @@ import torch.nn as nn
 from . import _C
 from . import _host
 from .data import BOS, EOS, PAD
-from .encoder import _RNNParams, _direct_grads, _notify
+from .encoder import _MODES, _RNNParams, _direct_grads, _notify
 
 _ALLOWED_ATTENTION_TYPES = {'none', 'dot', 'general', '1_layer_nn', 'concat'}   # better_model.py:11
 _ATT_CODE = {'none': 0, 'dot': 1, 'general': 2, '1_layer_nn': 3, 'concat': 4}
-_MODES = {'GRU': 0, 'LSTM': 1, 'RNN': 2}
 _FIELDS = ("emb", "w_ih", "w_hh", "b_ih", "b_hh", "attn_w1", "attn_b1", "attn_w2", "attn_b2", "w_c", "b_c",
            "w_o", "b_o")
 
@@ -263,7 +262,8 @@ class CharDecodingStep(nn.Module):
     self.hidden_size = encoder.hidden_size * (2 if encoder.bidirectional else 1)
     self.rnn_type = encoder.rnn_type
     self.num_layers = encoder.num_layers          # better_model.py:136
-    assert 1 <= self.num_layers <= _C.DEC_MAX_LAYERS, "the decoder stack holds up to %d layers" % _C.DEC_MAX_LAYERS
+    assert 1 <= self.num_layers <= _C.LR_DEC_MAX_LAYERS, \
+        "the decoder stack holds up to %d layers" % _C.LR_DEC_MAX_LAYERS
     self.rnn_dropout = rnn_dropout
     self.char_dim = char_dim
     self.vocab_size = vocab_size

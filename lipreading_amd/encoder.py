@@ -20,10 +20,14 @@ from .data import BOS, PAD
 
 _ALLOWED_RNN_TYPES = {'LSTM', 'GRU', 'RNN'}          # better_model.py:9
 _ALLOWED_FRAME_PROCESSING = {'flatten'}              # better_model.py:10
-_MODES = {'GRU': 0, 'LSTM': 1, 'RNN': 2}
-_PROJ_BF16X3, _INPUT_BF16_EXACT, _INPUT_STORED_BF16, _RECUR_SPLIT = 0x100, 0x200, 0x800, 0x1000   # lr_rnn_mode flags
-_PROJ_BF16X1 = 0x2000
+_MODES = {'GRU': _C.LR_RNN_GRU, 'LSTM': _C.LR_RNN_LSTM, 'RNN': _C.LR_RNN_TANH}
+_PROJ_BF16X3, _PROJ_BF16X1, _RECUR_SPLIT = _C.LR_RNN_PROJ_BF16X3, _C.LR_RNN_PROJ_BF16X1, _C.LR_RNN_RECUR_SPLIT   # flags
+_INPUT_BF16_EXACT, _INPUT_STORED_BF16 = _C.LR_RNN_INPUT_BF16_EXACT, _C.LR_RNN_INPUT_STORED_BF16
 _GATES = {'GRU': 3, 'LSTM': 4, 'RNN': 1}
+
+
+def _is_lstm(mode):
+  return (mode & _C.LR_RNN_CELL_MASK) == _C.LR_RNN_LSTM
 
 
 def _ptr_array(tensors):
@@ -144,7 +148,7 @@ class _RNNLayerFunction(torch.autograd.Function):
     y = torch.empty((B, T, D * H), dtype=torch.float32, device=dev)
     # need_state False: the final states are not extracted (h_n == NULL; the CTC-only step never reads them)
     h_n = torch.empty((D, B, H) if need_state else (0,), dtype=torch.float32, device=dev)
-    c_n = torch.empty((D, B, H), dtype=torch.float32, device=dev) if ((mode & 0xff) == 1 and need_state) else None
+    c_n = torch.empty((D, B, H), dtype=torch.float32, device=dev) if (_is_lstm(mode) and need_state) else None
     rbytes = L.lr_rnn_reserve_bytes(mode, B, T, I, H, D)
     reserve = torch.empty(rbytes, dtype=torch.uint8, device=dev)
     _C.check(L.lr_rnn_layer_forward(mode, x.data_ptr(), lens.data_ptr(), _ptr_array(w_ih),
@@ -173,7 +177,7 @@ class _RNNLayerFunction(torch.autograd.Function):
     b_ih, b_hh = list(weights[2::4]), list(weights[3::4])
     dy = dy.contiguous() if dy is not None else torch.zeros_like(y)
     dh_n = dh_n.contiguous() if dh_n is not None else None
-    dc_n = dc_n.contiguous() if ((mode & 0xff) == 1 and dc_n is not None) else None
+    dc_n = dc_n.contiguous() if (_is_lstm(mode) and dc_n is not None) else None
     direct = _direct_grads(weights)
     grads = [w.grad for w in weights] if direct else [torch.empty_like(w) for w in weights]
     dx = torch.empty_like(x) if need_dx else None

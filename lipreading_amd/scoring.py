@@ -22,7 +22,7 @@ from . import _C
 from . import _host
 from .data import EOS
 
-CHARS, WORDS, CHARS_ALIGN = 0, 1, 2   # LR_EDIT_* (include/lipreading_hip.h)
+CHARS, WORDS, CHARS_ALIGN = _C.LR_EDIT_CHARS, _C.LR_EDIT_WORDS, _C.LR_EDIT_CHARS_ALIGN
 OUT_FIELDS = ("status", "distance", "ref_len", "hyp_len", "hits", "sub", "ins", "dele")
 TOTAL_FIELDS = ("distance", "ref_len", "hyp_len", "hits", "sub", "ins", "dele", "pairs")
 

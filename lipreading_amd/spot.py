@@ -23,8 +23,8 @@ import torch
 from . import _C
 from . import _host
 
-BAD_ID, BAD_LENGTH = -1, -2                       # LR_SPOT_* (include/lipreading_hip.h)
-MAX_T, MAX_KW_LEN, MAX_HITS = 2048, 32, 16        # LR_SPOT_MAX_T, LR_SPOT_MAX_KW_LEN, LR_SPOT_MAX_HITS
+BAD_ID, BAD_LENGTH = _C.LR_SPOT_BAD_ID, _C.LR_SPOT_BAD_LENGTH
+MAX_T, MAX_KW_LEN, MAX_HITS = _C.LR_SPOT_MAX_T, _C.LR_SPOT_MAX_KW_LEN, _C.LR_SPOT_MAX_HITS
 
 
 class KeywordSpotter(object):

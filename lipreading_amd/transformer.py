@@ -29,7 +29,8 @@ from .data import BOS, PAD
 from .encoder import _ProjLogSoftmaxFunction, _direct_grads, _notify, _ptr_array
 
 
-_X3, _X_BF16, _DX_BF16, _ATTN_FUSED, _ROWBLOCK = 1, 2, 4, 8, 16   # LR_TFM_* (include/lipreading_hip.h)
+_X3, _X_BF16, _DX_BF16 = _C.LR_TFM_X3, _C.LR_TFM_X_BF16, _C.LR_TFM_DX_BF16
+_ATTN_FUSED, _ROWBLOCK = _C.LR_TFM_ATTN_FUSED, _C.LR_TFM_ROWBLOCK
 
 # test hook: False keeps the row-wise half of a layer as five launches per direction (lr_fgemm products + LayerNorm)
 rowblock_layers = True
