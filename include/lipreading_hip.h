@@ -195,6 +195,42 @@ int lr_lip_crop_collate_aug_u8(const void* frames, const float* lmk, const int64
 int lr_collate_pad_aug_f32(const float* packed, const int64_t* offsets, const int32_t* lens, const int32_t* tmap,
                            float* out, int B, int t_max, int feat, lr_stream_t stream);
 
+/* ---- A9, stabilised: mouth crops of fixed scale, roll-corrected, smoothed over time (BUILD-DEFINED) ---------- */
+
+/* lr_lip_crop_collate_aug_u8's batch with another window rule.  The box rule cuts the bounding box of the mouth points
+ * of one frame: its scale follows the mouth's opening, it shakes with the landmark noise and it keeps the head's roll.
+ * Here scale and roll come from the EYES, which do not move with speech, the centre is the mouth points' MEAN, and all
+ * of it is averaged over 2*radius+1 neighbouring frames of the same sample.
+ *   pose of row n (four fp32):  mx, my = mean of x, y over landmarks [lo,hi);  (ax, ay) = mean over [eb_lo,eb_hi)
+ *     minus mean over [ea_lo,ea_hi) (one fp32 subtraction each).  Every mean is a float64 sum in ascending index,
+ *     divided in float64 by the count, rounded once to fp32.
+ *   smoothed pose of row n = row i of a sample of len rows: each component's float64 sum over rows
+ *     max(0,i-radius) .. min(len-1,i+radius) in ascending order / count, rounded once to fp32 (radius 0: the raw pose).
+ *     The window never leaves the sample, whatever t_max is.
+ *   window, all fp32, every a + b*c one fmaf, (dx,dy,zoom,flip) = clip_aug[b] or (0,0,1,0) when clip_aug is NULL:
+ *     d = sqrtf(fmaf(ay,ay,ax*ax));  if !(extent*d*zoom >= 2) { ax = 2/(extent*zoom); ay = 0; }   (the 2-pixel minimum)
+ *     ex = extent*ax, ey = extent*ay;  cx = fmaf(-dy,ey,fmaf(dx,ex,mx));  cy = fmaf(dy,ex,fmaf(dx,ey,my));
+ *     ux = (ex*zoom)/S, uy = (ey*zoom)/S     — the side is `extent` eye distances, the shift is in units of the
+ *     un-zoomed side along the window's own axes.
+ *   output pixel (oy,ox): px = (ox+0.5f) - 0.5f*S, py likewise;  sx = fmaf(-py,uy,fmaf(px,ux,cx)) - 0.5f,
+ *     sy = fmaf(py,ux,fmaf(px,uy,cy)) - 0.5f;  from there lr_lip_crop_u8's arithmetic (clamp to the frame, floor, three
+ *     fmaf lerps, round to nearest).  flip != 0: output column S-1-ox shows what column ox would.
+ * Batch semantics are lr_lip_crop_collate_aug_u8's: tmap NULL means tmap[offsets[b]+t] = t; zeros for
+ * t >= min(lens[b], t_max) and for a map value < 0; the source row is offsets[b] + min(map value, lens[b]-1) and the
+ * pose is that SOURCE row's, smoothed over its source neighbours; EVERY byte of out is written; out need not be 16-byte
+ * aligned.  clip_aug and tmap are both NULL or both given.  NaN landmarks give unspecified pixels, never a read
+ * outside the frame.
+ *   pose      f32 [rows][4] or NULL: the smoothed (mx, my, ax, ay) of every row of every sample
+ *   workspace lr_lip_stable_workspace_bytes(rows, radius) bytes, 16-byte aligned (LR_ERR_WORKSPACE when too small)
+ * Two launches: the poses of all rows (one workgroup per sample), then the pixels. */
+#define LR_LIP_STABLE_MAX_RADIUS 32
+size_t lr_lip_stable_workspace_bytes(int64_t rows, int radius); /* 0 for arguments it rejects */
+int lr_lip_stable_collate_u8(const void* frames, const float* lmk, const int64_t* offsets, const int32_t* lens,
+                             const float* clip_aug, const int32_t* tmap, void* out, float* pose, void* workspace,
+                             size_t workspace_bytes, int B, int64_t rows, int t_max, int H, int W, int S, int npts,
+                             int lo, int hi, int ea_lo, int ea_hi, int eb_lo, int eb_hi, float extent, int radius,
+                             lr_stream_t stream);
+
 /* ---- dense fp32 contraction (MFMA f32 16x16x4 / 32x32x2), used by A3 ------------------- */
 
 /* C[M,N] = alpha * op(A)[M,K] * op(B)[K,N] + beta * C + bias[N]   (row-major, fp32)

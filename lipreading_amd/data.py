@@ -76,15 +76,28 @@ def make_collate_fn(device):
   return _collate_fn
 
 
-def make_pixel_collate_fn(device, size=96, margin=0.3):
+CROPS = ("box", "stable")
+
+
+def check_crop(crop):
+  if crop not in CROPS:
+    raise ValueError("crop must be box or stable, got %r" % (crop,))
+  return crop
+
+
+def make_pixel_collate_fn(device, size=96, margin=0.3, crop="box", extent=1.25, radius=2):
   """BUILD-DEFINED (the pixel regime of BASELINE configs[1]/[4]; the reference has no pixel path): batch =
   [((frames u8 (len,3,H,W), landmarks (len,68,3) in those frames' pixels), caption (n,))] ->
   (clips u8 (B,Tmax,3,size,size), frame_lens i64, chars i64 (B,Cmax) PAD=0, char_lens i64) — the tuple train() /
   eval() / greedy_cer take, with mouth-crop clips where the landmark regime has landmarks.  Frames and landmarks
   are uploaded ragged, back to back; every sample's frames are cropped about their own mouth landmarks and
   resampled to size x size straight into their rows of the zero-padded batch (lr_lip_crop_u8, landmarks.lip_crop's
-  arithmetic); chars and both lengths stay on the host like make_collate_fn's."""
-  from .landmarks import _mouth
+  arithmetic); chars and both lengths stay on the host like make_collate_fn's.
+  crop="stable": the stabilised, roll-corrected window of landmarks.lip_crop_stable (`extent` eye distances wide,
+  smoothed over 2*radius+1 frames of the sample) in place of the per-frame bounding box, and ONE call of
+  lr_lip_stable_collate_u8 on the ragged upload in place of a launch per sample; `margin` is then unused."""
+  from .landmarks import _mouth, stable_crop_collate
+  check_crop(crop)
   dev = torch.device(device)
   if dev.type != "cuda":
     raise _C.LipReadingHipError("collation runs on the MI355X only (no CPU fallback)")
@@ -101,16 +114,23 @@ def make_pixel_collate_fn(device, size=96, margin=0.3):
     B, t_max = len(pix), int(lens.max())
     frames_d = torch.from_numpy(np.concatenate(pix, axis=0)).to(dev, non_blocking=True)
     lmk_d = torch.from_numpy(np.concatenate(lmk, axis=0)).to(dev, non_blocking=True)
-    clips = torch.zeros((B, t_max, 3, size, size), dtype=torch.uint8, device=dev)
-    L = _C.lib()
-    off = 0
-    with torch.cuda.device(dev):
-      for b in range(B):
-        n = int(lens[b])
-        _C.check(L.lr_lip_crop_u8(frames_d[off:off + n].data_ptr(), lmk_d[off:off + n].data_ptr(), clips[b].data_ptr(),
-                                  n, H, W, size, 68, _mouth.start, _mouth.stop, float(margin), _C.stream_handle()),
-                 "lr_lip_crop_u8")
-        off += n
+    if crop == "stable":
+      offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+      off_d = torch.from_numpy(offsets).to(dev, non_blocking=True)
+      lens_d = torch.from_numpy(lens.astype(np.int32)).to(dev, non_blocking=True)
+      with torch.cuda.device(dev):
+        clips = stable_crop_collate(frames_d, lmk_d, off_d, lens_d, t_max, size, extent, radius)
+    else:
+      clips = torch.zeros((B, t_max, 3, size, size), dtype=torch.uint8, device=dev)
+      L = _C.lib()
+      off = 0
+      with torch.cuda.device(dev):
+        for b in range(B):
+          n = int(lens[b])
+          _C.check(L.lr_lip_crop_u8(frames_d[off:off + n].data_ptr(), lmk_d[off:off + n].data_ptr(),
+                                    clips[b].data_ptr(), n, H, W, size, 68, _mouth.start, _mouth.stop, float(margin),
+                                    _C.stream_handle()), "lr_lip_crop_u8")
+          off += n
     caps = [np.asarray(c, dtype=np.int64) for c in captions]
     tgt_lens = torch.tensor([len(c) for c in caps], dtype=torch.long)
     tgt = torch.zeros((len(caps), int(tgt_lens.max())), dtype=torch.long)

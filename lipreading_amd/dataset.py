@@ -256,7 +256,8 @@ class BatchLoader(object):
 
 def make_loader(dataset, batch_size, collate_fn, prefetch=0, augment=None, **loader_args):
   """prefetch=0: the plain BatchLoader over `collate_fn`.  prefetch=N > 0: a loader.PrefetchLoader of depth N that
-  yields the same batches (loader_args: device, pixels, size, margin, workers — what `collate_fn` was made with).
+  yields the same batches (loader_args: device, pixels, size, margin, workers, crop, extent, radius — what `collate_fn`
+  was made with).
   augment: an augment.AugmentSpec for a TRAINING loader; it is applied inside the prefetch loader's collate launch,
   so it needs prefetch > 0."""
   if augment is not None and not prefetch:

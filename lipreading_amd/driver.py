@@ -58,6 +58,11 @@ DEFAULTS = dict(  # train.py:134-167
     # loader only (augment.AugmentSpec; applied inside the prefetch loader's collate launch, so it needs --prefetch);
     # the per-epoch Train CER is scored on clean clips.  --augment_seed: the stream of draws (None = --seed)
     augment="", augment_seed=None,
+    # --crop=box|stable: the mouth window of the pixel regime, for the train, validation and test loaders alike (a model
+    # is evaluated on the crops it was trained on).  box: the bounding box of each frame's mouth points
+    # (lr_lip_crop_u8).  stable: centre = the mouth points' mean, side = --crop_extent eye distances, axes along the
+    # line between the eyes, all averaged over 2 * --crop_smooth + 1 frames (lr_lip_stable_collate_u8)
+    crop="box", crop_extent=1.25, crop_smooth=2,
     # who scores the transcripts behind the edit-distance errors (greedy, --ctc_decoder=beam, --attn_decode=beam|joint):
     # host (the Python loops of train.greedy_cer / ctc_cer / attention_cer) or device (train.device_scores: the ids
     # never leave the GPU, lr_edit_distance scores them, one read per loader; the epoch summary then carries val_wer)
@@ -169,6 +174,7 @@ def parse_flags(argv, defaults=DEFAULTS):
       if name not in explicit:
         out[name] = True
   augment_spec(out)
+  crop_check(out)
   align_check(out)
   spot_check(out)
   return out
@@ -183,6 +189,20 @@ def augment_spec(f):
   if spec is not None and not f.get("prefetch"):
     raise ValueError("--augment=%s needs --prefetch=N > 0 (got --prefetch=%r)" % (f["augment"], f.get("prefetch")))
   return spec
+
+
+def crop_check(f):
+  """ValueError for a --crop that is neither box nor stable, and for a window --crop=stable cannot cut."""
+  crop = f.get("crop", "box")
+  if crop not in ("box", "stable"):
+    raise ValueError("--crop must be box or stable (got --crop=%r)" % (crop,))
+  if crop == "stable":
+    extent, smooth = f.get("crop_extent"), f.get("crop_smooth")
+    if not (isinstance(extent, float) and 0.0 < extent < float("inf")):
+      raise ValueError("--crop_extent must be a positive number (got %r)" % (extent,))
+    if not (isinstance(smooth, int) and 0 <= smooth <= 32):
+      raise ValueError("--crop_smooth must be in [0, 32] frames (got %r)" % (smooth,))
+  return crop
 
 
 def align_check(f):
@@ -389,6 +409,7 @@ def run(**flags):
   f = dict(DEFAULTS)
   f.update(flags)
   augment = augment_spec(f)
+  crop_check(f)
   if f["frontend"] != "none" or f["encoder"] != "rnn":
     # the build-defined regimes are encoder + CTC with greedy CER (parse_flags sets the same for flag files)
     f["enable_ctc"], f["ctc_only"] = flags.get("enable_ctc", True), flags.get("ctc_only", True)
@@ -411,12 +432,17 @@ def run(**flags):
   if pixels:
     # u8 frames + landmarks -> mouth crops (B, Tmax, 3, S, S) on the GPU (lr_lip_crop_u8)
     from .data import make_pixel_collate_fn
-    collate = make_pixel_collate_fn(device, size=f["crop_size"])
+    collate = make_pixel_collate_fn(device, size=f["crop_size"], crop=f["crop"], extent=f["crop_extent"],
+                                    radius=f["crop_smooth"])
+    if f["crop"] != "box":
+      print("Mouth crops: %s (extent %g eye distances, smoothed over %d frames)" %
+            (f["crop"], f["crop_extent"], 2 * f["crop_smooth"] + 1))
   else:
     collate = make_collate_fn(device)   # padded on the GPU (lr_collate_pad_f32); lengths stay on the host
-  # only the train loader is augmented; validation and test clips are served as they are
+  # only the train loader is augmented; validation and test clips are served as they are.  The crop is one for all three
   train_loader, val_loader, test_loader = (make_loader(d, f["batch_size"], collate, prefetch=f["prefetch"], device=device,
-                                                       pixels=pixels, size=f["crop_size"],
+                                                       pixels=pixels, size=f["crop_size"], crop=f["crop"],
+                                                       extent=f["crop_extent"], radius=f["crop_smooth"],
                                                        augment=augment if d is sets[0] else None) for d in sets)
   if augment is not None:
     print("Augmenting the training clips: %s (seed %d)" % (augment, augment.seed))

@@ -133,3 +133,48 @@ def lip_crop(frames, lmks, size=96, margin=0.3, mouth=_mouth):
                                    mouth.start, mouth.stop, float(margin), _C.stream_handle()),
            "lr_lip_crop_u8")
   return out
+
+
+_eyes = (slice(36, 42), slice(42, 48))  # the 68-point scheme's two eye contours
+
+
+def stable_crop_collate(frames, lmks, offsets, lens, t_max, size, extent, radius, clip_aug=None, tmap=None,
+                        mouth=_mouth, eyes=_eyes, pose=None, workspace=None):
+  """lr_lip_stable_collate_u8 on device tensors: ragged frames u8 (rows,3,H,W), landmarks f32 (rows,npts,3), offsets
+  i64 (B,), lens i32 (B,) -> the padded batch u8 (B,t_max,3,size,size) in ONE call.  clip_aug f32 (B,4) and tmap i32
+  (rows,): both or neither.  pose: an f32 (rows,4) tensor to receive the smoothed poses.  workspace: a u8 tensor of
+  lr_lip_stable_workspace_bytes(rows, radius) bytes (allocated when None)."""
+  L = _C.lib()
+  rows, _, H, W = frames.shape
+  B = offsets.shape[0]
+  need = L.lr_lip_stable_workspace_bytes(rows, int(radius))
+  if workspace is None:
+    workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=frames.device)
+  out = torch.empty((B, int(t_max), 3, size, size), dtype=torch.uint8, device=frames.device)
+  _C.check(L.lr_lip_stable_collate_u8(frames.data_ptr(), lmks.data_ptr(), offsets.data_ptr(), lens.data_ptr(),
+                                      _C.ptr(clip_aug), _C.ptr(tmap), out.data_ptr(), _C.ptr(pose),
+                                      workspace.data_ptr(), workspace.numel(), B, rows, int(t_max), H, W, int(size),
+                                      lmks.shape[1], mouth.start, mouth.stop, eyes[0].start, eyes[0].stop,
+                                      eyes[1].start, eyes[1].stop, float(extent), int(radius), _C.stream_handle()),
+           "lr_lip_stable_collate_u8")
+  return out
+
+
+def lip_crop_stable(frames, lmks, size=96, extent=1.25, radius=2, mouth=_mouth, eyes=_eyes, return_pose=False):
+  """BUILD-DEFINED, the stabilised counterpart of `lip_crop` (include/lipreading_hip.h, "A9, stabilised"): the n rows
+  are ONE clip.  The window's centre is the mean of landmarks `mouth`, its side `extent` times the distance between
+  the means of the two `eyes` ranges, its axes follow the line between them (roll correction), and all of it is
+  averaged over the 2*radius+1 neighbouring frames.  frames (n,3,H,W) uint8 + landmarks (n,68,3) in image pixels ->
+  (n,3,size,size) uint8; with return_pose also the smoothed pose (n,4) float32 = (mx, my, ax, ay)."""
+  _C.require_cuda(frames, lmks)
+  assert frames.dim() == 4 and frames.shape[1] == 3 and frames.dtype == torch.uint8
+  assert lmks.dim() == 3 and lmks.shape[2] == 3 and lmks.shape[0] == frames.shape[0]
+  f = frames.contiguous()
+  l = lmks.to(torch.float32).contiguous()
+  n = f.shape[0]
+  offsets = torch.zeros(1, dtype=torch.int64, device=f.device)
+  lens = torch.full((1,), n, dtype=torch.int32, device=f.device)
+  pose = torch.empty((n, 4), dtype=torch.float32, device=f.device) if return_pose else None
+  with torch.cuda.device(f.device):
+    out = stable_crop_collate(f, l, offsets, lens, n, size, extent, radius, mouth=mouth, eyes=eyes, pose=pose)[0]
+  return (out, pose) if return_pose else out

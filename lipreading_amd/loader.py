@@ -11,6 +11,9 @@ stream and off the step's critical path:
                 own stream, collates it there in ONE launch (lr_lip_crop_collate_u8 / lr_collate_pad_f32) and records
                 an event; the consumer's stream waits on that event (no host synchronisation).
 
+With `crop="stable"` the pixel launch is lr_lip_stable_collate_u8 (the stabilised, roll-corrected window of
+landmarks.lip_crop_stable), augmented or not; its workspace lies behind the slot's device bytes.
+
 With `augment=AugmentSpec(...)` (augment.py) a worker also draws the batch's augmentation records into the slot — they
 ride the same upload — and the one launch is lr_lip_crop_collate_aug_u8 / lr_collate_pad_aug_f32, which applies them.
 Lengths, labels, batch order and batch shapes are those of the un-augmented loader; `plain()` iterates the same
@@ -197,6 +200,20 @@ def _slot_bytes(dataset, plan, pixels, augment=False):
         continue
     most = max(most, _align(a) + _align(b) + _align((hi - lo) * 8) + _align((hi - lo) * 4) +
                (_aug_bytes(hi - lo, rows, pixels) if augment else 0))
+  return most
+
+
+def _max_rows(dataset, plan):
+  """Frames of the largest pixel batch (sizes only, as _slot_bytes)."""
+  most = 1
+  for lo, hi in plan:
+    rows = 0
+    for i in range(lo, hi):
+      try:
+        rows += len(dataset[i][0][0])
+      except Exception:     # a malformed sample: its batch raises when it is packed
+        continue
+    most = max(most, rows)
   return most
 
 
@@ -399,7 +416,9 @@ class PrefetchLoader(object):
   PAD=0, char_lens i64), the last three on the host (pinned).  Re-iterable; one pass at a time."""
 
   def __init__(self, dataset, batch_size, device, pixels=False, size=96, margin=0.3, depth=2, workers=2, alloc=None,
-               augment=None):
+               augment=None, crop="box", extent=1.25, radius=2):
+    from .data import check_crop
+    check_crop(crop)
     dev = torch.device(device)
     if dev.type != "cuda":
       raise _C.LipReadingHipError("collation runs on the MI355X only (no CPU fallback)")
@@ -407,6 +426,7 @@ class PrefetchLoader(object):
       dev = torch.device("cuda", torch.cuda.current_device())
     self.dataset, self.batch_size, self.device = dataset, int(batch_size), dev
     self.pixels, self.size, self.margin = bool(pixels), int(size), float(margin)
+    self.crop, self.extent, self.radius = crop, float(extent), int(radius)
     self.depth = int(depth)
     self._pinned = alloc is None
     self.augment = augment
@@ -415,10 +435,17 @@ class PrefetchLoader(object):
     with torch.cuda.device(dev):
       self._copy = torch.cuda.Stream(dev)
       # ragged device staging, one per slot: rewritten only by a later upload on the same stream
-      self._stage = [torch.empty(self.host.slot_bytes, dtype=torch.uint8, device=dev) for _ in self.host.slots]
+      # crop="stable": the poses' workspace lies behind the slot's bytes, so no batch allocates one
+      self._work_bytes = 0
+      if self.pixels and crop == "stable":
+        self._work_bytes = int(_C.lib().lr_lip_stable_workspace_bytes(_max_rows(dataset, self.host.plan), self.radius))
+        if not self._work_bytes:
+          raise _C.LipReadingHipError("lr_lip_stable_workspace_bytes rejects radius=%r" % (radius,))
+      self._stage = [torch.empty(self.host.slot_bytes + self._work_bytes, dtype=torch.uint8, device=dev)
+                     for _ in self.host.slots]
     self._pending = [None] * len(self.host.slots)    # the event behind the last upload out of each slot
-    from .landmarks import _mouth
-    self._mouth = _mouth
+    from .landmarks import _eyes, _mouth
+    self._mouth, self._eyes = _mouth, _eyes
 
   def __len__(self):
     return len(self.host)
@@ -446,7 +473,16 @@ class PrefetchLoader(object):
       stage = self._stage[slot]
       stage[:pb.nbytes].copy_(self.host.slots[slot][:pb.nbytes], non_blocking=True)    # the batch's ONE upload
       base, s = stage.data_ptr(), self._copy.cuda_stream
-      if self.pixels and pb.augmented:
+      if self.pixels and self.crop == "stable":
+        out = torch.empty((pb.B, pb.t_max, 3, self.size, self.size), dtype=torch.uint8, device=dev)
+        aug = (base + pb.aug_off, base + pb.tmap_off) if pb.augmented else (None, None)
+        (ea, eb), work = self._eyes, self.host.slot_bytes     # slot_bytes is a multiple of 256
+        _C.check(L.lr_lip_stable_collate_u8(base + pb.frames_off, base + pb.lmk_off, base + pb.offsets_off,
+                                            base + pb.lens_off, aug[0], aug[1], out.data_ptr(), None, base + work,
+                                            self._work_bytes, pb.B, pb.rows, pb.t_max, pb.H, pb.W, self.size, 68,
+                                            self._mouth.start, self._mouth.stop, ea.start, ea.stop, eb.start, eb.stop,
+                                            self.extent, self.radius, s), "lr_lip_stable_collate_u8")
+      elif self.pixels and pb.augmented:
         out = torch.empty((pb.B, pb.t_max, 3, self.size, self.size), dtype=torch.uint8, device=dev)
         _C.check(L.lr_lip_crop_collate_aug_u8(base + pb.frames_off, base + pb.lmk_off, base + pb.offsets_off,
                                               base + pb.lens_off, base + pb.aug_off, base + pb.tmap_off, out.data_ptr(),
