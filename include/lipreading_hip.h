@@ -1030,6 +1030,84 @@ int lr_ctc_spot(const float* log_probs, int64_t stride_b, int64_t stride_t, cons
                 float* end_score, int32_t* end_start, void* workspace, size_t workspace_bytes, int B, int T, int C, int K,
                 lr_stream_t stream);
 
+/* ---- A6g (BUILD-DEFINED, no reference symbol): CTC segmentation — re-time a whole video's captions -------------- */
+/* The reference has no segmenter; the specification is this build's (lipreading_amd/csrc/lr_segment.hip, DESIGN.md
+ * §24, after Kuerzinger et al. 2020), the yardstick a NumPy restatement kept with the tests (tests/segment_cases.py).
+ * Per sample b: n = sizes[b] frames of fp32 log-probabilities, a target y[0..L) of class ids (L = target_lens[b], blank
+ * excluded) and utterances u = 0..U-1 (U = n_utts[b]), each the token range [utt_first[u], utt_first[u] +
+ * utt_count[u]) of the target; ranges may leave tokens unowned, may be empty and need not be ordered.  States as A6e:
+ * s = 0..2L, even = blank, odd s = y[(s-1)/2].  Before frame 0 every v is -inf.  For t = 0..n-1 and every s, `best` is
+ * chosen among stay v[t-1][s] (code 0), step v[t-1][s-1] (code 1, s >= 1), skip v[t-1][s-2] (code 2; s odd, s >= 3,
+ * cls(s) != cls(s-2)) and the fresh start 0.0f (code 3; s <= 1 and (t == 0 or LR_SEG_FREE_START)) IN THIS ORDER, a
+ * later candidate replacing an earlier one only if strictly greater; v[t][s] = best + lp[t][cls(s)] (one fp32 add) and
+ * the code goes into the 2-bit table.  With LR_SEG_FREE_START clear this is A6e's recursion (0.0f + x == x).
+ * End: the candidates of frame t are v[t][2L-1] then v[t][2L] (L == 0: v[t][0] alone), over t = 0..n-1 ascending with
+ * LR_SEG_FREE_END, t = n-1 alone without, the same strictly-greater rule; total = the chosen value.  The walk back
+ * follows the codes and stops after the frame whose code is 3, or at frame 0.
+ *   log_probs    element (b,t,c) at log_probs[b*stride_b + t*stride_t + c]; frames t >= n are never read; NaN is
+ *                unspecified but stays in bounds
+ *   sizes        [B] int32 or NULL (= T);  targets [B][target_stride] int32, ids past target_lens[b] are never read
+ *   utt_first / utt_count  [B][utt_stride] int32, n_utts [B] int32; all three (and the utt_* outputs) may be NULL:
+ *                no utterance outputs
+ *   flags        LR_SEG_FREE_START | LR_SEG_FREE_END
+ *   span         [B][2]: {first frame of the path, one past its last}
+ *   frame_token  [B][T]: the token of an odd state on the path, -1 on blank frames, outside the span and for t >= n
+ *   tok_start / tok_end / tok_logp  [B][target_stride]: as A6e (contiguous frames, fp32 sum in ascending t)
+ *   utt_start / utt_end / utt_frames / utt_logp / utt_worst  [B][utt_stride]: tok_start[first], tok_end[last], the
+ *                int32 sum of tok_end - tok_start over its tokens, the fp32 sum of their tok_logp in token order, the
+ *                target index of its token with the smallest tok_logp (the first on ties).  An empty utterance and
+ *                entries past U get -1, -1, 0, 0.0f, -1.
+ *   total        [B] fp32;  status [B], judged in this order: LR_SEG_BAD_LENGTH (sizes[b] outside [1, T], target_lens[b]
+ *                outside [0, target_stride] or n_utts[b] outside [0, utt_stride]), LR_SEG_BAD_ID (an id inside its
+ *                length outside [0, C) or equal to blank), LR_SEG_BAD_UTTERANCE (a negative first or count, or first +
+ *                count > L), LR_SEG_INFEASIBLE (total is -inf), else 0.
+ * Entries past L are -1 (integers) and 0 (floats).  A sample with a non-zero status reads nothing out of bounds and
+ * writes -1 / 0 everywhere (span included) and total = -inf.
+ * Limits, from the arguments alone: T <= LR_SEG_MAX_T, target_stride <= max_tokens <= LR_SEG_MAX_TOKENS, B <=
+ * LR_SEG_MAX_B (a sample is a row of the launch grids), C >= 2, else
+ * LR_ERR_UNSUPPORTED / LR_ERR_INVALID_ARG before any launch.  One prepare launch, ceil(T / frames per launch) forward
+ * launches whose order on `stream` is the only order between state tiles, one walk-back launch, three span launches. */
+#define LR_SEG_MAX_T 65536
+#define LR_SEG_MAX_TOKENS 16384
+#define LR_SEG_MAX_B 65535
+#define LR_SEG_FREE_START 1
+#define LR_SEG_FREE_END 2
+#define LR_SEG_INFEASIBLE 1
+#define LR_SEG_BAD_ID (-1)
+#define LR_SEG_BAD_LENGTH (-2)
+#define LR_SEG_BAD_UTTERANCE (-3)
+
+/* Workspace lr_ctc_segment needs; 0 for arguments it rejects.  With S = 2 * max_tokens + 1 rounded up to a multiple of
+ * the states a workgroup owns (plan[0]): B * ((ceil(T / 16) + 2) * S * 4 + 64) bytes — the 2-bit table, 16 steps per
+ * dword, the two value rows between forward launches and the sample's end record.  Past 4 GB at the limits. */
+size_t lr_ctc_segment_workspace_bytes(int B, int T, int C, int max_tokens);
+
+/* What lr_ctc_segment will launch for these sizes, decided on the host (no device call): plan [LR_SEG_PLAN_WORDS] int32
+ * on the HOST = {states a workgroup owns, frames one forward launch advances, forward launches, workgroups per forward
+ * launch, threads per workgroup, dynamic LDS bytes}.  Same status as lr_ctc_segment would give for the sizes. */
+#define LR_SEG_PLAN_WORDS 6
+int lr_ctc_segment_plan(int B, int T, int C, int max_tokens, int32_t* plan);
+
+int lr_ctc_segment(const float* log_probs, int64_t stride_b, int64_t stride_t, const int32_t* sizes,
+                   const int32_t* targets, int target_stride, const int32_t* target_lens, const int32_t* utt_first,
+                   const int32_t* utt_count, int utt_stride, const int32_t* n_utts, int blank, int flags,
+                   int32_t* frame_token, int32_t* tok_start, int32_t* tok_end, float* tok_logp, int32_t* utt_start,
+                   int32_t* utt_end, int32_t* utt_frames, float* utt_logp, int32_t* utt_worst, int32_t* span,
+                   float* total, int32_t* status, void* workspace, size_t workspace_bytes, int B, int T, int C,
+                   int max_tokens, lr_stream_t stream);
+
+/* lr_ctc_segment with its phases timed (tools/bench_segment.py): the same launches with device events between them,
+ * then a wait for the last one — the one entry of A6g that synchronises.  phase_ms [3] fp32 on the HOST = milliseconds
+ * of {the forward launches, the walk back, the span launches}. */
+int lr_ctc_segment_phases(const float* log_probs, int64_t stride_b, int64_t stride_t, const int32_t* sizes,
+                          const int32_t* targets, int target_stride, const int32_t* target_lens,
+                          const int32_t* utt_first, const int32_t* utt_count, int utt_stride, const int32_t* n_utts,
+                          int blank, int flags, int32_t* frame_token, int32_t* tok_start, int32_t* tok_end,
+                          float* tok_logp, int32_t* utt_start, int32_t* utt_end, int32_t* utt_frames, float* utt_logp,
+                          int32_t* utt_worst, int32_t* span, float* total, int32_t* status, void* workspace,
+                          size_t workspace_bytes, int B, int T, int C, int max_tokens, float* phase_ms,
+                          lr_stream_t stream);
+
 /* ---- A8 (BUILD-DEFINED, no reference symbol): 3-D conv frontend on bf16 MFMA -------------- */
 /* The reference has no conv frontend (src/models/lipreader/model.py:122,153-156 are comments, the
  * `ced` configs are empty); BASELINE.json's north_star asks for one ("im2col + MFMA GEMM for the 3D

@@ -158,3 +158,24 @@ def keyword_report(encoder, data_loader, device, char2idx, keywords, **spotter_k
       captions.append(''.join(inv[int(c)] for c in chars[b, 1:int(char_lens[b]) - 1]))
     hits.extend(spotted)
   return keyword_counts(captions, hits, keywords)
+
+
+def caption_shifts(records, min_confidence=0.5):
+  """How far CTC segmentation moved each video's captions: per record of train.segment_videos (or of the
+  driver's --segment file) dict(video, status, captions, median_shift_s, max_shift_s, low_confidence).  A caption's
+  shift is the larger of |new_start_s - old_start_s| and |new_end_s - old_end_s|; low_confidence counts the captions
+  whose confidence is below `min_confidence` or that hold no frame.  A video that was not segmented (status != 0) has
+  None shifts and low_confidence = its number of captions."""
+  out = []
+  for rec in records:
+    caps = rec["captions"]
+    row = dict(video=rec["video"], status=rec["status"], captions=len(caps), median_shift_s=None, max_shift_s=None,
+               low_confidence=len(caps))
+    if rec["status"] == 0 and caps:
+      shifts = sorted(max(abs(c["new_start_s"] - c["old_start_s"]), abs(c["new_end_s"] - c["old_end_s"])) for c in caps)
+      mid = len(shifts) // 2
+      row["median_shift_s"] = shifts[mid] if len(shifts) % 2 else 0.5 * (shifts[mid - 1] + shifts[mid])
+      row["max_shift_s"] = shifts[-1]
+      row["low_confidence"] = sum(1 for c in caps if c["confidence"] is None or c["confidence"] < min_confidence)
+    out.append(row)
+  return out

@@ -232,6 +232,44 @@ class FrameCaptionDataset(object):
     return char2idx, frames, captions
 
 
+class VideoClips(object):
+  """The samples of ONE video in start-time order, for work on the whole video (train.segment_videos):
+  the occlusion filter of FrameCaptionDataset, no sort by length, and the caption track's own times kept —
+  `s_e[i]` = (start, end) seconds of sample i, `captions[i]` its text, `kept[i]` its row in the video's files.
+  Indexable like FrameCaptionDataset, so the same loaders and collate functions take it (`pixels=True`: the u8 frames of
+  a `frames=True` dataview beside the landmarks).  A video may keep no sample at all: len() == 0."""
+
+  def __init__(self, vid_dir, char2idx, start_end='s_e', threshold=0.8, fps=29.97, cap='cap', frame_type='face_lmk_seq',
+               pixel_type='face_frames_seq', in_ext='.npy', pixels=False):
+    def load(base):
+      path = os.path.join(vid_dir, base + in_ext)
+      assert os.path.isfile(path), path
+      return list(np.load(path, allow_pickle=True))
+    frames, captions, start_ends = load(frame_type), load(cap), load(start_end)
+    assert len(captions) == len(frames) == len(start_ends)
+    kept = [i for i, (f, c, (start, end)) in enumerate(zip(frames, captions, start_ends))
+            if (end - start) * fps * threshold <= len(f) and len(c) + 2 < len(f)]
+    kept.sort(key=lambda i: (float(start_ends[i][0]), i))
+    self.vid_dir, self.char2idx, self.kept = vid_dir, char2idx, kept
+    self.frames = [frames[i] for i in kept]
+    self.captions = [captions[i] for i in kept]
+    self.s_e = [(float(start_ends[i][0]), float(start_ends[i][1])) for i in kept]
+    self.pixels = None
+    if pixels:
+      pix = load(pixel_type)
+      assert len(pix) == len(frames)
+      self.pixels = [np.ascontiguousarray(pix[i]) for i in kept]
+
+  def __len__(self):
+    return len(self.captions)
+
+  def __getitem__(self, index):
+    frames = self.frames[index]
+    if self.pixels is not None:
+      return (self.pixels[index], frames), parse_caption(self.char2idx, self.captions[index])
+    return frames, parse_caption(self.char2idx, self.captions[index])
+
+
 def iterate_batches(dataset, batch_size, collate_fn):
   """What `DataLoader(dataset, batch_size, collate_fn=..., shuffle=False)` yields
   (src/scripts/train.py:209-211): consecutive, un-shuffled batches of the sorted dataset."""

@@ -77,6 +77,11 @@ DEFAULTS = dict(  # train.py:134-167
     # and confidence.  --spot_confidence=p in (0, 1] (0 = no threshold) keeps spans whose per-character confidence is
     # at least p; --spot_max_hits spans per (utterance, keyword).  Needs a CTC head.
     spot="", keywords="", spot_confidence=0.0, spot_max_hits=4,
+    # --segment=PATH ('' = off): after the last epoch, CTC segmentation of every validation VIDEO (train.segment_videos:
+    # lr_ctc_segment) — the video's clips encoded and joined into one stream, its whole caption track aligned against it
+    # with both ends free — one JSON object per line: the video, status, stream length, and per kept caption its text,
+    # old and new times, confidence and worst character.  Needs a CTC head.
+    segment="",
 )
 
 
@@ -177,6 +182,7 @@ def parse_flags(argv, defaults=DEFAULTS):
   crop_check(out)
   align_check(out)
   spot_check(out)
+  segment_check(out)
   return out
 
 
@@ -209,6 +215,12 @@ def align_check(f):
   """ValueError for --align without a CTC head (neither --enable_ctc nor a regime that is encoder + CTC)."""
   if f.get("align") and not f.get("enable_ctc"):
     raise ValueError("--align=%s needs a CTC head: --enable_ctc=True (or a CTC-only regime)" % f["align"])
+
+
+def segment_check(f):
+  """ValueError for --segment without a CTC head (neither --enable_ctc nor a regime that is encoder + CTC)."""
+  if f.get("segment") and not f.get("enable_ctc"):
+    raise ValueError("--segment=%s needs a CTC head: --enable_ctc=True (or a CTC-only regime)" % f["segment"])
 
 
 def spot_check(f):
@@ -256,6 +268,22 @@ def write_spots(path, encoder, loader, device, char2idx, keywords, min_confidenc
       n += 1
       total += len(found)
   return dict(path=path, utterances=n, keywords=len(keywords), hits=total)
+
+
+def write_segments(path, encoder, vid_dirs, device, char2idx, batch_size, fps=29.97, **how):
+  """train.segment_videos over `vid_dirs` as JSON lines in `path`, one per video (its record as it is).  Returns
+  dict(path, videos, captions, segmented): videos written, captions kept in them, videos with status 0.  `how` goes to
+  segment_videos (the collate function and `pixels` of the regime, the occlusion threshold)."""
+  import json
+  from . import train as T
+  n = caps = ok = 0
+  with open(path, "w") as out:
+    for rec in T.segment_videos(encoder, vid_dirs, device, char2idx, batch_size, fps=fps, **how):
+      out.write(json.dumps(rec) + "\n")
+      n += 1
+      caps += len(rec["captions"])
+      ok += rec["status"] == 0
+  return dict(path=path, videos=n, captions=caps, segmented=int(ok))
 
 
 def write_alignments(path, encoder, loader, device, char2idx, fps=29.97):
@@ -415,6 +443,7 @@ def run(**flags):
     f["enable_ctc"], f["ctc_only"] = flags.get("enable_ctc", True), flags.get("ctc_only", True)
   align_check(f)
   spot_check(f)
+  segment_check(f)
   torch.manual_seed(f["seed"])
   rand = np.random.RandomState(seed=f["seed"])
   assert torch.cuda.is_available(), "the driver runs the HIP path: an MI355X is required (no CPU fallback)"
@@ -550,6 +579,10 @@ def run(**flags):
                               min_confidence=f["spot_confidence"] or None, max_hits=f["spot_max_hits"])
     print("Spotted %(keywords)d keywords in %(utterances)d validation utterances (%(hits)d hits): %(path)s"
           % out["spot"])
+  if f["segment"]:
+    out["segment"] = write_segments(f["segment"], encoder, sorted(splits[1]), device, char2idx, f["batch_size"],
+                                    collate_fn=collate, pixels=pixels, threshold=f["occlussion_threshold"])
+    print("Segmented %(segmented)d of %(videos)d validation videos (%(captions)d captions): %(path)s" % out["segment"])
   return out
 
 

@@ -946,3 +946,97 @@ def spot_loader(encoder, data_loader, device, char2idx, keywords, **spotter_kw):
     for b, found in enumerate(spotted):
       yield dict(index=index, frames=int(n[b]), hits=found)
       index += 1
+
+
+# ---- CTC segmentation of whole videos (lipreading_amd/segment.py) -------------------------------------
+
+def stream_position(offsets, frame):
+  """(clip, frame in the clip) of a frame of the stream whose clips start at `offsets` (ascending, offsets[0] == 0)."""
+  import bisect
+  clip = bisect.bisect_right(offsets, frame) - 1
+  return clip, frame - offsets[clip]
+
+
+def segment_videos(encoder, vid_dirs, device, char2idx, batch_size, fps=29.97, collate_fn=None, pixels=False,
+                   threshold=0.8):
+  """Where does each caption of a whole video really start and end, by the encoder's CTC head: a generator of one
+  record per video directory of `vid_dirs`, in their order.
+
+  Per video: its kept clips in start-time order (dataset.VideoClips) are encoded batch by batch through `collate_fn`
+  (default: data.make_collate_fn(device); pass the pixel regime's with pixels=True) — through _retried as align_loader
+  does — and every clip's valid log-probability rows are joined into ONE stream on the device.  The stream is segmented
+  (segment.CTCSegmenter, both ends free) against the whole caption track, every caption with its '<EOS>' — the training
+  target of its clip — one utterance.  Stream frames map back to (clip, frame in the clip) and so to seconds,
+  s_e[clip].start + frame / fps.
+
+  The record: dict(video, status, frames, tokens, total, span, captions=[dict(index (the caption's row in the video's
+  files), text, old_start_s, old_end_s, start, end (stream frames), start_clip, start_frame, end_clip, end_frame (of the
+  caption's last frame), new_start_s, new_end_s, logp, frames, confidence, worst)]).  status: 0, the kernel's
+  (segment.INFEASIBLE, ...), segment.TOO_LONG for a video past the kernel's limits and segment.NO_CLIPS for one that
+  keeps no clip; with a non-zero status the captions carry their old times only."""
+  from . import segment as SG
+  from .analysis import need_ctc_head
+  from .data import make_collate_fn
+  from .dataset import BatchLoader, VideoClips
+  from .decoder import ctc_labels
+  device = torch.device(device)
+  if device.type != "cuda":
+    raise _C.LipReadingHipError("CTC segmentation runs on the MI355X only (no CPU fallback)")
+  need_ctc_head(encoder)
+  segmenter = SG.CTCSegmenter(ctc_labels(char2idx), blank_index=0, fps=fps)
+  collate_fn = collate_fn if collate_fn is not None else make_collate_fn(device)
+  encoder.eval()
+  flag2 = torch.zeros(2, dtype=torch.int32, device=device)
+  for vid in vid_dirs:
+    clips = VideoClips(vid, char2idx, threshold=threshold, fps=fps, pixels=pixels)
+    caps = [dict(index=clips.kept[i], text=clips.captions[i], old_start_s=clips.s_e[i][0], old_end_s=clips.s_e[i][1])
+            for i in range(len(clips))]
+    rec = dict(video=os.path.basename(os.path.normpath(vid)), status=SG.NO_CLIPS, frames=0, tokens=0, total=None,
+               span=None, captions=caps)
+    if len(clips) == 0:
+      yield rec
+      continue
+    # the training targets: the caption's characters and '<EOS>' in the CTC head's class layout (chars[:, 1:] + 1)
+    ids = [[int(c) + 1 for c in clips[i][1][1:]] for i in range(len(clips))]
+    lens = [int(clips.frames[i].shape[0]) for i in range(len(clips))]
+    offsets = [0]
+    for n in lens[:-1]:
+      offsets.append(offsets[-1] + n)
+    rec["frames"], rec["tokens"] = sum(lens), sum(len(r) for r in ids)
+    if not SG.within_limits(rec["frames"], rec["tokens"]):
+      rec["status"] = SG.TOO_LONG
+      yield rec
+      continue
+    rows = []
+    with torch.no_grad():
+      for frames, frame_lens, _, _ in BatchLoader(clips, batch_size, collate_fn):
+        max_len = host_max_len(frame_lens)
+        frames_d, lens_d = frames.to(device), frame_lens.to(device)
+        n = [int(x) for x in frame_lens.tolist()]
+
+        def valid_rows():
+          log_probs = encoder(frames_d, lens_d, max_len=max_len)[0]
+          return torch.cat([log_probs[b, :n[b]] for b in range(len(n))], dim=0)
+
+        rows.append(_retried(encoder, flag2, valid_rows))
+      stream = torch.cat(rows, dim=0).unsqueeze(0)
+      assert stream.shape[1] == rec["frames"]
+      tg = torch.tensor([[c for r in ids for c in r]], dtype=torch.int32, device=device)
+      first = [0]
+      for r in ids[:-1]:
+        first.append(first[-1] + len(r))
+      d = lambda rows_: torch.tensor([rows_], dtype=torch.int32, device=device)
+      out = segmenter.segment_ids(stream, None, tg, d([tg.shape[1]])[0], d(first), d([len(r) for r in ids]),
+                                  d([len(ids)])[0])
+      got = segmenter.records(out, [clips.captions], tg)[0]
+    if got["status"] == 0:
+      rec.update(total=got["total"], span=list(got["span"]))
+    rec["status"] = got["status"]
+    if got["status"] == 0:
+      for cap, u in zip(caps, got["utterances"]):
+        sc, sf = stream_position(offsets, u["start"])
+        ec, ef = stream_position(offsets, u["end"] - 1)
+        cap.update(start=u["start"], end=u["end"], start_clip=sc, start_frame=sf, end_clip=ec, end_frame=ef,
+                   new_start_s=clips.s_e[sc][0] + sf / fps, new_end_s=clips.s_e[ec][0] + (ef + 1) / fps,
+                   logp=u["logp"], frames=u["frames"], confidence=u["confidence"], worst=u["worst"])
+    yield rec
