@@ -877,6 +877,39 @@ int lr_ctc_beam_lm_decode(const float* probs, int64_t stride_b, int64_t stride_t
                           int32_t* out_ids, int32_t* out_offsets, int32_t* out_lens, float* out_scores,
                           void* workspace, size_t workspace_bytes, int B, int T, int C, lr_stream_t stream);
 
+/* ---- A6c': the same searches with hotwords (contextual biasing) — no counterpart in the reference ---- */
+/* Phrases given as class ids raise the selection key of hypotheses that spell them, while the search runs; the
+ * specification and the blob's layout are in lipreading_amd/csrc/lr_ctc_beam.hip.
+ * Limits: at most 4096 automaton nodes and 1024 phrases, n_classes <= 256 (LR_ERR_UNSUPPORTED). */
+
+/* Bytes of the packed hotword blob (0 for arguments lr_ctc_beam_bias_pack rejects).  phrase_off[n_phrases+1]
+ * (phrase_off[0] = 0) delimits the phrases' class ids in phrase_cls; anchor: the class of ' ' (a phrase then matches
+ * only at the start of a word) or -1. */
+size_t lr_ctc_beam_bias_pack_bytes(int n_phrases, const int64_t* phrase_off, const int32_t* phrase_cls, int anchor,
+                                   int n_classes);
+
+/* Host only (no device call): build the Aho-Corasick automaton over the phrases and write it into `out` (host
+ * memory) as one dense table.  weights[n_phrases] fp32, each finite and > 0.  An empty phrase, a class id outside
+ * [0, n_classes), a bad weight or no phrase at all is LR_ERR_INVALID_ARG. */
+int lr_ctc_beam_bias_pack(void* out, size_t out_bytes, int n_phrases, const int64_t* phrase_off,
+                          const int32_t* phrase_cls, const float* weights, int anchor, int n_classes);
+
+/* lr_ctc_beam_decode plus the hotwords: bias = the packed blob on the device.  Workspace:
+ * lr_ctc_beam_workspace_bytes.  out_scores = -(log mass + the completed hotwords' weights), ascending. */
+int lr_ctc_beam_bias_decode(const float* probs, int64_t stride_b, int64_t stride_t, const int32_t* sizes,
+                            int log_input, int cutoff_top_n, float cutoff_prob, int beam_width, int blank,
+                            const void* bias, int32_t* out_ids, int32_t* out_offsets, int32_t* out_lens,
+                            float* out_scores, void* workspace, size_t workspace_bytes, int B, int T, int C,
+                            lr_stream_t stream);
+
+/* lr_ctc_beam_lm_decode plus the hotwords.  The dictionary is unchanged: a hotword whose words are not ARPA
+ * unigrams stays unreachable.  out_scores = -(log mass + the final word's term + the completed hotwords' weights). */
+int lr_ctc_beam_lm_bias_decode(const float* probs, int64_t stride_b, int64_t stride_t, const int32_t* sizes,
+                               int log_input, int cutoff_top_n, float cutoff_prob, int beam_width, int blank,
+                               const void* lm, const int32_t* class_roles, float alpha, float beta, const void* bias,
+                               int32_t* out_ids, int32_t* out_offsets, int32_t* out_lens, float* out_scores,
+                               void* workspace, size_t workspace_bytes, int B, int T, int C, lr_stream_t stream);
+
 /* ---- A6d: edit-distance scoring of decoded ids — decoder.py:44-73 (Decoder.wer / Decoder.cer) on the device ---- */
 /* The reference scores joined label strings on the host with the Levenshtein package.  Here the ids stay on the
  * device (lipreading_amd/csrc/lr_edit.hip): every class id spells a string over the caller's

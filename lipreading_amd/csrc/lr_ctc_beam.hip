@@ -85,7 +85,41 @@
 //            term alpha * lm + beta of its current word in LDS: phase 2 adds the cached term to the space
 //            extension and probes the trie for each word-character extension; phase 5 probes the trie again for
 //            the survivors and scores their new current word; the end term is the cached one.
+//
+// With hotwords (lr_ctc_beam_bias_decode, lr_ctc_beam_lm_bias_decode; contextual biasing as pyctcdecode's, the
+// specification is this build's own).  Everything above holds; the following is added.
+//   Phrases  q_k: class ids, length m_k >= 1, finite weight w_k > 0.  anchor = the class of ' ', or -1.  A start
+//            position i of a prefix y is admissible if anchor < 0, or i == 0, or y[i-1] == anchor: with an anchor a
+//            phrase matches only at the start of a word.  The blank never appears in y; every other class may appear
+//            in a phrase and is compared by index.
+//   Scores   occ_k(y) = the number of admissible i with y[i:i+m_k] == q_k (overlaps count).  partial(y) = the largest
+//            w_k * j / m_k over k and 1 <= j < m_k such that y ends with q_k[:j] and that suffix starts at an
+//            admissible position (0 if there is none).  bonus_end(y) = sum_k w_k * occ_k(y);
+//            bonus_run(y) = bonus_end(y) + partial(y).
+//   Search   the masses (p_blank, p_nonblank) evolve exactly as without hotwords (with a language model they carry
+//            its terms).  At every frame a candidate's selection key is score + bonus_run(its prefix), the tie-break
+//            unchanged: a parent's own continuation keeps the parent's bonus, an extension takes that of p+c.  The
+//            bonus is a function of the prefix, so merging by prefix holds.
+//   End      after the last frame the partial credit is dropped: final score = log mass (+ the LM's end term)
+//            + bonus_end; the beam is re-sorted by it, ties keeping the earlier rank.  out_scores = -(final score),
+//            ascending.  Offsets, ids and lens as above.
+//   LM       the dictionary is unchanged: a hotword whose words are not ARPA unigrams stays unreachable.
+//   Layout   the host (lr_ctc_beam_bias_pack) builds an Aho-Corasick automaton over the phrases (with an anchor: over
+//            anchor + q_k, the search starting in the state that follows one anchor; the anchor is not counted in
+//            j / m_k) and writes one read-only blob: next[node][C] int32 with the fail links resolved, out[node] =
+//            the sum of w_k of every phrase ending at the node (through the fail chain), part[node] = the best
+//            partial credit along the fail chain (phrases that end exactly there excluded).  Per hypothesis the loop
+//            keeps one node id and one banked fp32 sum (bonus_end) in LDS.  An extension's bonus is
+//            (bank + out[nn]) + part[nn] with nn = next[node][c], in fp32 and in that order: one 4-byte load and two
+//            more.  The key's bonus is added to sm.score in phase 2; phases 3 and 5 recompute the few masses they
+//            need (a merged extension's, a surviving extension's) with phase 2's own expression, so the masses stay
+//            bit-identical to the search without hotwords.
+//   Limits   at most 4096 automaton nodes, 1024 phrases, C <= 256 (the packer's LR_ERR_UNSUPPORTED); an empty phrase
+//            or a weight that is not finite and positive is LR_ERR_INVALID_ARG.
 #include <string.h>
+
+#include <type_traits>
+#include <vector>
 
 #include "lr_common.h"
 #include "lr_lm_dev.h"
@@ -206,6 +240,41 @@ struct LmArgs {
   float alpha, beta;
 };
 
+// the loop kernel's last argument: the plain and LM instantiations take LmArgs as it is, the bias ones the blob too
+struct BiasLmArgs : LmArgs {
+  const uint8_t* bias;   // the packed hotword automaton
+};
+template <bool BIAS>
+using LoopArgs = std::conditional_t<BIAS, BiasLmArgs, LmArgs>;
+
+// the packed hotword automaton (lr_ctc_beam_bias_pack): header, next[nodes][stride] int32, out[nodes], part[nodes] fp32
+constexpr uint32_t kBiasMagic = 0x5342524cu;   // "LRBS"
+constexpr int kBiasVersion = 1;
+constexpr int kBiasMaxNodes = 4096;
+constexpr int kBiasMaxPhrases = 1024;
+struct BiasHeader {
+  uint32_t magic;
+  int32_t version, nodes, stride, start, phrases, anchor, pad_;
+  int64_t next_off, out_off, part_off, bytes;
+};
+static_assert(sizeof(BiasHeader) == 64, "BiasHeader is part of the blob's layout");
+
+struct BiasView {
+  const int32_t* next;
+  const float* out;
+  const float* part;
+  int stride, start;
+};
+__device__ __forceinline__ BiasView bias_view(const uint8_t* blob) {
+  const BiasHeader* h = reinterpret_cast<const BiasHeader*>(blob);
+  return BiasView{reinterpret_cast<const int32_t*>(blob + h->next_off), reinterpret_cast<const float*>(blob + h->out_off),
+                  reinterpret_cast<const float*>(blob + h->part_off), h->stride, h->start};
+}
+// a class the blob was not packed for is in no phrase and is not the anchor: it leads to the root
+__device__ __forceinline__ int bias_next(const BiasView& v, int node, int c) {
+  return c < v.stride ? v.next[node * v.stride + c] : 0;
+}
+
 // ---------------------------------------------------------------------------------------
 // 2. the frame loop: one workgroup per utterance
 // ---------------------------------------------------------------------------------------
@@ -222,6 +291,25 @@ struct BeamLmSmem {
 };
 template <>
 struct BeamLmSmem<false> {};
+
+// hotword state of the beam (the bias instantiations only): automaton node, the banked bonus_end, this frame's
+// bonus_run of the own continuation; without a language model also the end's re-sort (the LM block has its own)
+template <bool BIAS, bool LM>
+struct BeamBiasSmem {};
+template <>
+struct BeamBiasSmem<true, true> {
+  int bnode[2][kBeamMaxW];
+  float bbank[2][kBeamMaxW];
+  float sbon[kBeamMaxW];
+};
+template <>
+struct BeamBiasSmem<true, false> {
+  int bnode[2][kBeamMaxW];
+  float bbank[2][kBeamMaxW];
+  float sbon[kBeamMaxW];
+  float fin[kBeamMaxW];
+  int perm[kBeamMaxW];
+};
 
 struct BeamSmem {
   float score[kMaxCand];          // candidate s = i*(n+1) + j: j = 0 parent i's own continuation, j = 1+k extension by
@@ -273,16 +361,32 @@ __device__ __forceinline__ uint64_t cand_key(float sc, int s, int n1, const int*
   return ((uint64_t)ord_f32(sc) << 16) | (uint64_t)(0xffffu - (uint32_t)tb);
 }
 
-// LM = false is the search without a language model; LM = true adds the terms and the dictionary of the header.
+// the mass of parent i's extension by kept class k, as phase 2 computes it: the bias instantiations keep the key in
+// sm.score and recompute the masses they need
 template <bool LM>
+__device__ __forceinline__ float ext_mass(const BeamSmem& sm, const BeamLmSmem<LM>& lsm, int cur, int i, int k) {
+  const int c = sm.kc[k];
+  const float pbi = sm.pb[cur][i], pnbi = sm.pnb[cur][i];
+  float sc = (c == sm.cls[cur][i] ? pbi : lr_lse2(pbi, pnbi)) + sm.kl[k];
+  if constexpr (LM) {
+    if (lsm.role[c] == kRoleSpace) sc += lsm.tterm[cur][i];
+  }
+  return sc;
+}
+
+// LM = false is the search without a language model; LM = true adds the terms and the dictionary of the header.
+// BIAS = true adds the hotwords' bonus to the selection key.  LM + BIAS re-sorts through the LM block's fin / perm, so
+// its 2.5 KB of hotword state fit beside the LM's 62 KB under the 64 KB of static LDS.
+template <bool LM, bool BIAS>
 __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
     const int32_t* __restrict__ kcls, const float* __restrict__ klp, const int32_t* __restrict__ kcnt,
     const int32_t* __restrict__ sizes, int32_t* __restrict__ npar, int32_t* __restrict__ ncls,
     int32_t* __restrict__ nfrm, int32_t* __restrict__ out_ids, int32_t* __restrict__ out_off,
     int32_t* __restrict__ out_lens, float* __restrict__ out_scores, int T, int W, int n, int blank, int C,
-    LmArgs lma) {
+    LoopArgs<BIAS> lma) {
   __shared__ BeamSmem sm;
   __shared__ BeamLmSmem<LM> lsm;
+  __shared__ BeamBiasSmem<BIAS, LM> bsm;
   const int b = blockIdx.x;
   const int tid = threadIdx.x;
   const int nt = blockDim.x;
@@ -309,6 +413,11 @@ __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
       lsm.tnode[0][0] = 0; lsm.tword[0][0] = -1; lsm.tterm[0][0] = 0.f;
       for (int q = 0; q < kLmMaxCtx; ++q) lsm.ctx[0][0][q] = bos;
     }
+  }
+  BiasView bv{};
+  if constexpr (BIAS) {
+    bv = bias_view(lma.bias);
+    if (tid == 0) { bsm.bnode[0][0] = bv.start; bsm.bbank[0][0] = 0.f; }
   }
   int cur = 0, nb = 1;
   // the kept list of the next frame is loaded one frame ahead
@@ -353,6 +462,11 @@ __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
         sm.spb[i] = nb_;
         sm.spnb[i] = nnb;
         sm.score[s] = lr_lse2(nb_, nnb);
+        if constexpr (BIAS) {
+          const float bo = bsm.bbank[cur][i] + bv.part[bsm.bnode[cur][i]];
+          bsm.sbon[i] = bo;
+          sm.score[s] += bo;
+        }
       } else {
         const int k = j - 1;
         float sc = LR_NEG_INF;
@@ -364,6 +478,12 @@ __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
               const int role = lsm.role[c];
               if (role == kRoleSpace) sc += lsm.tterm[cur][i];   // 0 when the current word is empty
               else if (role == kRoleWord && lm_trie_find(L, lsm.tnode[cur][i], c).x < 0) sc = LR_NEG_INF;
+            }
+          }
+          if constexpr (BIAS) {
+            if (sc > LR_NEG_INF) {
+              const int nn = bias_next(bv, bsm.bnode[cur][i], c);
+              sc += (bsm.bbank[cur][i] + bv.out[nn]) + bv.part[nn];
             }
           }
         }
@@ -390,11 +510,15 @@ __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
         }
         if (i >= 0) {
           const int e = i * n1 + 1 + k;
-          const float m = sm.score[e];
+          float m = sm.score[e];
+          if constexpr (BIAS) {
+            if (m > LR_NEG_INF) m = ext_mass<LM>(sm, lsm, cur, i, k);
+          }
           sm.score[e] = LR_NEG_INF;
           const float pn = lr_lse2(sm.spnb[tid], m);
           sm.spnb[tid] = pn;
           sm.score[tid * n1] = lr_lse2(sm.spb[tid], pn);
+          if constexpr (BIAS) sm.score[tid * n1] += bsm.sbon[tid];
         }
       }
     }
@@ -480,6 +604,7 @@ __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
           lsm.tterm[nxt][r] = lsm.tterm[cur][i];
           for (int q = 0; q < kLmMaxCtx; ++q) lsm.ctx[nxt][r][q] = lsm.ctx[cur][i][q];
         }
+        if constexpr (BIAS) { bsm.bnode[nxt][r] = bsm.bnode[cur][i]; bsm.bbank[nxt][r] = bsm.bbank[cur][i]; }
       } else {
         const int c = sm.kc[j - 1];
         const int id = 1 + t * W + r;
@@ -490,6 +615,11 @@ __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
         sm.node[nxt][r] = id; sm.par[nxt][r] = p; sm.cls[nxt][r] = c; sm.depth[nxt][r] = sm.depth[cur][i] + 1;
         sm.pb[nxt][r] = LR_NEG_INF;        sm.pnb[nxt][r] = sm.score[s];
         sm.hpre[nxt][r] = prefix_hash(sm.hpre[cur][i], c); sm.hpar[nxt][r] = sm.hpre[cur][i];
+        if constexpr (BIAS) {
+          const int nn = bias_next(bv, bsm.bnode[cur][i], c);
+          sm.pnb[nxt][r] = ext_mass<LM>(sm, lsm, cur, i, j - 1);   // sm.score[s] is the key
+          bsm.bnode[nxt][r] = nn; bsm.bbank[nxt][r] = bsm.bbank[cur][i] + bv.out[nn];
+        }
         if constexpr (LM) {
           const int role = lsm.role[c], node = lsm.tnode[cur][i];
           int* ctx = lsm.ctx[nxt][r];
@@ -518,12 +648,27 @@ __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
   // -- end of utterance (LM): the last word's term, then a stable re-sort by the final score
   if constexpr (LM) {
     if (tid < nb) lsm.fin[tid] = lr_lse2(sm.pb[cur][tid], sm.pnb[cur][tid]) + lsm.tterm[cur][tid];
+    if constexpr (BIAS) {
+      if (tid < nb) lsm.fin[tid] += bsm.bbank[cur][tid];
+    }
     __syncthreads();
     if (tid < nb) {
       const float f = lsm.fin[tid];
       int r = 0;
       for (int q = 0; q < nb; ++q) r += lsm.fin[q] > f || (lsm.fin[q] == f && q < tid);
       lsm.perm[r] = tid;
+    }
+  }
+
+  // -- end of utterance (hotwords without an LM): bonus_end, then the same stable re-sort
+  if constexpr (BIAS && !LM) {
+    if (tid < nb) bsm.fin[tid] = lr_lse2(sm.pb[cur][tid], sm.pnb[cur][tid]) + bsm.bbank[cur][tid];
+    __syncthreads();
+    if (tid < nb) {
+      const float f = bsm.fin[tid];
+      int r = 0;
+      for (int q = 0; q < nb; ++q) r += bsm.fin[q] > f || (bsm.fin[q] == f && q < tid);
+      bsm.perm[r] = tid;
     }
   }
 
@@ -534,6 +679,7 @@ __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
   // output rank r holds beam entry src(r)
   auto src = [&](int r) {
     if constexpr (LM) return lsm.perm[r];
+    else if constexpr (BIAS) return bsm.perm[r];
     else return r;
   };
   for (int64_t e = tid; e < (int64_t)W * T; e += nt) {
@@ -545,6 +691,8 @@ __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
     out_lens[(int64_t)b * W + tid] = tid < nb ? sm.depth[cur][src(tid)] : 0;
     if constexpr (LM)
       out_scores[(int64_t)b * W + tid] = tid < nb ? -lsm.fin[src(tid)] : __builtin_inff();
+    else if constexpr (BIAS)
+      out_scores[(int64_t)b * W + tid] = tid < nb ? -bsm.fin[src(tid)] : __builtin_inff();
     else
       out_scores[(int64_t)b * W + tid] =
           tid < nb ? -lr_lse2(sm.pb[cur][tid], sm.pnb[cur][tid]) : __builtin_inff();
@@ -605,6 +753,106 @@ Slot* host_probe(Slot* tab, uint64_t mask, uint64_t key) {
     if (tab[s].key == key || tab[s].key == kLmEmpty) return tab + s;
 }
 
+// the hotword automaton on the host: Aho-Corasick over the (anchor-prefixed) phrases, as a dense table
+struct BiasAuto {
+  int nodes = 0, start = 0;
+  std::vector<int32_t> next;        // [nodes][C]: the trie's edges while it is built, the resolved table afterwards
+  std::vector<double> out, part;    // [nodes]
+};
+
+// 1: built; 0: more phrases, nodes or classes than the blob holds (LR_ERR_UNSUPPORTED); -1: bad arguments.
+// weights == nullptr counts the nodes only.
+int bias_build(int n_phrases, const int64_t* off, const int32_t* cls, const float* weights, int anchor, int C,
+               BiasAuto* a) {
+  if (n_phrases < 1 || !off || !cls || C < 1 || off[0] != 0) return -1;
+  if (C > kBeamMaxC) return 0;
+  if (anchor < -1 || anchor >= C) return -1;
+  for (int k = 0; k < n_phrases; ++k) {
+    if (off[k + 1] <= off[k]) return -1;   // an empty phrase
+    for (int64_t j = off[k]; j < off[k + 1]; ++j)
+      if (cls[j] < 0 || cls[j] >= C) return -1;
+    if (weights && !(isfinite(weights[k]) && weights[k] > 0.f)) return -1;
+  }
+  if (n_phrases > kBiasMaxPhrases) return 0;
+  std::vector<int32_t>& next = a->next;
+  std::vector<double> own(1, 0.0), val(1, 0.0);   // weights ending at the node; its best partial credit
+  next.assign(C, -1);
+  int nodes = 1;
+  auto child = [&](int node, int c) {
+    if (next[(size_t)node * C + c] < 0) {
+      next[(size_t)node * C + c] = nodes++;
+      next.resize((size_t)nodes * C, -1);
+      own.push_back(0.0);
+      val.push_back(0.0);
+    }
+    return next[(size_t)node * C + c];
+  };
+  a->start = anchor >= 0 ? child(0, anchor) : 0;
+  for (int k = 0; k < n_phrases; ++k) {
+    const int64_t m = off[k + 1] - off[k];
+    const double w = weights ? (double)weights[k] : 0.0;
+    int node = a->start;
+    for (int64_t j = 1; j <= m; ++j) {
+      node = child(node, cls[off[k] + j - 1]);
+      if (nodes > kBiasMaxNodes) return 0;
+      if (j < m) val[node] = fmax(val[node], w * (double)j / (double)m);
+      else own[node] += w;
+    }
+  }
+  a->nodes = nodes;
+  if (!weights) return 1;
+  // breadth first: a node's fail target is shallower, so its row, out and part are final when the node is reached
+  std::vector<int> fail(nodes, 0), queue;
+  queue.reserve(nodes);
+  a->out.assign(nodes, 0.0);
+  a->part.assign(nodes, 0.0);
+  for (int c = 0; c < C; ++c) {
+    const int u = next[c];
+    if (u < 0) next[c] = 0;
+    else queue.push_back(u);
+  }
+  for (size_t h = 0; h < queue.size(); ++h) {
+    const int u = queue[h], f = fail[u];
+    a->out[u] = own[u] + a->out[f];
+    a->part[u] = fmax(val[u], a->part[f]);
+    for (int c = 0; c < C; ++c) {
+      int32_t& e = next[(size_t)u * C + c];
+      const int via = next[(size_t)f * C + c];
+      if (e < 0) e = via;
+      else { fail[e] = via; queue.push_back(e); }
+    }
+  }
+  return 1;
+}
+
+size_t bias_bytes(int nodes, int C) {
+  return lr_align_up(sizeof(BiasHeader) + (size_t)nodes * C * 4 + (size_t)nodes * 8, 16);
+}
+
+// the two hotword entry points: lr_ctc_beam_decode / lr_ctc_beam_lm_decode with the bias instantiation of the loop
+template <bool LM>
+int beam_bias_decode(const float* probs, int64_t stride_b, int64_t stride_t, const int32_t* sizes, int log_input,
+                     int cutoff_top_n, float cutoff_prob, int beam_width, int blank, const LmArgs& lma,
+                     const void* bias, int32_t* out_ids, int32_t* out_offsets, int32_t* out_lens, float* out_scores,
+                     void* workspace, size_t workspace_bytes, int B, int T, int C, lr_stream_t stream) {
+  LR_CHECK_ARG(probs && out_ids && out_offsets && out_lens && out_scores && workspace && bias);
+  LR_CHECK_ARG(B > 0 && T > 0 && C > 0 && beam_width > 0 && cutoff_top_n > 0);
+  LR_CHECK_ARG(blank >= 0 && blank < C && !(cutoff_prob != cutoff_prob));
+  if (!beam_supported(T, C, beam_width, cutoff_top_n)) return LR_ERR_UNSUPPORTED;
+  const int W = beam_width, n = cutoff_top_n;
+  if (workspace_bytes < beam_ws_bytes(B, T, n, W)) return LR_ERR_WORKSPACE;
+  const BeamWs w = beam_ws_carve(workspace, B, T, n, W);
+  const int64_t frames = (int64_t)B * T;
+  LR_LAUNCH(beam_prune_kernel, dim3((unsigned)((frames + kPruneWaves - 1) / kPruneWaves)),
+            dim3(kPruneWaves * LR_WAVE), 0, stream, probs, stride_b, stride_t, sizes, log_input, cutoff_prob,
+            w.kcls, w.klp, w.kcnt, B, T, C, n);
+  int st = lr_launch_status();
+  if (st != LR_OK) return st;
+  LR_LAUNCH((beam_loop_kernel<LM, true>), dim3(B), dim3(kLoopThreads), 0, stream, w.kcls, w.klp, w.kcnt, sizes,
+            w.npar, w.ncls, w.nfrm, out_ids, out_offsets, out_lens, out_scores, T, W, n, blank, C,
+            BiasLmArgs{lma, static_cast<const uint8_t*>(bias)});
+  return lr_launch_status();
+}
 
 }  // namespace
 
@@ -631,8 +879,8 @@ extern "C" int lr_ctc_beam_decode(const float* probs, int64_t stride_b, int64_t 
             w.kcls, w.klp, w.kcnt, B, T, C, n);
   int st = lr_launch_status();
   if (st != LR_OK) return st;
-  LR_LAUNCH(beam_loop_kernel<false>, dim3(B), dim3(kLoopThreads), 0, stream, w.kcls, w.klp, w.kcnt, sizes, w.npar,
-            w.ncls, w.nfrm, out_ids, out_offsets, out_lens, out_scores, T, W, n, blank, C, LmArgs{});
+  LR_LAUNCH((beam_loop_kernel<false, false>), dim3(B), dim3(kLoopThreads), 0, stream, w.kcls, w.klp, w.kcnt, sizes,
+            w.npar, w.ncls, w.nfrm, out_ids, out_offsets, out_lens, out_scores, T, W, n, blank, C, LmArgs{});
   return lr_launch_status();
 }
 
@@ -731,7 +979,63 @@ extern "C" int lr_ctc_beam_lm_decode(const float* probs, int64_t stride_b, int64
   int st = lr_launch_status();
   if (st != LR_OK) return st;
   const LmArgs lma{static_cast<const uint8_t*>(lm), class_roles, alpha, beta};
-  LR_LAUNCH(beam_loop_kernel<true>, dim3(B), dim3(kLoopThreads), 0, stream, w.kcls, w.klp, w.kcnt, sizes, w.npar,
-            w.ncls, w.nfrm, out_ids, out_offsets, out_lens, out_scores, T, W, n, blank, C, lma);
+  LR_LAUNCH((beam_loop_kernel<true, false>), dim3(B), dim3(kLoopThreads), 0, stream, w.kcls, w.klp, w.kcnt, sizes,
+            w.npar, w.ncls, w.nfrm, out_ids, out_offsets, out_lens, out_scores, T, W, n, blank, C, lma);
   return lr_launch_status();
+}
+
+extern "C" size_t lr_ctc_beam_bias_pack_bytes(int n_phrases, const int64_t* phrase_off, const int32_t* phrase_cls,
+                                              int anchor, int n_classes) {
+  BiasAuto a;
+  return bias_build(n_phrases, phrase_off, phrase_cls, nullptr, anchor, n_classes, &a) == 1
+             ? bias_bytes(a.nodes, n_classes) : 0;
+}
+
+extern "C" int lr_ctc_beam_bias_pack(void* out, size_t out_bytes, int n_phrases, const int64_t* phrase_off,
+                                     const int32_t* phrase_cls, const float* weights, int anchor, int n_classes) {
+  LR_CHECK_ARG(out && weights);
+  BiasAuto a;
+  const int ok = bias_build(n_phrases, phrase_off, phrase_cls, weights, anchor, n_classes, &a);
+  if (ok == 0) return LR_ERR_UNSUPPORTED;
+  if (ok < 0) return LR_ERR_INVALID_ARG;
+  const int C = n_classes;
+  const size_t bytes = bias_bytes(a.nodes, C);
+  if (out_bytes < bytes) return LR_ERR_WORKSPACE;
+  uint8_t* blob = static_cast<uint8_t*>(out);
+  memset(blob, 0, bytes);
+  BiasHeader* h = reinterpret_cast<BiasHeader*>(blob);
+  h->magic = kBiasMagic; h->version = kBiasVersion; h->nodes = a.nodes; h->stride = C; h->start = a.start;
+  h->phrases = n_phrases; h->anchor = anchor; h->pad_ = 0;
+  h->next_off = (int64_t)sizeof(BiasHeader);
+  h->out_off = h->next_off + (int64_t)a.nodes * C * 4;
+  h->part_off = h->out_off + (int64_t)a.nodes * 4;
+  h->bytes = (int64_t)bytes;
+  memcpy(blob + h->next_off, a.next.data(), (size_t)a.nodes * C * 4);
+  float* fo = reinterpret_cast<float*>(blob + h->out_off);
+  float* fp = reinterpret_cast<float*>(blob + h->part_off);
+  for (int u = 0; u < a.nodes; ++u) { fo[u] = (float)a.out[u]; fp[u] = (float)a.part[u]; }
+  return LR_OK;
+}
+
+extern "C" int lr_ctc_beam_bias_decode(const float* probs, int64_t stride_b, int64_t stride_t, const int32_t* sizes,
+                                       int log_input, int cutoff_top_n, float cutoff_prob, int beam_width, int blank,
+                                       const void* bias, int32_t* out_ids, int32_t* out_offsets, int32_t* out_lens,
+                                       float* out_scores, void* workspace, size_t workspace_bytes, int B, int T, int C,
+                                       lr_stream_t stream) {
+  return beam_bias_decode<false>(probs, stride_b, stride_t, sizes, log_input, cutoff_top_n, cutoff_prob, beam_width,
+                                 blank, LmArgs{}, bias, out_ids, out_offsets, out_lens, out_scores, workspace,
+                                 workspace_bytes, B, T, C, stream);
+}
+
+extern "C" int lr_ctc_beam_lm_bias_decode(const float* probs, int64_t stride_b, int64_t stride_t, const int32_t* sizes,
+                                          int log_input, int cutoff_top_n, float cutoff_prob, int beam_width,
+                                          int blank, const void* lm, const int32_t* class_roles, float alpha,
+                                          float beta, const void* bias, int32_t* out_ids, int32_t* out_offsets,
+                                          int32_t* out_lens, float* out_scores, void* workspace,
+                                          size_t workspace_bytes, int B, int T, int C, lr_stream_t stream) {
+  LR_CHECK_ARG(lm && class_roles && isfinite(alpha) && isfinite(beta));
+  const LmArgs lma{static_cast<const uint8_t*>(lm), class_roles, alpha, beta};
+  return beam_bias_decode<true>(probs, stride_b, stride_t, sizes, log_input, cutoff_top_n, cutoff_prob, beam_width,
+                                blank, lma, bias, out_ids, out_offsets, out_lens, out_scores, workspace,
+                                workspace_bytes, B, T, C, stream);
 }

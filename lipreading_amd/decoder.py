@@ -9,12 +9,16 @@ compaction) and a single device->host copy of the kept ids.
 BeamCTCDecoder keeps the reference's constructor and `(strings, offsets)` contract, but the
 search ctcdecode runs on CPU threads after `probs.cpu()` (decoder.py:139) runs on the GPU
 (lr_ctc_beam_decode: prefix beam search) with one device->host copy.  An ARPA `lm_path` adds ctcdecode's word
-language model (lr_ctc_beam_lm_decode; the reader is lipreading_amd/lm.py).
+language model (lr_ctc_beam_lm_decode; the reader is lipreading_amd/lm.py); `hotwords` tell either search which
+words to expect (lr_ctc_beam_bias_decode, lr_ctc_beam_lm_bias_decode; lipreading_amd/hotwords.py).
 """
+import warnings
+
 import torch
 
 from . import _C
 from . import _host
+from . import hotwords as hw
 from . import lm
 
 
@@ -73,10 +77,18 @@ class BeamCTCDecoder(Decoder):
   `lm_path` ending in '.arpa' or '.arpa.gz' loads an ARPA n-gram word model (lipreading_amd/lm.py); `alpha` weighs
   its log-probabilities and `beta` is added per word, as in ctcdecode (the specification is lr_ctc_beam.hip's).
   Any other path, or a KenLM binary file, raises NotImplementedError.  The labels then need a ' ' and distinct
-  one-character labels (ValueError otherwise)."""
+  one-character labels (ValueError otherwise).
+
+  `hotwords` (strings, or (string, weight) pairs; `hotword_weight` for the bare strings) raise the score of
+  hypotheses that spell them while the search runs, a half-spelled one in proportion (lr_ctc_beam_bias_decode,
+  DESIGN.md §13.2).  They are spelled in the one-character labels (ValueError for a character without one);
+  `hotword_anchor` lets them match only at the start of a word and needs a ' ' label.  With a language model the
+  dictionary still holds: hotwords with a word the model does not list cannot be reached, and are named in a
+  warning.  None or [] is the search without hotwords."""
 
   def __init__(self, labels, lm_path=None, alpha=0, beta=0, cutoff_top_n=40, cutoff_prob=1.0, beam_width=100,
-               num_processes=4, blank_index=0, log_probs_input=False):
+               num_processes=4, blank_index=0, log_probs_input=False, hotwords=None, hotword_weight=10.0,
+               hotword_anchor=True):
     super(BeamCTCDecoder, self).__init__(labels, blank_index)
     if lm_path is not None and not lm.is_arpa_path(lm_path):
       # decided by the name, before the file is opened
@@ -94,6 +106,14 @@ class BeamCTCDecoder(Decoder):
       # WordLM checks the weights, then the labels, then reads, packs and (once per device) uploads the file
       self._word_lm = lm.WordLM(lm_path, labels, alpha=alpha, beta=beta, blank_index=blank_index)
       self.lm, self.alpha, self.beta = self._word_lm.model, self._word_lm.alpha, self._word_lm.beta
+    self._hotwords = None
+    if hotwords:
+      self._hotwords = hw.Hotwords(hotwords, labels, weight=hotword_weight, anchor=hotword_anchor,
+                                   blank_index=blank_index)
+      lost = self._hotwords.unreachable_under(self.lm) if self.lm is not None else []
+      if lost:
+        warnings.warn("hotwords with a word the language model does not list cannot be decoded: %s"
+                      % ", ".join(repr(t) for t in lost))
 
   def decode_ids(self, probs, sizes=None):
     """Device part: probs (B,T,C) -> (ids (B,W,T) int32, offsets (B,W,T) int32, lens (B,W) int32,
@@ -117,7 +137,14 @@ class BeamCTCDecoder(Decoder):
     head = (probs.data_ptr(), probs.stride(0), probs.stride(1), _C.ptr(sz), int(self.log_probs_input), n,
             self.cutoff_prob, W, self.blank_index)
     tail = (ids.data_ptr(), off.data_ptr(), lens.data_ptr(), scores.data_ptr(), ws.data_ptr(), nbytes, B, T, C)
-    if self._word_lm is not None:
+    bias = None if self._hotwords is None else self._hotwords.tensor(dev)
+    if self._word_lm is not None and bias is not None:
+      blob, roles = self._word_lm.tensors(dev)
+      _host.launch(dev, "lr_ctc_beam_lm_bias_decode", L.lr_ctc_beam_lm_bias_decode,
+                   *head, blob.data_ptr(), roles.data_ptr(), self.alpha, self.beta, bias.data_ptr(), *tail)
+    elif bias is not None:
+      _host.launch(dev, "lr_ctc_beam_bias_decode", L.lr_ctc_beam_bias_decode, *head, bias.data_ptr(), *tail)
+    elif self._word_lm is not None:
       blob, roles = self._word_lm.tensors(dev)
       _host.launch(dev, "lr_ctc_beam_lm_decode", L.lr_ctc_beam_lm_decode,
                    *head, blob.data_ptr(), roles.data_ptr(), self.alpha, self.beta, *tail)

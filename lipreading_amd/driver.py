@@ -42,6 +42,9 @@ DEFAULTS = dict(  # train.py:134-167
     # language model, ctcdecode's default cutoff_top_n=40) with --beam_width hypotheses; --lm_path (an ARPA
     # file, '' = none) adds a word language model weighted by --lm_alpha, plus --lm_beta per word
     ctc_decoder="greedy", beam_width=100, lm_path="", lm_alpha=0.0, lm_beta=0.0,
+    # --hotwords=a,b,c ('' = none) tells the beam decoder which words to expect: each raises the score of the
+    # hypotheses that spell it by --hotword_weight, at the start of a word (BeamCTCDecoder's hotwords)
+    hotwords="", hotword_weight=10.0,
     # the error of a model WITH the attention decoder: teacher (the live loop's sampled-token mismatch rate under
     # teacher forcing, train.eval) or beam (the edit-distance CER of the decoder's own beam-search transcript,
     # train.attention_cer, --attn_beam_width hypotheses of up to --attn_max_label_len characters) or joint (the same
@@ -159,6 +162,8 @@ def parse_flags(argv, defaults=DEFAULTS):
     raise SystemExit("--ctc_decoder must be greedy or beam")
   if out.get("lm_path") and out.get("ctc_decoder") != "beam":
     raise SystemExit("--lm_path needs --ctc_decoder=beam")
+  if (out.get("hotwords") or "hotword_weight" in explicit) and out.get("ctc_decoder") != "beam":
+    raise SystemExit("--hotwords and --hotword_weight need --ctc_decoder=beam")
   if out.get("attn_decode") not in ("teacher", "beam", "joint"):
     raise SystemExit("--attn_decode must be teacher, beam or joint")
   if out.get("attn_decode") == "joint" and not out.get("enable_ctc"):
@@ -497,9 +502,12 @@ def run(**flags):
   ctc_decoder = None
   if ctc_only and f["ctc_decoder"] == "beam":
     from .decoder import BeamCTCDecoder, ctc_labels
-    ctc_decoder = BeamCTCDecoder(ctc_labels(char2idx), lm_path=f["lm_path"] or None, alpha=f["lm_alpha"],
+    labels = ctc_labels(char2idx)
+    ctc_decoder = BeamCTCDecoder(labels, lm_path=f["lm_path"] or None, alpha=f["lm_alpha"],
                                  beta=f["lm_beta"], beam_width=f["beam_width"], blank_index=0,
-                                 log_probs_input=True)
+                                 log_probs_input=True,
+                                 hotwords=[w for w in f["hotwords"].split(",") if w] or None,
+                                 hotword_weight=f["hotword_weight"], hotword_anchor=" " in labels)
 
   error_of = make_error_of(f, encoder, decoding_step, ctc_decoder, device, char2idx)
 

@@ -3,11 +3,14 @@ decode() end to end with its one device->host copy and the strings) next to the 
 tests/test_beam_cpu.py spread over a process pool.
 
   python tools/bench_beam.py [--iters 50] [--threads 16] [--cpu-batches 1] [--lm model.arpa [--alpha A --beta B]]
+                             [--hotwords N [--hotword-weight X]]
 
 B = 32, T = 75, C = 65 (the fallback vocabulary), model-like peaked frames; (W, n) in
 {(1,1), (8,40), (100,40), (128,64)}.  With --lm the same rows follow again with the ARPA language model
 (lr_ctc_beam_lm_decode; ctc_labels() of the fallback vocabulary, whose ' ' separates words; GPU columns only).
-One JSON line per row and a table at the end.
+With --hotwords N the plain rows follow again with N seeded hotwords of 3-8 random classes (lr_ctc_beam_bias_decode,
+not anchored: these labels have no ' '), each beside the plain row of the same run; with --lm too, the LM rows
+follow with the hotwords anchored (lr_ctc_beam_lm_bias_decode).  One JSON line per row and a table at the end.
 """
 import argparse
 import json
@@ -15,6 +18,7 @@ import os
 import sys
 import time
 import multiprocessing
+import warnings
 
 import numpy as np
 
@@ -64,6 +68,16 @@ def time_gpu(dec, pd, iters):
   return gpu_ms, (time.perf_counter() - t0) * 1e3 / iters
 
 
+def random_hotwords(labels, count, seed=1):
+  """`count` distinct strings of 3-8 one-character labels (never the blank's or ' ')."""
+  rng = np.random.default_rng(seed)
+  chars = [l for l in labels[1:] if len(l) == 1 and l != " "]
+  out = set()
+  while len(out) < count:
+    out.add("".join(rng.choice(chars, int(rng.integers(3, 9)))))
+  return sorted(out)
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument("--iters", type=int, default=50)
@@ -72,6 +86,8 @@ def main():
   ap.add_argument("--lm", default=None, help="an ARPA file: add rows with the language model")
   ap.add_argument("--alpha", type=float, default=0.5)
   ap.add_argument("--beta", type=float, default=1.0)
+  ap.add_argument("--hotwords", type=int, default=0, help="N: add rows with N random hotwords")
+  ap.add_argument("--hotword-weight", type=float, default=10.0)
   a = ap.parse_args()
   import torch
   from lipreading_amd import _build
@@ -122,18 +138,48 @@ def main():
                  gpu_decode_ms=round(e2e_ms, 4))
       rows.append(row)
       print(json.dumps(row), flush=True)
+  if a.hotwords:
+    plain = {(r["W"], r["n"]): r["gpu_decode_ids_ms"] for r in rows if "lm" not in r}
+    with_lm = {(r["W"], r["n"]): r["gpu_decode_ids_ms"] for r in rows if "lm" in r}
+    for W, n in SHAPES:
+      dec = BeamCTCDecoder(labels, beam_width=W, cutoff_top_n=n, hotwords=random_hotwords(labels, a.hotwords),
+                           hotword_weight=a.hotword_weight, hotword_anchor=False)
+      gpu_ms, e2e_ms = time_gpu(dec, pd, a.iters)
+      row = dict(W=W, n=n, B=B, T=T, C=C, hotwords=a.hotwords, gpu_decode_ids_ms=round(gpu_ms, 4),
+                 gpu_decode_ms=round(e2e_ms, 4), plain_decode_ids_ms=plain[(W, n)])
+      rows.append(row)
+      print(json.dumps(row), flush=True)
+    for W, n in SHAPES if a.lm else []:
+      with warnings.catch_warnings():
+        warnings.simplefilter("ignore")   # random strings are no words of the model: only the lookups are timed
+        dec = BeamCTCDecoder(lm_labels, lm_path=a.lm, alpha=a.alpha, beta=a.beta, beam_width=W, cutoff_top_n=n,
+                             hotwords=random_hotwords(lm_labels, a.hotwords), hotword_weight=a.hotword_weight)
+      gpu_ms, e2e_ms = time_gpu(dec, pd, a.iters)
+      row = dict(W=W, n=n, B=B, T=T, C=C, hotwords=a.hotwords, lm=os.path.basename(a.lm),
+                 gpu_decode_ids_ms=round(gpu_ms, 4), gpu_decode_ms=round(e2e_ms, 4),
+                 plain_decode_ids_ms=with_lm[(W, n)])
+      rows.append(row)
+      print(json.dumps(row), flush=True)
   print("\n| W | n | GPU decode_ids ms | GPU decode() ms | CPU restatement ms (%d procs) |" % a.threads)
   print("|---|---|---|---|---|")
   for r in rows:
-    if "lm" in r:
+    if "lm" in r or "hotwords" in r:
       continue
     print("| %d | %d | %.3f | %.3f | %.1f |" % (r["W"], r["n"], r["gpu_decode_ids_ms"], r["gpu_decode_ms"],
                                                r["cpu_ref_ms"]))
   if a.lm:
     print("\nwith the language model %s:\n| W | n | GPU decode_ids ms | GPU decode() ms |\n|---|---|---|---|" % a.lm)
     for r in rows:
-      if "lm" in r:
+      if "lm" in r and "hotwords" not in r:
         print("| %d | %d | %.3f | %.3f |" % (r["W"], r["n"], r["gpu_decode_ids_ms"], r["gpu_decode_ms"]))
+  if a.hotwords:
+    print("\nwith %d hotwords:\n| W | n | LM | decode_ids ms, no hotwords | decode_ids ms, hotwords | ratio |\n"
+          "|---|---|---|---|---|---|" % a.hotwords)
+    for r in rows:
+      if "hotwords" in r:
+        print("| %d | %d | %s | %.3f | %.3f | %.2f |" % (r["W"], r["n"], r.get("lm", "-"), r["plain_decode_ids_ms"],
+                                                        r["gpu_decode_ids_ms"],
+                                                        r["gpu_decode_ids_ms"] / r["plain_decode_ids_ms"]))
 
 
 if __name__ == "__main__":
