@@ -262,6 +262,10 @@ int lr_sgemm(int transA, int transB, int M, int N, int K, float alpha, const flo
  *   b_ih, b_hh  D pointers -> [G*H]
  *   y      [B,T,D*H]      outputs (direction d in columns [d*H,(d+1)*H))
  *   h_n    [D,B,H]        final hidden state; c_n [D,B,H] (LSTM; may be NULL for GRU)
+ *                         h_n may be NULL: the final states are not extracted (one launch less; c_n is then ignored
+ *                         and may be NULL for an LSTM too) — y and every gradient are the same bits either way
+ *   I is any positive size and the W_ih pointers need no alignment: a layer whose I is no multiple of 4, or whose
+ *   W_ih is not 16-byte aligned, takes element loads in its input projection (tests/test_gpu_rnn_fp64.py)
  *   reserve               saved activations for the backward pass (lr_rnn_reserve_bytes)
  * Pointer arrays (w_ih ...) are HOST arrays of D device pointers. */
 int lr_rnn_pair_supported(int mode, int B, int T, int I, int H, int D);         /* see LR_RNN_RECUR_SPLIT: 2 or 0 */
