@@ -1145,6 +1145,73 @@ int lr_ctc_segment_phases(const float* log_probs, int64_t stride_b, int64_t stri
                           size_t workspace_bytes, int B, int T, int C, int max_tokens, float* phase_ms,
                           lr_stream_t stream);
 
+/* ---- A6h (BUILD-DEFINED, no reference symbol): N-best minimum error rate training of the CTC head --------------- */
+/* The reference trains the CTC head on the frame-synchronous likelihood alone; the specification is this build's
+ * (lipreading_amd/csrc/lr_nbest.hip), the yardstick a float64 torch restatement kept with the tests
+ * (tests/mwer_cases.py).  Per utterance b: n_b = sizes[b] frames (clamped into [0, T]) of fp32 log-probabilities
+ * lp[t][c] over C classes, a blank class, and N hypothesis slots; slot n holds a class-id string y_n of len_n ids and
+ * a risk r_n.
+ *   hyp_status [B][N]  LR_NBEST_USED (0);
+ *                      LR_NBEST_EMPTY (1): len_n < 0;
+ *                      LR_NBEST_REJECTED (2): len_n > max_hyp_len, an id inside the length outside [0, C) or equal to
+ *                        blank, or a non-finite r_n — such a slot reads nothing out of bounds;
+ *                      LR_NBEST_INFEASIBLE (3): no alignment of y_n fits n_b frames (n_b == 0, or n_b < len_n + the
+ *                        number of adjacent equal ids; also a lattice that -inf log-probabilities leave empty).
+ * Over the LR_NBEST_USED slots only:
+ *   ll_n   = log sum over alignments of prod_t p_t(.): the CTC recursion, a blank between repeats; len_n == 0 is
+ *            legal (all blank)
+ *   p_n    = exp(ll_n - logsumexp_m ll_m);   R_b = sum_n p_n r_n
+ *   U      = number of utterances with at least one used slot
+ *   loss   = sum_b R_b / max(U, 1) (LR_CTC_MEAN) or sum_b R_b (LR_CTC_SUM);  out_status[0] = 1 when U == 0: the loss
+ *            is then 0 with an all-zero gradient (lr_ctc_reduce's "skip this batch" contract)
+ *   grad[b][t][c] = g * w * sum_n p_n (r_n - R_b) occ_n(t, c) for t < n_b, exactly 0 for n_b <= t < T, where
+ *            occ_n(t, c) = d ll_n / d lp[t][c] is the posterior probability, under y_n's alignments, that frame t
+ *            emits class c;  g = grad_scale[0] (a DEVICE scalar, NULL = 1);  w = 1 / U (mean) or 1 (sum).  Every row
+ *            sums to 0 over c, so the gradient at the logits in front of a log_softmax is the same tensor; with one
+ *            used slot the coefficient, and the gradient, is exactly 0.
+ * Arguments:
+ *   log_probs   element (b,t,c) at log_probs[b*stride_b + t*stride_t + c];  sizes [B] int32 or NULL (= T)
+ *   hyps        int32 ids, slot (b,n)'s row at hyps + b*hyp_stride_b + n*hyp_stride_n (elements): `ids[:, :N]` of the
+ *               beam search's (B, W, T) output goes in as it is.  Ids past len_n are never read.
+ *   hyp_lens    slot (b,n)'s at hyp_lens[b*lens_stride_b + n];  risk [B][N] fp32
+ *   hyp_ll      [B][N] fp32, -inf where the status is not 0;  post [B][N] = p_n, 0 where the status is not 0
+ *   utt_risk    [B] = R_b (0 without a used slot);  out_loss [1], out_status [1]
+ *   grad_weight [B] = w for utterances with a used slot, 0 for the others
+ *   grad        addressed like log_probs; EVERY one of its B * T * C elements is written
+ * The lattices, the softmax and the occupancy sums are fp64 in log space; every sum has a fixed order and nothing is
+ * accumulated with atomics: two launches on the same inputs give bit-identical hyp_ll, loss and grad.
+ * Limits, from the arguments alone: N <= LR_NBEST_MAX_SLOTS, C <= LR_NBEST_MAX_CLASSES, max_hyp_len <=
+ * LR_NBEST_MAX_HYP_LEN, B, T >= 1, else LR_ERR_UNSUPPORTED before any launch. */
+#define LR_NBEST_MAX_SLOTS 16
+#define LR_NBEST_MAX_CLASSES 256
+#define LR_NBEST_MAX_HYP_LEN 256
+#define LR_NBEST_USED 0
+#define LR_NBEST_EMPTY 1
+#define LR_NBEST_REJECTED 2
+#define LR_NBEST_INFEASIBLE 3
+
+/* Workspace of the two entries below; 0 for arguments it rejects.  With S = 2 * max_hyp_len + 1 rounded up to 8:
+ * two fp64 tables (alpha, beta) of B * N * T * S cells behind 2 * B * N fp64 words (ll_n and p_n (r_n - R_b)). */
+size_t lr_ctc_nbest_workspace_bytes(int B, int T, int C, int N, int max_hyp_len);
+
+/* Two launches: B * N workgroups, one per (utterance, slot), walk alpha forwards and beta backwards side by side;
+ * one workgroup then takes the softmax over each utterance's slots, the expected risks and the loss. */
+int lr_ctc_nbest_risk(const float* log_probs, int64_t stride_b, int64_t stride_t, const int32_t* sizes,
+                      const int32_t* hyps, int64_t hyp_stride_b, int64_t hyp_stride_n, const int32_t* hyp_lens,
+                      int64_t lens_stride_b, const float* risk, int blank, int reduction, float* hyp_ll, float* post,
+                      int32_t* hyp_status, float* utt_risk, float* out_loss, int32_t* out_status, float* grad_weight,
+                      void* workspace, size_t workspace_bytes, int B, int T, int C, int N, int max_hyp_len,
+                      lr_stream_t stream);
+
+/* One launch, one workgroup per (utterance, frame): the same inputs, lr_ctc_nbest_risk's outputs and its workspace,
+ * unmodified.  Per frame the slots are added in slot order, a class's states in ascending order. */
+int lr_ctc_nbest_risk_grad(const float* log_probs, int64_t stride_b, int64_t stride_t, const int32_t* sizes,
+                           const int32_t* hyps, int64_t hyp_stride_b, int64_t hyp_stride_n, const int32_t* hyp_lens,
+                           int64_t lens_stride_b, const float* risk, int blank, int reduction, const float* hyp_ll,
+                           const float* post, const int32_t* hyp_status, const float* utt_risk,
+                           const float* grad_weight, const float* grad_scale, float* grad, void* workspace,
+                           size_t workspace_bytes, int B, int T, int C, int N, int max_hyp_len, lr_stream_t stream);
+
 /* ---- A8 (BUILD-DEFINED, no reference symbol): 3-D conv frontend on bf16 MFMA -------------- */
 /* The reference has no conv frontend (src/models/lipreader/model.py:122,153-156 are comments, the
  * `ced` configs are empty); BASELINE.json's north_star asks for one ("im2col + MFMA GEMM for the 3D

@@ -85,6 +85,12 @@ DEFAULTS = dict(  # train.py:134-167
     # with both ends free — one JSON object per line: the video, status, stream length, and per kept caption its text,
     # old and new times, confidence and worst character.  Needs a CTC head.
     segment="",
+    # --mwer=N (0 = off): train the encoder+CTC loop on the expected edit distance over the beam search's N best
+    # hypotheses (minimum word / character error rate, train.train_mwer) plus --mwer_ctc_weight times the
+    # CTC loss as an anchor.  --mwer_unit=char|word: the edit distance that is the risk.  --mwer_reference=True adds the
+    # reference transcript as one more hypothesis where no beam is exact.  Needs --ctc_decoder=beam and a CTC-only
+    # regime; the search is the evaluation's own (beam width, language model, hotwords).
+    mwer=0, mwer_ctc_weight=0.01, mwer_unit="char", mwer_reference=False,
 )
 
 
@@ -188,6 +194,7 @@ def parse_flags(argv, defaults=DEFAULTS):
   align_check(out)
   spot_check(out)
   segment_check(out)
+  mwer_check(out)
   return out
 
 
@@ -226,6 +233,28 @@ def segment_check(f):
   """ValueError for --segment without a CTC head (neither --enable_ctc nor a regime that is encoder + CTC)."""
   if f.get("segment") and not f.get("enable_ctc"):
     raise ValueError("--segment=%s needs a CTC head: --enable_ctc=True (or a CTC-only regime)" % f["segment"])
+
+
+def mwer_check(f):
+  """ValueError for --mwer outside the encoder+CTC loop or without the beam decoder, for an N the kernels or the
+  search cannot serve, and for a unit that is neither char nor word."""
+  if f.get("mwer_unit", "char") not in ("char", "word"):
+    raise ValueError("--mwer_unit must be char or word (got --mwer_unit=%r)" % (f["mwer_unit"],))
+  n = f.get("mwer") or 0
+  if not n:
+    return
+  if not (f.get("ctc_only") and f.get("enable_ctc")):
+    raise ValueError("--mwer=%d trains the encoder+CTC loop: it needs --ctc_only=True --enable_ctc=True (or a "
+                     "CTC-only regime)" % n)
+  if f.get("ctc_decoder") != "beam":
+    raise ValueError("--mwer=%d needs --ctc_decoder=beam: its hypotheses are the beam search's" % n)
+  slots = n + bool(f.get("mwer_reference"))
+  if n < 1 or slots > 16 or n > int(f.get("beam_width", 100)):
+    raise ValueError("--mwer=%d: between 1 and %d hypotheses%s, and no more than --beam_width=%s"
+                     % (n, 16 - bool(f.get("mwer_reference")), " beside the reference" * bool(f.get("mwer_reference")),
+                        f.get("beam_width")))
+  if not float(f.get("mwer_ctc_weight", 0.01)) >= 0.0:
+    raise ValueError("--mwer_ctc_weight must be >= 0 (got %r)" % (f["mwer_ctc_weight"],))
 
 
 def spot_check(f):
@@ -449,6 +478,7 @@ def run(**flags):
   align_check(f)
   spot_check(f)
   segment_check(f)
+  mwer_check(f)
   torch.manual_seed(f["seed"])
   rand = np.random.RandomState(seed=f["seed"])
   assert torch.cuda.is_available(), "the driver runs the HIP path: an MI355X is required (no CPU fallback)"
@@ -510,8 +540,14 @@ def run(**flags):
                                  hotword_weight=f["hotword_weight"], hotword_anchor=" " in labels)
 
   error_of = make_error_of(f, encoder, decoding_step, ctc_decoder, device, char2idx)
+  mwer = None
+  if f["mwer"]:
+    from .mwer import MWERLoss
+    mwer = MWERLoss(ctc_decoder, nbest=f["mwer"], unit=f["mwer_unit"], with_reference=f["mwer_reference"])
+    print("Training on the expected %s edit distance over %d beam hypotheses%s (CTC weight %g)"
+          % (f["mwer_unit"], f["mwer"], " and the reference" if f["mwer_reference"] else "", f["mwer_ctc_weight"]))
 
-  opt = tuple(FusedAdam(fl, lr=f["learning_rate"]) for fl in flats)
+  opt =tuple(FusedAdam(fl, lr=f["learning_rate"]) for fl in flats)
   if pixels and hasattr(encoder, "encoder"):
     # (single process, one backward per step: the sequence encoder's share of the clip's sum of squares is taken beside
     # the conv backward, optim.FusedAdam.sum_squares_early)
@@ -549,8 +585,15 @@ def run(**flags):
     print(f'\tCurrent Teacher Forcing Ratio: {tfr}')
     for o in opt:
       o.reset(lr)     # what re-creating Adam every epoch does (:275-276): moments and step count start over
-    dec_loss, ctc_loss = T.train(encoder, decoding_step, train_loader, opt[0] if ctc_only else opt, device, char2idx,
-                                 teacher_forcing_ratio=tfr, grad_norm=f["grad_norm"], graphs=graphs)
+    expected_risk = None
+    if mwer is not None:
+      expected_risk, ctc_loss = T.train_mwer(encoder, train_loader, opt[0], device, char2idx, mwer,
+                                             grad_norm=f["grad_norm"], ctc_weight=f["mwer_ctc_weight"])
+      dec_loss = 0.0
+      print(f'\tAVG Expected Risk: {expected_risk}')
+    else:
+      dec_loss, ctc_loss = T.train(encoder, decoding_step, train_loader, opt[0] if ctc_only else opt, device, char2idx,
+                                   teacher_forcing_ratio=tfr, grad_norm=f["grad_norm"], graphs=graphs)
     print(f'\tAVG Decoder Loss: {dec_loss}')
     print(f'\tAVG CTC Loss: {ctc_loss}')
     val_cer = error_of(val_loader)
@@ -569,6 +612,8 @@ def run(**flags):
                         # batches that updated nothing (the reference's `continue`, train_better_model.py:49-50) and how
                         # many of them because a one-launch recurrence timed out
                         skipped_batches=stats.get("skipped", 0), recurrence_faults=stats.get("recurrence_faults", 0)))
+    if expected_risk is not None:
+      history[-1]["expected_risk"] = expected_risk
     if val_scores is not None:
       history[-1]["val_wer"] = val_scores["wer"]
       print(f'\tVal WER: {val_scores["wer"]}')

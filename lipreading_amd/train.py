@@ -334,6 +334,75 @@ def ctc_step(encoder, opt, frames, frame_lens, chars, char_lens, grad_norm=None,
   return loss, status
 
 
+def mwer_step(encoder, opt, mwer, frames, frame_lens, chars, char_lens, grad_norm=None, max_len=None, ctc_weight=0.01,
+              grad_sync=None):
+  """One encoder+CTC optimisation step on the N-best expected risk, anchored by the CTC likelihood:
+  loss = mwer(log_probs) + ctc_weight * ctc_loss('mean') (lipreading_amd/mwer.py).  `mwer` is an
+  mwer.MWERLoss over ctc_labels(char2idx); the references are the CTC labels themselves (chars[:, 1:] + 1).
+
+  Eager, and without a host read: search -> score -> loss -> backward -> Adam are all enqueued; Adam is skipped on the
+  device when either loss reports a batch to skip (the OR of the two status words) or a recurrence timed out (the
+  fault word, inside FusedAdam.step as in ctc_step).  Returns (expected risk, ctc loss, status, info): device tensors,
+  `info` the MWERLoss's dict plus the step's `log_probs` (detached)."""
+  if grad_sync is not None:
+    raise NotImplementedError("data-parallel MWER is not built: the N-best lists differ from rank to rank and the "
+                              "step has no exchange for its skip word; run mwer_step in a single process")
+  dev = frames.device
+  frame_lens, chars, char_lens = frame_lens.to(dev), chars.to(dev), char_lens.to(dev)
+  if (chars.dtype == torch.int64 and frame_lens.dtype == torch.int64 and char_lens.dtype == torch.int64
+      and chars.dim() == 2 and chars.stride(1) == 1):
+    labels_p1, frame_lens32, label_lens32 = opt.zero_grad_and_prepare_ctc(chars, frame_lens, char_lens)
+  else:
+    opt.zero_grad()
+    labels_p1 = (chars[:, 1:] + 1).to(torch.int32).contiguous()
+    frame_lens32, label_lens32 = frame_lens.to(torch.int32), (char_lens - 1).to(torch.int32)
+  log_probs, _, _ = encoder(frames, frame_lens32, max_len=max_len, need_final_state=False)
+  ctc, ctc_status, _ = ctc_loss_prepared(log_probs, labels_p1, frame_lens32, label_lens32, 'mean')
+  risk, mwer_status, info = mwer(log_probs, frame_lens32, labels_p1, label_lens32)
+  status = ctc_status | mwer_status
+  info["log_probs"] = log_probs.detach().clone()   # (a copy: the encoder may reuse the buffer in its backward)
+  (risk + ctc_weight * ctc).backward(_one(dev))
+  opt.step(grad_norm=grad_norm, grad_scale=1.0, skip=status)
+  return risk.detach(), ctc.detach(), status, info
+
+
+def train_mwer(encoder, data_loader, opt, device, char2idx, mwer, grad_norm=None, ctc_weight=0.01):
+  """An epoch of mwer_step over `data_loader`: the encoder+CTC branch of train() with the N-best expected risk as the
+  objective.  Prints and returns (mean expected risk, mean CTC loss) over len(data_loader); a skipped batch adds 0 to
+  both, as in train()."""
+  assert encoder.enable_ctc, "MWER trains the CTC head: the encoder must have enable_ctc=True"
+  assert isinstance(opt, FusedAdam), "opt must be lipreading_amd.optim.FusedAdam"
+  device = torch.device(device)
+  encoder.train()
+  risk_sum = torch.zeros((), dtype=torch.float32, device=device)
+  ctc_sum = torch.zeros((), dtype=torch.float32, device=device)
+  skipped_before = opt.skipped_steps()
+  watch = RecurrenceWatch(device)
+  for frames, frame_lens, chars, char_lens in data_loader:
+    _check_framing(chars, char_lens, frame_lens, char2idx, True)
+    max_len = host_max_len(frame_lens)
+    frames, chars = frames.to(device, non_blocking=True), chars.to(device, non_blocking=True)
+    frame_lens_d, char_lens_d = frame_lens.to(device, non_blocking=True), char_lens.to(device, non_blocking=True)
+    risk, ctc, status, _ = mwer_step(encoder, opt, mwer, frames, frame_lens_d, chars, char_lens_d, grad_norm=grad_norm,
+                                     max_len=max_len, ctc_weight=ctc_weight)
+    keep = status.reshape(()) == 0
+    risk_sum += torch.where(keep, risk, torch.zeros_like(risk))
+    ctc_sum += torch.where(keep, ctc, torch.zeros_like(ctc))
+    watch.after_step(None)
+  avg_risk = (risk_sum / len(data_loader)).item()
+  avg_ctc = (ctc_sum / len(data_loader)).item()
+  global last_epoch_stats
+  faults = int(_C.lib().lr_rnn_pair_errors())
+  last_epoch_stats = {"batches": len(data_loader), "skipped": opt.skipped_steps() - skipped_before,
+                      "recurrence_faults": faults}
+  if last_epoch_stats["skipped"] or faults:
+    print("\tSkipped batches: %(skipped)d of %(batches)d (recurrence time-outs: %(recurrence_faults)d)"
+          % last_epoch_stats)
+  print(f'\tTraining expected risk: {avg_risk}')
+  print(f'\tTraining ctc_loss: {avg_ctc}')
+  return avg_risk, avg_ctc
+
+
 # test hook / switch: False keeps the CTC branch of a decoder step on the step's own stream
 overlap_ctc_branch = True
 _ctc_side = None
