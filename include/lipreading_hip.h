@@ -231,6 +231,53 @@ int lr_lip_stable_collate_u8(const void* frames, const float* lmk, const int64_t
                              int lo, int hi, int ea_lo, int ea_hi, int eb_lo, int eb_hi, float extent, int radius,
                              lr_stream_t stream);
 
+/* ---- Landmark pose: every frame's landmarks aligned to a canonical face inside the collate launch (BUILD-DEFINED) - */
+
+/* lr_collate_pad_aug_f32's batch with the head's translation, rotation and (optionally) scale taken out of every
+ * frame: a rigid or similarity alignment to the template `tmpl`, estimated from points that do not move with speech
+ * (`rigid`: nose bridge, eye corners) and applied to all npts points.
+ *   lmk     f32 [rows][npts][3]  samples back to back;  offsets, lens, tmap, t_max as in lr_collate_pad_aug_f32
+ *           (tmap may be NULL: the identity)
+ *   tmpl    f32 [npts][3]        the canonical face, on the device
+ *   rigid_host                   HOST array of n_rigid distinct point indices (handed to the kernel by value)
+ *   radius                       half-width of the smoothing window;  flags & LR_POSE_SCALE: similarity, else s = 1
+ * All arithmetic is float64, inputs widened from fp32, every output value rounded to fp32 once.
+ *   per source row n, p_i = lmk[n][rigid[i]], q_i = tmpl[rigid[i]]:  pbar_n, qbar = the means over i;
+ *     M_n = sum_i (q_i - qbar)(p_i - pbar_n)^T  (3x3);  v_n = sum_i |p_i - pbar_n|^2;
+ *     a row with a non-finite value among its npts*3 coordinates is BAD.
+ *   window, row n = row i of a sample of len rows: M~_n, v~_n = the sums of M_m, v_m over the non-BAD rows m in
+ *     max(0,i-radius) .. min(len-1,i+radius) of the same sample, ascending.  The window never leaves the sample.
+ *     The translation is not smoothed: it is row n's own pbar_n.
+ *   solve: R~_n = the proper rotation (det = +1) that maximises tr(R M~_n^T) — for M~ = U S V^T,
+ *     R = U diag(1, 1, det(U V^T)) V^T;  s~_n = tr(R~_n M~_n^T) / v~_n with LR_POSE_SCALE, else 1.  (Here: the
+ *     eigenvector of Horn's 4x4 symmetric matrix with the largest eigenvalue, by a fixed number of cyclic Jacobi
+ *     sweeps.)  Where the maximiser is not unique (collinear rigid points) any maximiser may come out; it is finite.
+ *   out[b][t][j][:] = fp32( s~_n R~_n (lmk[n][j] - pbar_n) + qbar ), n = offsets[b] + min(m, lens[b]-1),
+ *     m = tmap[offsets[b]+t];  zeros for t >= min(lens[b], t_max), for m < 0 and for a BAD source row.  EVERY element
+ *     of out is written.
+ *   status int32 [rows]: LR_POSE_OK the row was normalised; LR_POSE_DEGENERATE the window has no usable row or
+ *     v~_n == 0, then R = I and s = 1; LR_POSE_BAD_ROW the row has a non-finite coordinate.
+ *   pose   f32 [rows][13] or NULL: R~ row-major, s~, pbar (a BAD row: I, 1, 0).  pose and status cover every row of
+ *     every sample, whatever tmap says (as lr_lip_stable_collate_u8's pose).
+ *   workspace lr_lmk_pose_workspace_bytes(rows, n_rigid, radius) bytes, 16-byte aligned.
+ * Every sum has a fixed order and there are no atomics: two launches give the same bits, and a batch gives the bits of
+ * B one-sample calls.  Errors, all before any launch: 3 <= n_rigid <= LR_POSE_MAX_RIGID, 1 <= npts <=
+ * LR_POSE_MAX_POINTS, 0 <= radius <= LR_POSE_MAX_RADIUS or an unknown flag bit -> LR_ERR_UNSUPPORTED; a rigid index
+ * outside [0, npts) or a repeated one, a NULL required pointer, rows > 2^31-1 -> LR_ERR_INVALID_ARG; LR_ERR_WORKSPACE.
+ * Two launches: the rows' statistics (one wave per row), then one wave per (sample, frame). */
+#define LR_POSE_MAX_RADIUS 32
+#define LR_POSE_MAX_RIGID 64
+#define LR_POSE_MAX_POINTS 256
+#define LR_POSE_SCALE 1
+#define LR_POSE_OK 0
+#define LR_POSE_DEGENERATE 1
+#define LR_POSE_BAD_ROW 2
+size_t lr_lmk_pose_workspace_bytes(int64_t rows, int n_rigid, int radius); /* 0 for arguments it rejects */
+int lr_lmk_pose_collate_f32(const float* lmk, const int64_t* offsets, const int32_t* lens, const int32_t* tmap,
+                            const float* tmpl, const int32_t* rigid_host, int n_rigid, float* out, float* pose,
+                            int32_t* status, void* workspace, size_t workspace_bytes, int B, int64_t rows, int t_max,
+                            int npts, int radius, int flags, lr_stream_t stream);
+
 /* ---- dense fp32 contraction (MFMA f32 16x16x4 / 32x32x2), used by A3 ------------------- */
 
 /* C[M,N] = alpha * op(A)[M,K] * op(B)[K,N] + beta * C + bias[N]   (row-major, fp32)

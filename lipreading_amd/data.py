@@ -32,8 +32,9 @@ def host_max_len(frame_lens):
   return int(frame_lens.max()) if not frame_lens.is_cuda else None
 
 
-def pad_frames(seqs, device):
-  """(len_i, ...) float sequences -> ((B, Tmax, ...) float32 on `device`, lens int64)."""
+def pad_frames(seqs, device, pose=None):
+  """(len_i, ...) float sequences -> ((B, Tmax, ...) float32 on `device`, lens int64).  pose: a landmarks.PoseSpec;
+  the one launch is then lr_lmk_pose_collate_f32 (every frame aligned to the spec's template) on the same upload."""
   assert len(seqs) > 0
   arrs = [np.asarray(s, dtype=np.float32) for s in seqs]
   tail = arrs[0].shape[1:]
@@ -49,6 +50,13 @@ def pad_frames(seqs, device):
   packed_d = packed.to(dev, non_blocking=True)
   off_d = torch.from_numpy(offsets).to(dev, non_blocking=True)
   lens_d = torch.from_numpy(lens.astype(np.int32)).to(dev, non_blocking=True)
+  if pose is not None:
+    from .landmarks import pose_collate
+    if tuple(tail) != (pose.npts, 3):
+      raise ValueError("pose normalisation takes (len, %d, 3) landmarks, got (len,) + %r" % (pose.npts, tuple(tail)))
+    with torch.cuda.device(dev):
+      out = pose_collate(packed_d.view(-1, pose.npts, 3), off_d, lens_d, t_max, pose)
+    return out, torch.from_numpy(lens)
   out = torch.empty((B, t_max, feat), dtype=torch.float32, device=dev)
   with torch.cuda.device(dev):
     _C.check(_C.lib().lr_collate_pad_f32(packed_d.data_ptr(), off_d.data_ptr(), lens_d.data_ptr(),
@@ -57,14 +65,16 @@ def pad_frames(seqs, device):
   return out.reshape((B, t_max) + tuple(tail)), torch.from_numpy(lens)
 
 
-def make_collate_fn(device):
+def make_collate_fn(device, pose=None):
   """Returns a `_collate_fn(batch)` with the reference's contract (data_loader.py:117-152):
   batch = [(frames (len,68,3), caption (n,))] -> (frames f32 (B,Tmax,68,3), frame_lens i64,
-  chars i64 (B,Cmax) PAD=0, char_lens i64); frames live on `device`, chars and both lens on the host."""
+  chars i64 (B,Cmax) PAD=0, char_lens i64); frames live on `device`, chars and both lens on the host.
+  pose: a landmarks.PoseSpec (BUILD-DEFINED; None: the reference's raw landmarks): every frame's head pose is taken out
+  inside the collate launch (lr_lmk_pose_collate_f32)."""
   def _collate_fn(batch):
     assert all(len(x) == 2 for x in batch)
     frames, captions = zip(*batch)
-    src, src_lens = pad_frames(frames, device)
+    src, src_lens = pad_frames(frames, device, pose=pose)
     caps = [np.asarray(c, dtype=np.int64) for c in captions]
     tgt_lens = torch.tensor([len(c) for c in caps], dtype=torch.long)
     tgt = torch.zeros((len(caps), int(tgt_lens.max())), dtype=torch.long)

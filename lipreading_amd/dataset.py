@@ -292,10 +292,12 @@ class BatchLoader(object):
     return iterate_batches(self.dataset, self.batch_size, self.collate_fn)
 
 
-def make_loader(dataset, batch_size, collate_fn, prefetch=0, augment=None, **loader_args):
+def make_loader(dataset, batch_size, collate_fn, prefetch=0, augment=None, pose=None, **loader_args):
   """prefetch=0: the plain BatchLoader over `collate_fn`.  prefetch=N > 0: a loader.PrefetchLoader of depth N that
   yields the same batches (loader_args: device, pixels, size, margin, workers, crop, extent, radius — what `collate_fn`
   was made with).
+  pose: the landmarks.PoseSpec `collate_fn` was made with (data.make_collate_fn(device, pose=...)); the prefetch
+  loader normalises inside its own collate launch.
   augment: an augment.AugmentSpec for a TRAINING loader; it is applied inside the prefetch loader's collate launch,
   so it needs prefetch > 0."""
   if augment is not None and not prefetch:
@@ -304,6 +306,8 @@ def make_loader(dataset, batch_size, collate_fn, prefetch=0, augment=None, **loa
     return BatchLoader(dataset, batch_size, collate_fn)
   if augment is not None:
     loader_args["augment"] = augment
+  if pose is not None:
+    loader_args["pose"] = pose
   from .loader import PrefetchLoader
   return PrefetchLoader(dataset, batch_size, depth=int(prefetch), **loader_args)
 

@@ -66,6 +66,13 @@ DEFAULTS = dict(  # train.py:134-167
     # (lr_lip_crop_u8).  stable: centre = the mouth points' mean, side = --crop_extent eye distances, axes along the
     # line between the eyes, all averaged over 2 * --crop_smooth + 1 frames (lr_lip_stable_collate_u8)
     crop="box", crop_extent=1.25, crop_smooth=2,
+    # --lmk_pose=none|rigid|similarity: the landmark regime's counterpart, for the train, validation and test loaders
+    # alike.  Every frame's landmarks are aligned to a canonical face inside the collate launch
+    # (lr_lmk_pose_collate_f32, landmarks.PoseSpec): the head's translation and rotation (rigid) and also its scale
+    # (similarity) are taken out, estimated from the nose bridge and the eye corners over 2 * --lmk_pose_smooth + 1
+    # frames.  --lmk_pose_template=PATH.npy: the canonical face (68, 3); loaded when the file exists, otherwise fitted
+    # from the training set (landmarks.fit_template) and written there ('' = fitted, not written)
+    lmk_pose="none", lmk_pose_smooth=0, lmk_pose_template="",
     # who scores the transcripts behind the edit-distance errors (greedy, --ctc_decoder=beam, --attn_decode=beam|joint):
     # host (the Python loops of train.greedy_cer / ctc_cer / attention_cer) or device (train.device_scores: the ids
     # never leave the GPU, lr_edit_distance scores them, one read per loader; the epoch summary then carries val_wer)
@@ -191,6 +198,7 @@ def parse_flags(argv, defaults=DEFAULTS):
         out[name] = True
   augment_spec(out)
   crop_check(out)
+  lmk_pose_check(out)
   align_check(out)
   spot_check(out)
   segment_check(out)
@@ -221,6 +229,50 @@ def crop_check(f):
     if not (isinstance(smooth, int) and 0 <= smooth <= 32):
       raise ValueError("--crop_smooth must be in [0, 32] frames (got %r)" % (smooth,))
   return crop
+
+
+def lmk_pose_check(f):
+  """ValueError for a --lmk_pose that is none of none, rigid and similarity, for a --lmk_pose_smooth outside [0, 32] and
+  for --lmk_pose in the pixel regime, which feeds no landmarks to the encoder."""
+  mode = f.get("lmk_pose", "none")
+  if mode not in ("none", "rigid", "similarity"):
+    raise ValueError("--lmk_pose must be none, rigid or similarity (got --lmk_pose=%r)" % (mode,))
+  if mode == "none":
+    return mode
+  smooth = f.get("lmk_pose_smooth", 0)
+  if isinstance(smooth, bool) or not (isinstance(smooth, int) and 0 <= smooth <= 32):
+    raise ValueError("--lmk_pose_smooth must be in [0, 32] frames (got %r)" % (smooth,))
+  if f.get("frontend", "none") == "conv3d":
+    raise ValueError("--lmk_pose=%s normalises the landmarks the encoder reads; --frontend=conv3d reads mouth crops "
+                     "(its counterpart is --crop=stable)" % mode)
+  return mode
+
+
+def lmk_pose_spec(f, train_set, device):
+  """The PoseSpec of the flags `f` (None for --lmk_pose=none).  The template is loaded from --lmk_pose_template when
+  that file exists; otherwise it is fitted from `train_set`'s clips and written there (under torch.distributed by rank
+  0 only).  One printed line says which."""
+  if lmk_pose_check(f) == "none":
+    return None
+  from .landmarks import PoseSpec, fit_template
+  path = f.get("lmk_pose_template") or ""
+  if path and os.path.isfile(path):
+    template = np.load(path, allow_pickle=False)
+    if template.shape != (68, 3):
+      raise ValueError("--lmk_pose_template=%s holds shape %r, not (68, 3)" % (path, tuple(template.shape)))
+    print("Landmark pose: %s, template loaded from %s" % (f["lmk_pose"], path))
+  else:
+    template = fit_template(train_set.frames, device=device)
+    writer = not (torch.distributed.is_available() and torch.distributed.is_initialized()
+                  and torch.distributed.get_rank() != 0)
+    if path and writer:
+      if os.path.dirname(path):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+      with open(path, "wb") as fh:           # (np.save(path) would append .npy to another extension)
+        np.save(fh, template)
+    print("Landmark pose: %s, template fitted from %d training clips%s"
+          % (f["lmk_pose"], len(train_set.frames), " and written to %s" % path if path and writer else ""))
+  return PoseSpec(template, radius=int(f.get("lmk_pose_smooth", 0)), scale=f["lmk_pose"] == "similarity")
 
 
 def align_check(f):
@@ -472,6 +524,7 @@ def run(**flags):
   f.update(flags)
   augment = augment_spec(f)
   crop_check(f)
+  lmk_pose_check(f)
   if f["frontend"] != "none" or f["encoder"] != "rnn":
     # the build-defined regimes are encoder + CTC with greedy CER (parse_flags sets the same for flag files)
     f["enable_ctc"], f["ctc_only"] = flags.get("enable_ctc", True), flags.get("ctc_only", True)
@@ -493,6 +546,7 @@ def run(**flags):
                               refresh=f["refresh"], pixels=pixels)
           for name, ids in zip(("train", "val", "test"), splits)]
   char2idx = sets[0].char2idx
+  pose = None
   if pixels:
     # u8 frames + landmarks -> mouth crops (B, Tmax, 3, S, S) on the GPU (lr_lip_crop_u8)
     from .data import make_pixel_collate_fn
@@ -502,11 +556,14 @@ def run(**flags):
       print("Mouth crops: %s (extent %g eye distances, smoothed over %d frames)" %
             (f["crop"], f["crop_extent"], 2 * f["crop_smooth"] + 1))
   else:
-    collate = make_collate_fn(device)   # padded on the GPU (lr_collate_pad_f32); lengths stay on the host
-  # only the train loader is augmented; validation and test clips are served as they are.  The crop is one for all three
+    pose = lmk_pose_spec(f, sets[0], device)
+    # padded on the GPU (lr_collate_pad_f32, or lr_lmk_pose_collate_f32 with --lmk_pose); lengths stay on the host
+    collate = make_collate_fn(device, pose=pose) if pose is not None else make_collate_fn(device)
+  # only the train loader is augmented; validation and test clips are served as they are.  The crop and the landmark
+  # pose are one for all three
   train_loader, val_loader, test_loader = (make_loader(d, f["batch_size"], collate, prefetch=f["prefetch"], device=device,
                                                        pixels=pixels, size=f["crop_size"], crop=f["crop"],
-                                                       extent=f["crop_extent"], radius=f["crop_smooth"],
+                                                       extent=f["crop_extent"], radius=f["crop_smooth"], pose=pose,
                                                        augment=augment if d is sets[0] else None) for d in sets)
   if augment is not None:
     print("Augmenting the training clips: %s (seed %d)" % (augment, augment.seed))

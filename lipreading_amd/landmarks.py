@@ -11,9 +11,13 @@ The reference does this per frame in NumPy inside the offline ETL; here whole cl
 launch so the step can sit in front of the encoder on the GPU.  dlib / PRNet inference itself is out
 of scope (third-party nets, weights not shipped): `landmark_step` takes the network's position maps.
 """
+import ctypes
+
+import numpy as np
 import torch
 
 from . import _C
+from ._host import PerDevice
 
 _mouth = slice(48, 68)  # face.py:21 (defined, unused by the reference as well)
 
@@ -178,3 +182,168 @@ def lip_crop_stable(frames, lmks, size=96, extent=1.25, radius=2, mouth=_mouth, 
   with torch.cuda.device(f.device):
     out = stable_crop_collate(f, l, offsets, lens, n, size, extent, radius, mouth=mouth, eyes=eyes, pose=pose)[0]
   return (out, pose) if return_pose else out
+
+
+# ---- head-pose normalisation (include/lipreading_hip.h, "Landmark pose") ------------------------------
+RIGID_68 = (27, 28, 29, 30, 33, 36, 39, 42, 45)   # nose bridge, nose base and the four eye corners
+
+
+class PoseSpec(object):
+  """What lr_lmk_pose_collate_f32 aligns to and how: the canonical face `template` (npts, 3), the indices `rigid` of
+  the points the alignment is estimated from, the half-width `radius` of the smoothing window (frames either side) and
+  `scale` (True: similarity, False: rigid).  Validated on the host: a ValueError carries the offending value.  The
+  template is uploaded once per device."""
+
+  def __init__(self, template, rigid=RIGID_68, radius=0, scale=True):
+    t = np.array(template.detach().cpu().numpy() if torch.is_tensor(template) else template, dtype=np.float32)
+    if t.ndim != 2 or t.shape[1] != 3 or not 1 <= t.shape[0] <= _C.LR_POSE_MAX_POINTS:
+      raise ValueError("template must be (npts, 3) with 1 <= npts <= %d, got shape %r"
+                       % (_C.LR_POSE_MAX_POINTS, tuple(t.shape)))
+    if not np.isfinite(t).all():
+      raise ValueError("template has a non-finite coordinate at point %d" % int(np.argwhere(~np.isfinite(t))[0][0]))
+    try:
+      rigid = tuple(int(i) for i in rigid)
+    except (TypeError, ValueError):
+      raise ValueError("rigid must be a sequence of point indices, got %r" % (rigid,))
+    if not 3 <= len(rigid) <= _C.LR_POSE_MAX_RIGID:
+      raise ValueError("rigid must name 3 .. %d points, got %d" % (_C.LR_POSE_MAX_RIGID, len(rigid)))
+    for i in rigid:
+      if not 0 <= i < t.shape[0]:
+        raise ValueError("rigid index %d is outside [0, %d)" % (i, t.shape[0]))
+      if rigid.count(i) > 1:
+        raise ValueError("rigid index %d is repeated" % i)
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= _C.LR_POSE_MAX_RADIUS:
+      raise ValueError("radius must be an integer in [0, %d], got %r" % (_C.LR_POSE_MAX_RADIUS, radius))
+    t.setflags(write=False)
+    self.template, self.npts, self.rigid, self.radius, self.scale = t, int(t.shape[0]), rigid, radius, bool(scale)
+    self.flags = _C.LR_POSE_SCALE if self.scale else 0
+    self._rigid_c = (ctypes.c_int32 * len(rigid))(*rigid)     # the HOST array the entry reads
+    self.rigid_ptr = ctypes.addressof(self._rigid_c)
+    self._dev = PerDevice()
+
+  def template_on(self, dev):
+    return self._dev.get(dev, lambda d: torch.from_numpy(self.template.copy()).to(d))
+
+  def workspace_bytes(self, rows):
+    return int(_C.lib().lr_lmk_pose_workspace_bytes(int(rows), len(self.rigid), self.radius))
+
+  def __repr__(self):
+    return "PoseSpec(npts=%d, rigid=%r, radius=%d, scale=%r)" % (self.npts, self.rigid, self.radius, self.scale)
+
+
+def pose_collate(lmks, offsets, lens, t_max, spec, tmap=None, return_pose=False, workspace=None):
+  """lr_lmk_pose_collate_f32 on device tensors, the twin of `stable_crop_collate`: ragged landmarks f32 (rows,npts,3),
+  offsets i64 (B,), lens i32 (B,) -> the padded, pose-normalised batch f32 (B,t_max,npts,3) in ONE call.  tmap i32
+  (rows,) or None (identity).  return_pose: also pose f32 (rows,13) = (R row-major, s, centroid) and status i32 (rows,)
+  of every row.  workspace: a u8 tensor of spec.workspace_bytes(rows) bytes (allocated when None)."""
+  _C.require_cuda(lmks, offsets, lens, tmap)
+  L = _C.lib()
+  if lmks.dim() != 3 or tuple(lmks.shape[1:]) != (spec.npts, 3) or lmks.dtype != torch.float32:
+    raise ValueError("landmarks must be float32 (rows, %d, 3), got %s %r" % (spec.npts, lmks.dtype, tuple(lmks.shape)))
+  assert lmks.is_contiguous() and offsets.dtype == torch.int64 and lens.dtype == torch.int32
+  assert tmap is None or (tmap.dtype == torch.int32 and tmap.shape == (lmks.shape[0],))
+  rows, B, dev = lmks.shape[0], offsets.shape[0], lmks.device
+  if workspace is None:
+    workspace = torch.empty(max(spec.workspace_bytes(rows), 16), dtype=torch.uint8, device=dev)
+  out = torch.empty((B, int(t_max), spec.npts, 3), dtype=torch.float32, device=dev)
+  status = torch.empty((rows,), dtype=torch.int32, device=dev)
+  pose = torch.empty((rows, 13), dtype=torch.float32, device=dev) if return_pose else None
+  _C.check(L.lr_lmk_pose_collate_f32(lmks.data_ptr(), offsets.data_ptr(), lens.data_ptr(), _C.ptr(tmap),
+                                     spec.template_on(dev).data_ptr(), spec.rigid_ptr, len(spec.rigid), out.data_ptr(),
+                                     _C.ptr(pose), status.data_ptr(), workspace.data_ptr(), workspace.numel(), B, rows,
+                                     int(t_max), spec.npts, spec.radius, spec.flags, _C.stream_handle()),
+           "lr_lmk_pose_collate_f32")
+  return (out, pose, status) if return_pose else out
+
+
+def normalise_pose(lmks, spec, return_pose=False):
+  """One clip: landmarks (n,npts,3) on the device -> the clip aligned to spec.template, f32 (n,npts,3); with
+  return_pose also pose (n,13) and status (n,) (see `pose_collate`)."""
+  _C.require_cuda(lmks)
+  if lmks.dim() != 3 or lmks.shape[0] < 1:
+    raise ValueError("a clip is (n >= 1, npts, 3), got %r" % (tuple(lmks.shape),))
+  l = lmks.to(torch.float32).contiguous()
+  n = l.shape[0]
+  offsets = torch.zeros(1, dtype=torch.int64, device=l.device)
+  lens = torch.full((1,), n, dtype=torch.int32, device=l.device)
+  with torch.cuda.device(l.device):
+    got = pose_collate(l, offsets, lens, n, spec, return_pose=return_pose)
+  return (got[0][0], got[1], got[2]) if return_pose else got[0]
+
+
+def canonical_orientation(points):
+  """The host half of `fit_template`, float64: (68,3) points -> the same points about their origin in the face's own
+  axes.  x runs along the mean of points 42..47 minus the mean of points 36..41 (eye to eye), y from the eyes' midpoint
+  to the mean of points 48..67 (the mouth), orthogonalised against x, z = x × y.  ValueError when the three anchor
+  means are collinear (or coincide)."""
+  p = np.asarray(points, dtype=np.float64)
+  if p.shape != (68, 3):
+    raise ValueError("the orientation is defined on the 68-point scheme, got shape %r" % (tuple(p.shape),))
+  eye_a, eye_b, mouth = p[36:42].mean(axis=0), p[42:48].mean(axis=0), p[48:68].mean(axis=0)
+  x = eye_b - eye_a
+  y = mouth - 0.5 * (eye_a + eye_b)
+  nx, ny = np.linalg.norm(x), np.linalg.norm(y)
+  if not (nx > 0 and ny > 0):
+    raise ValueError("the eye and mouth anchor means coincide: %r %r %r" % (eye_a, eye_b, mouth))
+  x = x / nx
+  y = y - (y @ x) * x
+  if not np.linalg.norm(y) > 1e-9 * ny:
+    raise ValueError("the eye and mouth anchor means are collinear: %r %r %r" % (eye_a, eye_b, mouth))
+  y = y / np.linalg.norm(y)
+  z = np.cross(x, y)
+  return p @ np.stack([x, y, z], axis=1)
+
+
+def _rigid_frame(points, rigid):
+  """points (..., npts, 3) float64 -> (points about their rigid centroid, the rigid RMS radius)."""
+  c = points[..., list(rigid), :].mean(axis=-2, keepdims=True)
+  d = points - c
+  return d, np.sqrt((d[..., list(rigid), :] ** 2).sum(axis=-1).mean(axis=-1))
+
+
+def fit_template(clips, rigid=RIGID_68, iters=3, max_frames=20000, device=None):
+  """Generalised Procrustes on the device: the canonical face of a set of clips [(len_i,68,3)], as (68,3) float32.
+  Start from the first frame about its rigid centroid; `iters` times align the first `max_frames` frames (dataset
+  order) to the current template with `pose_collate` (radius 0, scale on), average in float64, re-centre on the rigid
+  centroid and rescale so that the rigid RMS radius is the mean rigid RMS radius of the raw frames (magnitudes stay in
+  the pixels range the reference feeds); then `canonical_orientation` on the host."""
+  dev = torch.device("cuda" if device is None else device)
+  if dev.type != "cuda":
+    raise _C.LipReadingHipError("the template is fitted on the MI355X only (no CPU fallback)")
+  if iters < 1 or max_frames < 1:
+    raise ValueError("iters and max_frames must be positive, got %r and %r" % (iters, max_frames))
+  rows, left = [], int(max_frames)
+  for c in clips:
+    if left <= 0:
+      break
+    a = np.asarray(c.detach().cpu().numpy() if torch.is_tensor(c) else c, dtype=np.float32)[:left]
+    if a.ndim != 3 or a.shape[1:] != (68, 3):
+      raise ValueError("a clip is (len, 68, 3), got shape %r" % (tuple(a.shape),))
+    rows.append(a)
+    left -= len(a)
+  if not rows or not sum(len(a) for a in rows):
+    raise ValueError("no frame to fit the template from")
+  frames = np.ascontiguousarray(np.concatenate(rows))
+  good = np.isfinite(frames).all(axis=(1, 2))
+  if not good.any():
+    raise ValueError("every frame has a non-finite coordinate")
+  first = int(np.argmax(good))
+  target = float(_rigid_frame(frames[good].astype(np.float64), rigid)[1].mean())
+  tmpl = _rigid_frame(frames[first].astype(np.float64), rigid)[0]
+  n = len(frames)
+  with torch.cuda.device(dev):
+    frames_d = torch.from_numpy(frames).to(dev)
+    offsets = torch.zeros(1, dtype=torch.int64, device=dev)
+    lens = torch.full((1,), n, dtype=torch.int32, device=dev)
+    for _ in range(int(iters)):
+      spec = PoseSpec(tmpl.astype(np.float32), rigid=rigid, radius=0, scale=True)
+      out, _, status = pose_collate(frames_d, offsets, lens, n, spec, return_pose=True)
+      keep = (status == _C.LR_POSE_OK).cpu().numpy()
+      if not keep.any():
+        raise ValueError("no frame could be aligned (the rigid points of every frame, or of the template, coincide)")
+      mean = out[0].cpu().numpy()[keep].astype(np.float64).mean(axis=0)
+      d, radius = _rigid_frame(mean, rigid)
+      if not radius > 0:
+        raise ValueError("the rigid points of the mean face coincide")
+      tmpl = d * (target / radius)
+  return canonical_orientation(tmpl).astype(np.float32)

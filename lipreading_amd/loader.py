@@ -14,6 +14,10 @@ stream and off the step's critical path:
 With `crop="stable"` the pixel launch is lr_lip_stable_collate_u8 (the stabilised, roll-corrected window of
 landmarks.lip_crop_stable), augmented or not; its workspace lies behind the slot's device bytes.
 
+With `pose=PoseSpec(...)` (landmarks.py) the landmark launch is lr_lmk_pose_collate_f32 — every frame aligned to the
+spec's canonical face — with the batch's frame map when the batch is augmented; its workspace and status words lie behind
+the slot's device bytes as well.  A loader built without it issues the calls it always issued.
+
 With `augment=AugmentSpec(...)` (augment.py) a worker also draws the batch's augmentation records into the slot — they
 ride the same upload — and the one launch is lr_lip_crop_collate_aug_u8 / lr_collate_pad_aug_f32, which applies them.
 Lengths, labels, batch order and batch shapes are those of the un-augmented loader; `plain()` iterates the same
@@ -203,14 +207,14 @@ def _slot_bytes(dataset, plan, pixels, augment=False):
   return most
 
 
-def _max_rows(dataset, plan):
-  """Frames of the largest pixel batch (sizes only, as _slot_bytes)."""
+def _max_rows(dataset, plan, pixels=True):
+  """Frames of the largest batch (sizes only, as _slot_bytes)."""
   most = 1
   for lo, hi in plan:
     rows = 0
     for i in range(lo, hi):
       try:
-        rows += len(dataset[i][0][0])
+        rows += len(dataset[i][0][0]) if pixels else len(dataset[i][0])
       except Exception:     # a malformed sample: its batch raises when it is packed
         continue
     most = max(most, rows)
@@ -416,9 +420,12 @@ class PrefetchLoader(object):
   PAD=0, char_lens i64), the last three on the host (pinned).  Re-iterable; one pass at a time."""
 
   def __init__(self, dataset, batch_size, device, pixels=False, size=96, margin=0.3, depth=2, workers=2, alloc=None,
-               augment=None, crop="box", extent=1.25, radius=2):
+               augment=None, crop="box", extent=1.25, radius=2, pose=None):
     from .data import check_crop
     check_crop(crop)
+    if pose is not None and pixels:
+      raise ValueError("pose=%r normalises the landmark regime's batches; pixels=True has none (use crop=\"stable\")"
+                       % (pose,))
     dev = torch.device(device)
     if dev.type != "cuda":
       raise _C.LipReadingHipError("collation runs on the MI355X only (no CPU fallback)")
@@ -429,7 +436,7 @@ class PrefetchLoader(object):
     self.crop, self.extent, self.radius = crop, float(extent), int(radius)
     self.depth = int(depth)
     self._pinned = alloc is None
-    self.augment = augment
+    self.augment, self.pose = augment, pose
     self.host = HostStage(dataset, batch_size, pixels=pixels, depth=depth, workers=workers,
                           alloc=alloc or _pinned_alloc, augment=augment)
     with torch.cuda.device(dev):
@@ -441,6 +448,14 @@ class PrefetchLoader(object):
         self._work_bytes = int(_C.lib().lr_lip_stable_workspace_bytes(_max_rows(dataset, self.host.plan), self.radius))
         if not self._work_bytes:
           raise _C.LipReadingHipError("lr_lip_stable_workspace_bytes rejects radius=%r" % (radius,))
+      # pose=: the rows' statistics and, behind them, the rows' status words
+      self._status_off = 0
+      if pose is not None:
+        most = _max_rows(dataset, self.host.plan, pixels=False)
+        self._status_off = _align(pose.workspace_bytes(most))
+        if not self._status_off:
+          raise _C.LipReadingHipError("lr_lmk_pose_workspace_bytes rejects %r" % (pose,))
+        self._work_bytes = self._status_off + _align(most * 4)
       self._stage = [torch.empty(self.host.slot_bytes + self._work_bytes, dtype=torch.uint8, device=dev)
                      for _ in self.host.slots]
     self._pending = [None] * len(self.host.slots)    # the event behind the last upload out of each slot
@@ -493,6 +508,17 @@ class PrefetchLoader(object):
         _C.check(L.lr_lip_crop_collate_u8(base + pb.frames_off, base + pb.lmk_off, base + pb.offsets_off,
                                           base + pb.lens_off, out.data_ptr(), pb.B, pb.t_max, pb.H, pb.W, self.size,
                                           68, self._mouth.start, self._mouth.stop, self.margin, s), "lr_lip_crop_collate_u8")
+      elif self.pose is not None:
+        spec, work = self.pose, self.host.slot_bytes          # slot_bytes is a multiple of 256
+        if pb.tail != (spec.npts, 3):
+          raise ValueError("pose normalisation takes (len, %d, 3) landmarks, got (len,) + %r" % (spec.npts, pb.tail))
+        out = torch.empty((pb.B, pb.t_max) + pb.tail, dtype=torch.float32, device=dev)
+        _C.check(L.lr_lmk_pose_collate_f32(base + pb.frames_off, base + pb.offsets_off, base + pb.lens_off,
+                                           base + pb.tmap_off if pb.augmented else None,
+                                           spec.template_on(dev).data_ptr(), spec.rigid_ptr, len(spec.rigid),
+                                           out.data_ptr(), None, base + work + self._status_off, base + work,
+                                           self._status_off, pb.B, pb.rows, pb.t_max, spec.npts, spec.radius, spec.flags,
+                                           s), "lr_lmk_pose_collate_f32")
       else:
         out = torch.empty((pb.B, pb.t_max, pb.feat), dtype=torch.float32, device=dev)
         if pb.augmented:
