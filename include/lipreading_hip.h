@@ -278,6 +278,47 @@ int lr_lmk_pose_collate_f32(const float* lmk, const int64_t* offsets, const int3
                             int32_t* status, void* workspace, size_t workspace_bytes, int B, int64_t rows, int t_max,
                             int npts, int radius, int flags, lr_stream_t stream);
 
+/* ---- Landmark augmentation: one 3x3 matrix, a shift and noise per clip, on a collated batch (BUILD-DEFINED) -------- */
+
+/* Training-time augmentation of a COLLATED landmark batch: it runs behind lr_collate_pad_f32, lr_collate_pad_aug_f32 or
+ * lr_lmk_pose_collate_f32, so frame maps, masked frames, padding and pose are settled and neither tmap nor the pose
+ * status is needed.  The host draws (lipreading_amd/augment.py, LandmarkAugmentSpec), the kernel applies.
+ *   x, y        f32 [B][t_max][npts][3]; they may be the same buffer (in place), otherwise they must not overlap
+ *   lens        int32 [B] on the device, clamped into [0, t_max]
+ *   mirror_perm int32 [npts] on the device: the left/right partner of every point
+ *   clip_stats  f64 [B][4] = (c_x, c_y, c_z, r), or NULL
+ *   workspace   lr_lmk_augment_workspace_bytes(B) bytes, 16-byte aligned
+ *   rec         16 eight-byte words per clip: words 0-8 A row-major f64; 9-11 shift f64; 12 jitter f64; 13 mirror f64
+ *               (0 or 1); 14 key, read as uint64; 15 zero.  The host folds everything linear into A (rotation, scale,
+ *               stretch, the mirror's sign flip): the device never evaluates a sine.
+ * All arithmetic is float64, inputs widened from fp32, every output value rounded to fp32 once.
+ *   EMPTY rows: row (b, t) is EMPTY when t >= min(lens[b], t_max), when all npts*3 of its values are zero of either
+ *     sign, or when any of its values is not finite.  Padding, masked frames and the pose entry's BAD rows are exactly
+ *     the all-zero rows, which is why nothing else is needed to recognise them.  The other rows are LIVE.
+ *   clip statistics, over the LIVE rows of clip b, n = LIVE rows * npts:  c_b = sum x / n;
+ *     r_b = sqrt(max(sum |x|^2 / n - |c_b|^2, 0));  a clip without a LIVE row has c = 0, r = 0.  The sums have a fixed
+ *     order that does not depend on B, on the other clips or on the launch.
+ *   noise (no transcendental function, so it is exact on host and device): mix = the splitmix64 finaliser
+ *     (augment._mix), GOLDEN = 0x9E3779B97F4A7C15;  z = mix(key_b + GOLDEN + uint64((t*npts + j)*3 + k)), wrapping,
+ *     with t, j, k the OUTPUT frame, point and coordinate;  S = the sum of the four 16-bit fields of z;
+ *     g = double(S - 131070) * 2.6428997921303014e-05 (1 over the standard deviation of the sum of four uniform 16-bit
+ *     integers: g has unit variance).  The noise is evaluated only where jitter != 0.
+ *   LIVE rows:  y[b][t][j][k] = fp32( sum_l A[k][l] * (x[b][t][j'][l] - c_l) + c_k + r_b * (shift_k + jitter * g) ),
+ *     j' = mirror_perm[j] when mirror != 0, else j;  j' is clamped into [0, npts) inside the kernel: no value of
+ *     mirror_perm can read outside the row.
+ *   EMPTY rows: all zeros.  EVERY element of y is written.
+ * Two launches give the same bits, a batch gives the bits of B one-clip calls, in place gives the bits of out of place.
+ * Errors, all before any launch: npts outside [1, LR_LMK_AUG_MAX_POINTS], B < 1, t_max < 1 or B*t_max >= 2^31 ->
+ * LR_ERR_UNSUPPORTED; a NULL required pointer, or x and y overlapping without being equal -> LR_ERR_INVALID_ARG; a
+ * workspace that is too small -> LR_ERR_WORKSPACE.
+ * Two launches: the clips' statistics (one workgroup per clip), then one wave per row. */
+#define LR_LMK_AUG_MAX_POINTS 256
+#define LR_LMK_AUG_REC_WORDS 16
+size_t lr_lmk_augment_workspace_bytes(int B); /* 0 for arguments it rejects */
+int lr_lmk_augment_f32(const float* x, const int32_t* lens, const void* rec, const int32_t* mirror_perm, float* y,
+                       double* clip_stats, void* workspace, size_t workspace_bytes, int B, int t_max, int npts,
+                       lr_stream_t stream);
+
 /* ---- dense fp32 contraction (MFMA f32 16x16x4 / 32x32x2), used by A3 ------------------- */
 
 /* C[M,N] = alpha * op(A)[M,K] * op(B)[K,N] + beta * C + bias[N]   (row-major, fp32)

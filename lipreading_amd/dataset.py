@@ -292,22 +292,30 @@ class BatchLoader(object):
     return iterate_batches(self.dataset, self.batch_size, self.collate_fn)
 
 
-def make_loader(dataset, batch_size, collate_fn, prefetch=0, augment=None, pose=None, **loader_args):
+def make_loader(dataset, batch_size, collate_fn, prefetch=0, augment=None, pose=None, lmk_augment=None,
+                **loader_args):
   """prefetch=0: the plain BatchLoader over `collate_fn`.  prefetch=N > 0: a loader.PrefetchLoader of depth N that
   yields the same batches (loader_args: device, pixels, size, margin, workers, crop, extent, radius — what `collate_fn`
   was made with).
   pose: the landmarks.PoseSpec `collate_fn` was made with (data.make_collate_fn(device, pose=...)); the prefetch
   loader normalises inside its own collate launch.
   augment: an augment.AugmentSpec for a TRAINING loader; it is applied inside the prefetch loader's collate launch,
-  so it needs prefetch > 0."""
+  so it needs prefetch > 0.
+  lmk_augment: an augment.LandmarkAugmentSpec for a TRAINING loader of the landmark regime; lr_lmk_augment_f32 runs
+  behind the prefetch loader's collate launch, so it needs prefetch > 0 as well."""
   if augment is not None and not prefetch:
     raise ValueError("augment=%r needs the prefetch loader: pass prefetch=N > 0 (got prefetch=%r)" % (augment, prefetch))
+  if lmk_augment is not None and not prefetch:
+    raise ValueError("lmk_augment=%r needs the prefetch loader: pass prefetch=N > 0 (got prefetch=%r)"
+                     % (lmk_augment, prefetch))
   if not prefetch:
     return BatchLoader(dataset, batch_size, collate_fn)
   if augment is not None:
     loader_args["augment"] = augment
   if pose is not None:
     loader_args["pose"] = pose
+  if lmk_augment is not None:
+    loader_args["lmk_augment"] = lmk_augment
   from .loader import PrefetchLoader
   return PrefetchLoader(dataset, batch_size, depth=int(prefetch), **loader_args)
 

@@ -73,6 +73,11 @@ DEFAULTS = dict(  # train.py:134-167
     # frames.  --lmk_pose_template=PATH.npy: the canonical face (68, 3); loaded when the file exists, otherwise fitted
     # from the training set (landmarks.fit_template) and written there ('' = fitted, not written)
     lmk_pose="none", lmk_pose_smooth=0, lmk_pose_template="",
+    # --lmk_augment=mirror=0.5,rot=10/10/15,scale=0.1,stretch=0.05,shift=0.05,jitter=0.01: training-time augmentation
+    # of the landmark regime's TRAIN batches (augment.LandmarkAugmentSpec: one 3x3 matrix, a shift and noise per clip;
+    # lr_lmk_augment_f32 behind the prefetch loader's collate launch, so it needs --prefetch).  Its seed is
+    # --augment_seed (None = --seed); the per-epoch Train CER is scored on clean clips
+    lmk_augment="",
     # who scores the transcripts behind the edit-distance errors (greedy, --ctc_decoder=beam, --attn_decode=beam|joint):
     # host (the Python loops of train.greedy_cer / ctc_cer / attention_cer) or device (train.device_scores: the ids
     # never leave the GPU, lr_edit_distance scores them, one read per loader; the epoch summary then carries val_wer)
@@ -197,6 +202,7 @@ def parse_flags(argv, defaults=DEFAULTS):
       if name not in explicit:
         out[name] = True
   augment_spec(out)
+  lmk_augment_spec(out)
   crop_check(out)
   lmk_pose_check(out)
   align_check(out)
@@ -214,6 +220,22 @@ def augment_spec(f):
   spec = AugmentSpec.parse(f.get("augment") or "", seed=f.get("seed", 0) if seed is None else seed)
   if spec is not None and not f.get("prefetch"):
     raise ValueError("--augment=%s needs --prefetch=N > 0 (got --prefetch=%r)" % (f["augment"], f.get("prefetch")))
+  return spec
+
+
+def lmk_augment_spec(f):
+  """The LandmarkAugmentSpec of the flags `f` (None without --lmk_augment).  ValueError for a policy that does not
+  parse, for --lmk_augment without --prefetch (lr_lmk_augment_f32 runs behind the prefetch loader's collate launch) and
+  for --lmk_augment in the pixel regime, which feeds no landmarks to the encoder."""
+  from .augment import LandmarkAugmentSpec
+  seed = f.get("augment_seed")
+  spec = LandmarkAugmentSpec.parse(f.get("lmk_augment") or "", seed=f.get("seed", 0) if seed is None else seed)
+  if spec is not None and not f.get("prefetch"):
+    raise ValueError("--lmk_augment=%s needs --prefetch=N > 0 (got --prefetch=%r)"
+                     % (f["lmk_augment"], f.get("prefetch")))
+  if spec is not None and f.get("frontend", "none") == "conv3d":
+    raise ValueError("--lmk_augment=%s augments the landmarks the encoder reads; --frontend=conv3d reads mouth crops "
+                     "(its counterpart is --augment)" % f["lmk_augment"])
   return spec
 
 
@@ -523,6 +545,7 @@ def run(**flags):
   f = dict(DEFAULTS)
   f.update(flags)
   augment = augment_spec(f)
+  lmk_augment = lmk_augment_spec(f)
   crop_check(f)
   lmk_pose_check(f)
   if f["frontend"] != "none" or f["encoder"] != "rnn":
@@ -564,9 +587,12 @@ def run(**flags):
   train_loader, val_loader, test_loader = (make_loader(d, f["batch_size"], collate, prefetch=f["prefetch"], device=device,
                                                        pixels=pixels, size=f["crop_size"], crop=f["crop"],
                                                        extent=f["crop_extent"], radius=f["crop_smooth"], pose=pose,
-                                                       augment=augment if d is sets[0] else None) for d in sets)
+                                                       augment=augment if d is sets[0] else None,
+                                                       lmk_augment=lmk_augment if d is sets[0] else None) for d in sets)
   if augment is not None:
     print("Augmenting the training clips: %s (seed %d)" % (augment, augment.seed))
+  if lmk_augment is not None:
+    print("Augmenting the training landmarks: %s (seed %d)" % (lmk_augment, lmk_augment.seed))
   print("Initializing model")
   ctc_only = bool(f["ctc_only"])
   if pixels or f["encoder"] == "transformer":
@@ -655,7 +681,8 @@ def run(**flags):
     print(f'\tAVG CTC Loss: {ctc_loss}')
     val_cer = error_of(val_loader)
     val_scores = error_of.last_scores   # (--score=device: the validation pass's dict, before the next pass replaces it)
-    train_cer = error_of(train_loader.plain() if augment is not None else train_loader)   # on clean clips
+    clean = augment is None and lmk_augment is None
+    train_cer = error_of(train_loader if clean else train_loader.plain())   # on clean clips
     encoder.save_best_model(val_cer, encoder_path)
     if not ctc_only:
       decoding_step.save_best_model(val_cer, decoder_path)

@@ -271,6 +271,89 @@ def normalise_pose(lmks, spec, return_pose=False):
   return (got[0][0], got[1], got[2]) if return_pose else got[0]
 
 
+# ---- landmark-space augmentation (include/lipreading_hip.h, "Landmark augmentation") ------------------
+def _mirror_68():
+  """The iBUG 68-point scheme's left/right partners: jaw 0..16 <-> 16..0, brows 17..21 <-> 26..22, nostrils
+  31..35 <-> 35..31, the eyes and the mouth contour by contour; the points on the face's midline are their own."""
+  pairs = [(i, 16 - i) for i in range(8)] + [(17 + i, 26 - i) for i in range(5)] + [(31, 35), (32, 34)]
+  pairs += [(36, 45), (37, 44), (38, 43), (39, 42), (40, 47), (41, 46)]
+  pairs += [(48, 54), (49, 53), (50, 52), (55, 59), (56, 58), (60, 64), (61, 63), (65, 67)]
+  perm = list(range(68))
+  for a, b in pairs:
+    perm[a], perm[b] = b, a
+  return tuple(perm)
+
+
+MIRROR_68 = _mirror_68()
+_perm_on = {}                                 # perm -> PerDevice: a permutation is uploaded once per device
+
+
+def check_mirror_perm(perm, npts):
+  """perm as a tuple of ints; ValueError unless it is an involution of range(npts)."""
+  try:
+    perm = tuple(int(i) for i in perm)
+  except (TypeError, ValueError):
+    raise ValueError("perm must be a sequence of point indices, got %r" % (perm,))
+  if len(perm) != npts:
+    raise ValueError("perm names the partner of each of the %d points, got %d entries" % (npts, len(perm)))
+  for j, p in enumerate(perm):
+    if not 0 <= p < npts:
+      raise ValueError("perm[%d] = %d is outside [0, %d)" % (j, p, npts))
+    if perm[p] != j:
+      raise ValueError("perm is not an involution: perm[%d] = %d but perm[%d] = %d" % (j, p, p, perm[p]))
+  return perm
+
+
+def mirror_perm_on(perm, dev):
+  """The int32 device copy of a (validated) permutation, made once per device."""
+  per = _perm_on.setdefault(perm, PerDevice())
+  return per.get(dev, lambda d: torch.tensor(perm, dtype=torch.int32).to(d))
+
+
+def augment_landmarks(batch, lens, rec, perm=MIRROR_68, out=None, return_stats=False):
+  """lr_lmk_augment_f32 on device tensors: a COLLATED batch f32 (B,t_max,npts,3), lens int32 or int64 (B,) on the
+  device, rec = augment.LandmarkAugmentSpec.draw's records — uint64 numpy (B,16), or a device tensor of (B,16)
+  eight-byte elements — -> the augmented batch f32 (B,t_max,npts,3).  out: the tensor to write (`batch` itself: in
+  place; otherwise it must not share memory with it); None: a new one.  perm: the left/right partner of every point,
+  an involution of range(npts).  return_stats: also the clips' (c_x, c_y, c_z, r) as f64 (B,4)."""
+  _C.require_cuda(batch, lens, out)
+  if batch.dim() != 4 or batch.shape[3] != 3 or batch.dtype != torch.float32 or not batch.is_contiguous():
+    raise ValueError("a collated batch is contiguous float32 (B, t_max, npts, 3), got %s %r"
+                     % (batch.dtype, tuple(batch.shape)))
+  B, t_max, npts = int(batch.shape[0]), int(batch.shape[1]), int(batch.shape[2])
+  if B < 1 or t_max < 1 or not 1 <= npts <= _C.LR_LMK_AUG_MAX_POINTS:
+    raise ValueError("B and t_max must be positive and 1 <= npts <= %d, got %r"
+                     % (_C.LR_LMK_AUG_MAX_POINTS, tuple(batch.shape)))
+  if lens.dtype not in (torch.int32, torch.int64) or tuple(lens.shape) != (B,):
+    raise ValueError("lens must be int32 or int64 (%d,), got %s %r" % (B, lens.dtype, tuple(lens.shape)))
+  perm = check_mirror_perm(perm, npts)
+  dev = batch.device
+  if isinstance(rec, np.ndarray):
+    if rec.dtype != np.uint64 or rec.shape != (B, _C.LR_LMK_AUG_REC_WORDS):
+      raise ValueError("rec must be uint64 (%d, %d), got %s %r" % (B, _C.LR_LMK_AUG_REC_WORDS, rec.dtype, rec.shape))
+    rec = torch.from_numpy(np.ascontiguousarray(rec).view(np.int64)).to(dev)
+  else:
+    _C.require_cuda(rec)
+    if rec.element_size() != 8 or tuple(rec.shape) != (B, _C.LR_LMK_AUG_REC_WORDS) or not rec.is_contiguous():
+      raise ValueError("rec must be (%d, %d) contiguous eight-byte words, got %s %r"
+                       % (B, _C.LR_LMK_AUG_REC_WORDS, rec.dtype, tuple(rec.shape)))
+  if out is None:
+    out = torch.empty_like(batch)
+  elif out.shape != batch.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+    raise ValueError("out must be contiguous float32 %r on %s, got %s %r on %s"
+                     % (tuple(batch.shape), dev, out.dtype, tuple(out.shape), out.device))
+  L = _C.lib()
+  with torch.cuda.device(dev):
+    lens32 = lens.to(torch.int32).contiguous()
+    need = int(L.lr_lmk_augment_workspace_bytes(B))
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    stats = torch.empty((B, 4), dtype=torch.float64, device=dev) if return_stats else None
+    _C.check(L.lr_lmk_augment_f32(batch.data_ptr(), lens32.data_ptr(), rec.data_ptr(),
+                                  mirror_perm_on(perm, dev).data_ptr(), out.data_ptr(), _C.ptr(stats), work.data_ptr(),
+                                  need, B, t_max, npts, _C.stream_handle()), "lr_lmk_augment_f32")
+  return (out, stats) if return_stats else out
+
+
 def canonical_orientation(points):
   """The host half of `fit_template`, float64: (68,3) points -> the same points about their origin in the face's own
   axes.  x runs along the mean of points 42..47 minus the mean of points 36..41 (eye to eye), y from the eyes' midpoint

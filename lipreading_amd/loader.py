@@ -18,6 +18,9 @@ With `pose=PoseSpec(...)` (landmarks.py) the landmark launch is lr_lmk_pose_coll
 spec's canonical face — with the batch's frame map when the batch is augmented; its workspace and status words lie behind
 the slot's device bytes as well.  A loader built without it issues the calls it always issued.
 
+With `lmk_augment=LandmarkAugmentSpec(...)` (augment.py) the landmark regime's batches are also mirrored, turned, scaled,
+stretched, shifted and jittered: lr_lmk_augment_f32, in place on the padded batch, behind whichever landmark collate ran.
+
 With `augment=AugmentSpec(...)` (augment.py) a worker also draws the batch's augmentation records into the slot — they
 ride the same upload — and the one launch is lr_lip_crop_collate_aug_u8 / lr_collate_pad_aug_f32, which applies them.
 Lengths, labels, batch order and batch shapes are those of the un-augmented loader; `plain()` iterates the same
@@ -46,6 +49,7 @@ from . import _C
 MAX_WORKERS = 8         # a GPU job may use 16 CPUs; never sized by os.cpu_count()
 WAIT_SECONDS = 120.0    # upper bound of every blocking wait on the host
 _ALIGN = 256            # every region of a slot starts on a 256-byte boundary (vector loads, int64 offsets)
+LMK_REC_BYTES = 128     # a clip's landmark-augmentation record: 16 eight-byte words (augment.LMK_REC_WORDS)
 DRAW_AHEAD = 16         # batches whose augmentation records ONE call of AugmentSpec.draw covers: a draw is some fifty
                         # numpy calls, each of which hands the GIL over and takes it back from the thread that launches
                         # the step, so the workers draw for many batches at once (DESIGN.md "Clip augmentation")
@@ -67,6 +71,7 @@ class PackedBatch(object):
   pixels:    frames u8 [rows][3][H][W] | lmk f32 [rows][68][3] | offsets i64 [B] | lens i32 [B]
   landmarks: rows f32 [rows][feat]                             | offsets i64 [B] | lens i32 [B]
   augmented: ... | aug f32 [B][4] (pixels only) | tmap i32 [rows]     (AugmentSpec.draw's records)
+  landmark-augmented: ... | lmk_aug u64 [B][16], the last region      (LandmarkAugmentSpec.draw's records)
   frame_lens / chars / char_lens: int64 numpy arrays, the values the plain collate functions return."""
 
   def __init__(self):
@@ -76,6 +81,8 @@ class PackedBatch(object):
     self.frames_off = self.lmk_off = self.offsets_off = self.lens_off = 0
     self.augmented = False
     self.aug_off = self.tmap_off = 0
+    self.lmk_augmented = False
+    self.lmk_aug_off = 0
     self.H = self.W = self.feat = 0
     self.tail = ()
     self.frame_lens = self.chars = self.char_lens = None
@@ -100,6 +107,9 @@ class PackedBatch(object):
     if name == "tmap":
       assert self.augmented
       return buf[self.tmap_off:self.tmap_off + rows * 4].view(np.int32)
+    if name == "lmk_aug":
+      assert self.lmk_augmented
+      return buf[self.lmk_aug_off:self.lmk_aug_off + B * LMK_REC_BYTES].view(np.uint64).reshape(B, LMK_REC_BYTES // 8)
     raise KeyError(name)
 
 
@@ -118,11 +128,14 @@ def _aug_bytes(B, rows, pixels):
   return (_align(B * 16) if pixels else 0) + _align(rows * 4)
 
 
-def pack_batch(samples, pixels, buf, augment=None, pass_no=0, indices=None, records=None):
+def pack_batch(samples, pixels, buf, augment=None, pass_no=0, indices=None, records=None, lmk_augment=None,
+               lmk_records=None):
   """Gather one batch into `buf` (1-D uint8 numpy array, a slot of the ring).  Host memory only.  Raises what the
   plain collate raises for a malformed batch (AssertionError), before anything is written.  augment: an AugmentSpec,
   whose draw for (pass_no, indices = the samples' dataset indices) follows `lens`; None: today's bytes.  records: that
-  draw's (clip, tmap) if the caller has it already (a record depends on seed, pass, index and length only)."""
+  draw's (clip, tmap) if the caller has it already (a record depends on seed, pass, index and length only).
+  lmk_augment: a LandmarkAugmentSpec, whose draw (lmk_records, if the caller has it already) lies in a region of its own
+  behind all the others; None: no such region."""
   pb = PackedBatch()
   pb.pixels = bool(pixels)
   assert len(samples) > 0
@@ -161,6 +174,12 @@ def pack_batch(samples, pixels, buf, augment=None, pass_no=0, indices=None, reco
     pb.aug_off = pb.nbytes
     pb.tmap_off = pb.aug_off + (_align(pb.B * 16) if pixels else 0)
     pb.nbytes = pb.aug_off + _aug_bytes(pb.B, rows, pixels)
+  if lmk_augment is not None:
+    assert not pixels, "landmark augmentation belongs to the landmark regime"
+    assert indices is not None and len(indices) == len(samples), "an augmented batch needs its dataset indices"
+    pb.lmk_augmented = True
+    pb.lmk_aug_off = pb.nbytes
+    pb.nbytes = pb.lmk_aug_off + _align(pb.B * LMK_REC_BYTES)
   assert pb.nbytes <= buf.shape[0], "slot of %d bytes is too small for a batch of %d" % (buf.shape[0], pb.nbytes)
   offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
   frames = pb.region(buf, "frames")
@@ -180,12 +199,16 @@ def pack_batch(samples, pixels, buf, augment=None, pass_no=0, indices=None, reco
     if pixels:
       pb.region(buf, "aug")[...] = clip       # (the landmark regime has no window to move: the map alone applies)
     pb.region(buf, "tmap")[:] = tmap
+  if lmk_augment is not None:
+    rec = lmk_augment.draw(pass_no, indices, lens) if lmk_records is None else lmk_records
+    assert rec.shape == (pb.B, LMK_REC_BYTES // 8) and rec.dtype == np.uint64
+    pb.region(buf, "lmk_aug")[...] = rec
   pb.frame_lens = lens
   pb.chars, pb.char_lens = _pad_chars(captions)
   return pb
 
 
-def _slot_bytes(dataset, plan, pixels, augment=False):
+def _slot_bytes(dataset, plan, pixels, augment=False, lmk_augment=False):
   """Bytes of the largest batch (the dataset is in memory): sizes only, the shape checks belong to pack_batch."""
   most = _ALIGN
   for lo, hi in plan:
@@ -203,7 +226,8 @@ def _slot_bytes(dataset, plan, pixels, augment=False):
       except Exception:     # a malformed sample: its batch raises when it is packed
         continue
     most = max(most, _align(a) + _align(b) + _align((hi - lo) * 8) + _align((hi - lo) * 4) +
-               (_aug_bytes(hi - lo, rows, pixels) if augment else 0))
+               (_aug_bytes(hi - lo, rows, pixels) if augment else 0) +
+               (_align((hi - lo) * LMK_REC_BYTES) if lmk_augment else 0))
   return most
 
 
@@ -233,11 +257,11 @@ class _HostEpoch(object):
   """The workers of one pass over the dataset.  submit(slot) hands the next batch of the plan to a worker together
   with the slot it may fill; get(k) returns batch k's PackedBatch or re-raises its worker's exception."""
 
-  def __init__(self, stage, augment=None, pass_no=0):
+  def __init__(self, stage, augment=None, pass_no=0, lmk_augment=None):
     self._dataset, self._plan, self._pixels = stage.dataset, stage.plan, stage.pixels
-    self._augment, self._pass_no = augment, int(pass_no)
+    self._augment, self._lmk_augment, self._pass_no = augment, lmk_augment, int(pass_no)
     self._draw_lock = threading.Lock()
-    self._drawn = {}                 # chunk of DRAW_AHEAD batches -> (first index, row starts, clip, tmap)
+    self._drawn = {}                 # chunk of DRAW_AHEAD batches -> (first index, row starts, clip, tmap, lmk records)
     self._bufs = stage._np
     self._tasks = queue.Queue()
     self._cv = threading.Condition()
@@ -257,9 +281,11 @@ class _HostEpoch(object):
       k, slot = task
       try:
         lo, hi = self._plan[k]
+        drawn = self._augment is not None or self._lmk_augment is not None
+        records, lmk_records = self._records(k) if drawn else (None, None)
         res = pack_batch([self._dataset[i] for i in range(lo, hi)], self._pixels, self._bufs[slot],
-                         augment=self._augment, pass_no=self._pass_no, indices=range(lo, hi),
-                         records=self._records(k) if self._augment is not None else None)
+                         augment=self._augment, pass_no=self._pass_no, indices=range(lo, hi), records=records,
+                         lmk_augment=self._lmk_augment, lmk_records=lmk_records)
         res.index, res.slot = k, slot
       except BaseException as exc:   # handed to the consumer, which raises it at batch k
         res = exc
@@ -268,9 +294,10 @@ class _HostEpoch(object):
         self._cv.notify_all()
 
   def _records(self, k):
-    """Batch k's (clip, tmap), cut out of ONE draw for its chunk of DRAW_AHEAD batches (made by the worker that needs
-    it first).  None if the chunk cannot be drawn (a malformed sample somewhere in it): the batch then draws for
-    itself, and the malformed batch raises when IT is packed."""
+    """Batch k's ((clip, tmap), landmark records), cut out of ONE draw of each policy for its chunk of DRAW_AHEAD
+    batches (made by the worker that needs it first); None for a policy that is off.  (None, None) if the chunk cannot
+    be drawn (a malformed sample somewhere in it): the batch then draws for itself, and the malformed batch raises when
+    IT is packed."""
     c = k // DRAW_AHEAD
     with self._draw_lock:
       got = self._drawn.get(c, False)
@@ -280,17 +307,21 @@ class _HostEpoch(object):
           lo, hi = self._plan[b0][0], self._plan[b1 - 1][1]
           lens = np.array([len(self._dataset[i][0][0]) if self._pixels else len(self._dataset[i][0])
                            for i in range(lo, hi)], dtype=np.int64)
-          clip, tmap = self._augment.draw(self._pass_no, range(lo, hi), lens)
-          got = (lo, np.concatenate([[0], np.cumsum(lens)]), clip, tmap)
+          clip, tmap = (self._augment.draw(self._pass_no, range(lo, hi), lens) if self._augment is not None
+                        else (None, None))
+          rec = (self._lmk_augment.draw(self._pass_no, range(lo, hi), lens) if self._lmk_augment is not None
+                 else None)
+          got = (lo, np.concatenate([[0], np.cumsum(lens)]), clip, tmap, rec)
         except Exception:
           got = None
         self._drawn = {c2: v for c2, v in self._drawn.items() if c2 >= c - 1}   # workers are a few batches apart
         self._drawn[c] = got
     if got is None:
-      return None
-    first, starts, clip, tmap = got
+      return None, None
+    first, starts, clip, tmap, rec = got
     lo, hi = self._plan[k]
-    return clip[lo - first:hi - first], tmap[starts[lo - first]:starts[hi - first]]
+    return ((clip[lo - first:hi - first], tmap[starts[lo - first]:starts[hi - first]]) if clip is not None else None,
+            rec[lo - first:hi - first] if rec is not None else None)
 
   def submit(self, slot):
     if self._stop.is_set() or self.submitted >= len(self._plan):
@@ -336,15 +367,18 @@ class HostStage(object):
   asks for the next batch (PrefetchLoader drives the same workers but returns a slot only after its upload).
 
   augment: an AugmentSpec; every augmented pass draws with the next pass number (0, 1, ...; `set_pass` pins it), so two
-  passes differ and a resumed run can repeat one.  A pass takes its number when it starts, completed or abandoned."""
+  passes differ and a resumed run can repeat one.  A pass takes its number when it starts, completed or abandoned.
+  lmk_augment: a LandmarkAugmentSpec (landmark regime); its records are drawn beside `augment`'s, with the same pass
+  number."""
 
-  def __init__(self, dataset, batch_size, pixels=False, depth=2, workers=2, alloc=None, augment=None):
+  def __init__(self, dataset, batch_size, pixels=False, depth=2, workers=2, alloc=None, augment=None,
+               lmk_augment=None):
     assert depth >= 1 and workers >= 1
     self.dataset, self.batch_size, self.pixels = dataset, int(batch_size), bool(pixels)
     self.depth, self.workers = int(depth), min(int(workers), MAX_WORKERS)
-    self.augment, self.pass_no = augment, 0
+    self.augment, self.lmk_augment, self.pass_no = augment, lmk_augment, 0
     self.plan = batch_plan(len(dataset), self.batch_size)
-    self.slot_bytes = _slot_bytes(dataset, self.plan, self.pixels, augment is not None)
+    self.slot_bytes = _slot_bytes(dataset, self.plan, self.pixels, augment is not None, lmk_augment is not None)
     alloc = alloc or _plain_alloc
     self.slots = [alloc(self.slot_bytes) for _ in range(self.depth + 1)]
     assert all(s.dtype == torch.uint8 and s.dim() == 1 and s.numel() >= self.slot_bytes and not s.is_cuda
@@ -363,8 +397,8 @@ class HostStage(object):
     """Start the workers of a new pass (the previous pass, if it was abandoned, is shut down first).  augmented=False:
     a pass with augmentation off, which leaves the pass number alone."""
     self.close()
-    if augmented and self.augment is not None:
-      self._epoch = _HostEpoch(self, self.augment, self.pass_no)
+    if augmented and (self.augment is not None or self.lmk_augment is not None):
+      self._epoch = _HostEpoch(self, self.augment, self.pass_no, self.lmk_augment)
       self.pass_no += 1
     else:
       self._epoch = _HostEpoch(self)
@@ -420,12 +454,15 @@ class PrefetchLoader(object):
   PAD=0, char_lens i64), the last three on the host (pinned).  Re-iterable; one pass at a time."""
 
   def __init__(self, dataset, batch_size, device, pixels=False, size=96, margin=0.3, depth=2, workers=2, alloc=None,
-               augment=None, crop="box", extent=1.25, radius=2, pose=None):
+               augment=None, crop="box", extent=1.25, radius=2, pose=None, lmk_augment=None, mirror_perm=None):
     from .data import check_crop
     check_crop(crop)
     if pose is not None and pixels:
       raise ValueError("pose=%r normalises the landmark regime's batches; pixels=True has none (use crop=\"stable\")"
                        % (pose,))
+    if lmk_augment is not None and pixels:
+      raise ValueError("lmk_augment=%r augments the landmark regime's batches; pixels=True has none (use augment=)"
+                       % (lmk_augment,))
     dev = torch.device(device)
     if dev.type != "cuda":
       raise _C.LipReadingHipError("collation runs on the MI355X only (no CPU fallback)")
@@ -436,9 +473,14 @@ class PrefetchLoader(object):
     self.crop, self.extent, self.radius = crop, float(extent), int(radius)
     self.depth = int(depth)
     self._pinned = alloc is None
-    self.augment, self.pose = augment, pose
+    self.augment, self.pose, self.lmk_augment = augment, pose, lmk_augment
+    self._perm = None
+    if lmk_augment is not None:
+      from .landmarks import MIRROR_68, check_mirror_perm
+      perm = MIRROR_68 if mirror_perm is None else mirror_perm
+      self._perm = check_mirror_perm(perm, len(perm))
     self.host = HostStage(dataset, batch_size, pixels=pixels, depth=depth, workers=workers,
-                          alloc=alloc or _pinned_alloc, augment=augment)
+                          alloc=alloc or _pinned_alloc, augment=augment, lmk_augment=lmk_augment)
     with torch.cuda.device(dev):
       self._copy = torch.cuda.Stream(dev)
       # ragged device staging, one per slot: rewritten only by a later upload on the same stream
@@ -456,6 +498,16 @@ class PrefetchLoader(object):
         if not self._status_off:
           raise _C.LipReadingHipError("lr_lmk_pose_workspace_bytes rejects %r" % (pose,))
         self._work_bytes = self._status_off + _align(most * 4)
+      # lmk_augment=: the clips' statistics, behind pose's bytes; the permutation is uploaded here, once
+      self._lmk_work_off = self._lmk_work_bytes = 0
+      if lmk_augment is not None:
+        from .landmarks import mirror_perm_on
+        self._perm_dev = mirror_perm_on(self._perm, dev)
+        self._lmk_work_off = self._work_bytes
+        self._lmk_work_bytes = int(_C.lib().lr_lmk_augment_workspace_bytes(self.host.batch_size))
+        if not self._lmk_work_bytes:
+          raise _C.LipReadingHipError("lr_lmk_augment_workspace_bytes rejects B=%r" % (batch_size,))
+        self._work_bytes += _align(self._lmk_work_bytes)
       self._stage = [torch.empty(self.host.slot_bytes + self._work_bytes, dtype=torch.uint8, device=dev)
                      for _ in self.host.slots]
     self._pending = [None] * len(self.host.slots)    # the event behind the last upload out of each slot
@@ -529,6 +581,14 @@ class PrefetchLoader(object):
           _C.check(L.lr_collate_pad_f32(base + pb.frames_off, base + pb.offsets_off, base + pb.lens_off,
                                         out.data_ptr(), pb.B, pb.t_max, pb.feat, s), "lr_collate_pad_f32")
         out = out.reshape((pb.B, pb.t_max) + pb.tail)
+      if pb.lmk_augmented:                                    # in place, behind whichever landmark collate ran
+        if pb.tail != (len(self._perm), 3):
+          raise ValueError("landmark augmentation takes (len, %d, 3) landmarks, got (len,) + %r"
+                           % (len(self._perm), pb.tail))
+        work = base + self.host.slot_bytes + self._lmk_work_off
+        _C.check(L.lr_lmk_augment_f32(out.data_ptr(), base + pb.lens_off, base + pb.lmk_aug_off,
+                                      self._perm_dev.data_ptr(), out.data_ptr(), None, work, self._lmk_work_bytes, pb.B,
+                                      pb.t_max, len(self._perm), s), "lr_lmk_augment_f32")
       event = torch.cuda.Event()
       event.record(self._copy)
     self._pending[slot] = event
