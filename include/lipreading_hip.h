@@ -1002,6 +1002,55 @@ int lr_ctc_beam_lm_bias_decode(const float* probs, int64_t stride_b, int64_t str
                                int32_t* out_ids, int32_t* out_offsets, int32_t* out_lens, float* out_scores,
                                void* workspace, size_t workspace_bytes, int B, int T, int C, lr_stream_t stream);
 
+/* ---- A6c'': sessions — the same four searches fed chunk by chunk — no counterpart in the reference ---- */
+/* A session is one device buffer owned by the caller: for B independent utterance slots a 32-byte header each (the
+ * configuration of the last reset, frames consumed, live hypotheses, status bits), the beam's arrays in beam order and
+ * the trie's three node tables [B][1 + max_frames * beam_width] (lipreading_amd/csrc/lr_ctc_beam.hip).
+ * Fed the same frames in any chunks, a session holds what the one-shot entry computes, bit for bit; offsets count the
+ * session's frames.  lm == NULL / bias == NULL select the variant as with_lm / with_bias do at the reset.
+ * Limits: the one-shot search's, with max_frames in T's place (else 0 bytes / LR_ERR_UNSUPPORTED). */
+#define LR_BEAM_STREAM_OVERFLOW 1 /* frames past max_frames were offered and not consumed */
+#define LR_BEAM_STREAM_MISMATCH 2 /* a call's beam_width, max_frames, B or variant is not the slot's */
+
+/* Bytes of the state (0 for arguments the reset rejects). */
+size_t lr_ctc_beam_stream_state_bytes(int B, int max_frames, int beam_width, int with_lm, int with_bias);
+
+/* Workspace of one advance of chunk_T frames: the pruned per-frame class lists (0 for arguments it rejects). */
+size_t lr_ctc_beam_stream_workspace_bytes(int B, int chunk_T, int C, int beam_width, int cutoff_top_n);
+
+/* Slots with mask[b] != 0 (mask [B] int32 on the device; NULL: all slots) go back to the empty prefix, the model's
+ * <s> context and the automaton's start state, with 0 frames and no status bit; every other slot keeps every bit.
+ * Under a mask the slot must already carry this configuration (else it is left alone and gets
+ * LR_BEAM_STREAM_MISMATCH); with NULL whatever the buffer held is overwritten.  The node tables are not cleared. */
+int lr_ctc_beam_stream_reset(void* state, size_t state_bytes, const int32_t* mask, int B, int max_frames,
+                             int beam_width, int with_lm, int with_bias, const void* lm, const void* bias,
+                             lr_stream_t stream);
+
+/* Consumes frames [0, clamp(sizes[b], 0, chunk_T)) of slot b's chunk (sizes NULL = chunk_T): two launches, the
+ * pruning of lr_ctc_beam_decode over the chunk and the frame loop from the slot's beam.  A slot with no frame keeps
+ * every bit.  Frames past max_frames are not consumed (LR_BEAM_STREAM_OVERFLOW); a slot whose header disagrees with
+ * beam_width, max_frames, B or the variant is left alone (LR_BEAM_STREAM_MISMATCH).  The bits stay until a reset. */
+int lr_ctc_beam_stream_advance(const float* probs, int64_t stride_b, int64_t stride_t, const int32_t* sizes,
+                               int log_input, int cutoff_top_n, float cutoff_prob, int beam_width, int blank,
+                               const void* lm, const int32_t* class_roles, float alpha, float beta, const void* bias,
+                               void* state, size_t state_bytes, int max_frames, void* workspace,
+                               size_t workspace_bytes, int B, int chunk_T, int C, lr_stream_t stream);
+
+/* What the one-shot entry would answer if every slot's stream ended now — the variant's end terms and re-sort
+ * applied — without changing a byte of the state.  The layout is read from the slots' headers.
+ *   out_ids / out_offsets [B][n_out][out_width] int32, -1 padded: the first n_out hypotheses, of each the first
+ *                         min(len, out_width) ids;  out_lens [B][n_out] the TRUE lengths;  out_scores [B][n_out]
+ *                         (+inf in empty slots)
+ *   out_stable  [B]  length of the longest common prefix, as id strings, of ALL live hypotheses: every later
+ *                    hypothesis extends a live one, so these ids of the best hypothesis are final (their offsets
+ *                    are not: two trie nodes can spell one prefix)
+ *   out_frames, out_status [B]  frames consumed, LR_BEAM_STREAM_* bits (MISMATCH also for a header that does not
+ *                    fit state_bytes or the variant lm / bias select; the slot's outputs are then empty) */
+int lr_ctc_beam_stream_read(const void* state, size_t state_bytes, const void* lm, float alpha, float beta,
+                            const void* bias, int n_out, int out_width, int32_t* out_ids, int32_t* out_offsets,
+                            int32_t* out_lens, float* out_scores, int32_t* out_stable, int32_t* out_frames,
+                            int32_t* out_status, int B, lr_stream_t stream);
+
 /* ---- A6d: edit-distance scoring of decoded ids — decoder.py:44-73 (Decoder.wer / Decoder.cer) on the device ---- */
 /* The reference scores joined label strings on the host with the Levenshtein package.  Here the ids stay on the
  * device (lipreading_amd/csrc/lr_edit.hip): every class id spells a string over the caller's

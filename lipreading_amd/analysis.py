@@ -179,3 +179,39 @@ def caption_shifts(records, min_confidence=0.5):
       row["low_confidence"] = sum(1 for c in caps if c["confidence"] is None or c["confidence"] < min_confidence)
     out.append(row)
   return out
+
+
+# ---- commit delay of a streamed beam search (decoder.BeamStream) ------------------------------------
+
+def commit_delay(reads, offsets, total_frames):
+  """How long after it was spoken each character of the final best hypothesis became final.
+
+  reads: [(frames, stable)] of one utterance in feeding order — the frames consumed at a read and the stable-prefix
+  length it reported; offsets: the final best hypothesis's frame offsets, one per character; total_frames: the
+  utterance's length.  Character i is committed at the first read whose stable exceeds i; its delay is that read's
+  frame count minus offsets[i].  A character no read before the end covered is committed when the utterance ends, at
+  total_frames.  -> (delays [int] per character, how many were committed only at the end).  Pure: no tensors."""
+  delays, at_end = [], 0
+  k = 0
+  reads = [(int(f), int(s)) for f, s in reads]
+  for i, off in enumerate(offsets):
+    while k < len(reads) and reads[k][1] <= i:
+      k += 1   # stable never decreases, so the first covering read of character i is not before that of i - 1
+    at = reads[k][0] if k < len(reads) else total_frames
+    if at >= total_frames:
+      at, at_end = total_frames, at_end + 1
+    delays.append(at - int(off))
+  return delays, at_end
+
+
+def commit_delay_stats(per_utterance):
+  """[(delays, at_end)] of commit_delay over a loader -> dict(chars, mean, p90, end_share): the mean and the 90th
+  percentile (nearest rank) of the delays in frames, and the share of characters committed only at the end.  No
+  characters: chars 0 and None for the rest."""
+  delays = sorted(d for ds, _ in per_utterance for d in ds)
+  n = len(delays)
+  if n == 0:
+    return dict(chars=0, mean=None, p90=None, end_share=None)
+  rank = -(-9 * n // 10)   # ceil(0.9 n)
+  return dict(chars=n, mean=sum(delays) / n, p90=delays[rank - 1],
+              end_share=sum(e for _, e in per_utterance) / n)

@@ -116,6 +116,19 @@
 //            bit-identical to the search without hotwords.
 //   Limits   at most 4096 automaton nodes, 1024 phrases, C <= 256 (the packer's LR_ERR_UNSUPPORTED); an empty phrase
 //            or a weight that is not finite and positive is LR_ERR_INVALID_ARG.
+//
+// Sessions (lr_ctc_beam_stream_*): the four searches above, fed chunk by chunk.  Everything above holds, frame by
+// frame; t is the frame's index in the session, so offsets and the trie's node ids count the session's frames.
+//   Advance  consumes frames [0, clamp(sizes[b], 0, chunk_T)) of slot b's chunk from the slot's beam as the last
+//            advance left it: the pruning launch over the chunk, then the loop kernel's STREAM instantiation.
+//   Read     what the one-shot entry would put out if the stream ended now: the End terms of the variant are the
+//            read's (they do not feed back into the loop) and it changes no byte of the state.  stable = the length
+//            of the longest common prefix, as id strings, of all live hypotheses: every later hypothesis is a live
+//            one or extends one, so those ids are final.
+//   Equality fed the same frames in any chunks, a session holds the one-shot entry's bits: the state stored between
+//            two launches is exactly what the loop carries from one frame to the next (the beam's arrays in beam
+//            order, the live count, the trie), and fp32 values go through memory unchanged.
+//   Limits   the search's, with max_frames in T's place.  No trie compaction: a session ends at max_frames.
 #include <string.h>
 
 #include <type_traits>
@@ -374,16 +387,95 @@ __device__ __forceinline__ float ext_mass(const BeamSmem& sm, const BeamLmSmem<L
   return sc;
 }
 
+// A session (lr_ctc_beam_stream_*): one caller-owned device buffer that holds, for B independent slots, what the loop
+// keeps in LDS between two frames, so that the search can stop after any frame and go on in a later launch.
+//   header   [B] StreamHdr: the configuration of the last reset, the frames consumed, the live hypotheses, status bits
+//   beam     [B][W] per array, in beam order: node, par, cls, depth, pb, pnb, hpre, hpar; with a language model tnode,
+//            tword, tterm, ctx [B][W][kLmMaxCtx]; with hotwords bnode, bbank
+//   trie     npar, ncls, nfrm [B][1 + max_frames * W]: node 1 + t*W + r is created at the session's frame t
+// Every section starts at a multiple of 256 bytes.  The header's place does not depend on the configuration, so a call
+// whose arguments disagree with it finds it all the same.
+constexpr int32_t kStreamMagic = 0x5342524d;   // "MRBS"
+constexpr int kStreamThreads = 128;            // reset and read: one thread per beam entry
+struct StreamHdr {
+  int32_t magic, B, W, max_frames, variant, frames, nb, status;
+};
+static_assert(sizeof(StreamHdr) == 32, "StreamHdr is part of the state's layout");
+struct StreamState {
+  StreamHdr* hdr;
+  int32_t *node, *par, *cls, *depth;
+  float *pb, *pnb;
+  uint64_t *hpre, *hpar;
+  int32_t *tnode, *tword;
+  float* tterm;
+  int32_t* ctx;
+  int32_t* bnode;
+  float* bbank;
+  int32_t *npar, *ncls, *nfrm;
+};
+// what the one-shot instantiations take in the session's place
+struct NoStream {
+  int unused_;
+};
+// one advance: the state's sections and the max_frames the caller states
+struct StreamLaunch : StreamState {
+  int max_frames;
+};
+template <bool STREAM>
+using StreamArg = std::conditional_t<STREAM, StreamLaunch, NoStream>;
+
+__host__ __device__ inline int stream_variant(bool lm, bool bias) { return (lm ? 1 : 0) | (bias ? 2 : 0); }
+
+// the state's sections for (B, max_frames, W, variant) over `base`; returns the state's size in bytes
+__host__ __device__ inline size_t stream_carve(void* base, int B, int max_frames, int W, int variant, StreamState* s) {
+  char* p = static_cast<char*>(base);
+  size_t o = 0;
+  const size_t slots = (size_t)B * W;
+  auto take = [&](size_t bytes) {
+    char* at = p ? p + o : nullptr;
+    o += (bytes + 255) & ~(size_t)255;
+    return at;
+  };
+  s->hdr = reinterpret_cast<StreamHdr*>(take((size_t)B * sizeof(StreamHdr)));
+  s->node = reinterpret_cast<int32_t*>(take(slots * 4));
+  s->par = reinterpret_cast<int32_t*>(take(slots * 4));
+  s->cls = reinterpret_cast<int32_t*>(take(slots * 4));
+  s->depth = reinterpret_cast<int32_t*>(take(slots * 4));
+  s->pb = reinterpret_cast<float*>(take(slots * 4));
+  s->pnb = reinterpret_cast<float*>(take(slots * 4));
+  s->hpre = reinterpret_cast<uint64_t*>(take(slots * 8));
+  s->hpar = reinterpret_cast<uint64_t*>(take(slots * 8));
+  s->tnode = s->tword = s->ctx = s->bnode = nullptr;
+  s->tterm = s->bbank = nullptr;
+  if (variant & 1) {
+    s->tnode = reinterpret_cast<int32_t*>(take(slots * 4));
+    s->tword = reinterpret_cast<int32_t*>(take(slots * 4));
+    s->tterm = reinterpret_cast<float*>(take(slots * 4));
+    s->ctx = reinterpret_cast<int32_t*>(take(slots * 4 * kLmMaxCtx));
+  }
+  if (variant & 2) {
+    s->bnode = reinterpret_cast<int32_t*>(take(slots * 4));
+    s->bbank = reinterpret_cast<float*>(take(slots * 4));
+  }
+  const size_t nodes = (size_t)B * (size_t)beam_nodes(max_frames, W) * 4;
+  s->npar = reinterpret_cast<int32_t*>(take(nodes));
+  s->ncls = reinterpret_cast<int32_t*>(take(nodes));
+  s->nfrm = reinterpret_cast<int32_t*>(take(nodes));
+  return o;
+}
+
 // LM = false is the search without a language model; LM = true adds the terms and the dictionary of the header.
 // BIAS = true adds the hotwords' bonus to the selection key.  LM + BIAS re-sorts through the LM block's fin / perm, so
 // its 2.5 KB of hotword state fit beside the LM's 62 KB under the 64 KB of static LDS.
-template <bool LM, bool BIAS>
+// STREAM = true is one advance of a session: T is the chunk's length, the beam comes from `ss` into the [0] halves
+// and goes back from the [cur] ones, the frames count on from the slot's, and nothing is put out (beam_read_kernel).
+template <bool LM, bool BIAS, bool STREAM = false>
 __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
     const int32_t* __restrict__ kcls, const float* __restrict__ klp, const int32_t* __restrict__ kcnt,
     const int32_t* __restrict__ sizes, int32_t* __restrict__ npar, int32_t* __restrict__ ncls,
     int32_t* __restrict__ nfrm, int32_t* __restrict__ out_ids, int32_t* __restrict__ out_off,
     int32_t* __restrict__ out_lens, float* __restrict__ out_scores, int T, int W, int n, int blank, int C,
-    LoopArgs<BIAS> lma) {
+    LoopArgs<BIAS> lma, StreamArg<STREAM> ss) {
   __shared__ BeamSmem sm;
   __shared__ BeamLmSmem<LM> lsm;
   __shared__ BeamBiasSmem<BIAS, LM> bsm;
@@ -393,7 +485,25 @@ __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
   const int n1 = n + 1;
   int len = sizes ? sizes[b] : T;
   len = len < 0 ? 0 : (len > T ? T : len);
-  const int64_t nbase = (int64_t)b * beam_nodes(T, W);
+  int t0 = 0, nb = 1;   // the first frame's index in the utterance; the live hypotheses
+  int64_t nbase = (int64_t)b * beam_nodes(T, W);
+  if constexpr (STREAM) {
+    // T is the chunk's length; the slot's header decides where its frames count from and how many may follow
+    const StreamHdr h = ss.hdr[b];
+    if (h.magic != kStreamMagic || h.B != (int)gridDim.x || h.W != W || h.max_frames != ss.max_frames ||
+        h.variant != stream_variant(LM, BIAS) || h.frames < 0 || h.frames > h.max_frames || h.nb < 0 || h.nb > W) {
+      if (tid == 0) ss.hdr[b].status = h.status | LR_BEAM_STREAM_MISMATCH;
+      return;
+    }
+    t0 = h.frames;
+    nb = h.nb;
+    if (len > h.max_frames - t0) {
+      len = h.max_frames - t0;
+      if (tid == 0) ss.hdr[b].status = h.status | LR_BEAM_STREAM_OVERFLOW;
+    }
+    if (len <= 0) return;   // the slot keeps every other bit
+    nbase = (int64_t)b * beam_nodes(h.max_frames, W);
+  }
   int32_t* gpar = npar + nbase;
   int32_t* gcls = ncls + nbase;
   int32_t* gfrm = nfrm + nbase;
@@ -419,7 +529,20 @@ __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
     bv = bias_view(lma.bias);
     if (tid == 0) { bsm.bnode[0][0] = bv.start; bsm.bbank[0][0] = 0.f; }
   }
-  int cur = 0, nb = 1;
+  if constexpr (STREAM) {
+    if (tid < nb) {
+      const int64_t g = (int64_t)b * W + tid;
+      sm.node[0][tid] = ss.node[g]; sm.par[0][tid] = ss.par[g]; sm.cls[0][tid] = ss.cls[g];
+      sm.depth[0][tid] = ss.depth[g]; sm.pb[0][tid] = ss.pb[g]; sm.pnb[0][tid] = ss.pnb[g];
+      sm.hpre[0][tid] = ss.hpre[g]; sm.hpar[0][tid] = ss.hpar[g];
+      if constexpr (LM) {
+        lsm.tnode[0][tid] = ss.tnode[g]; lsm.tword[0][tid] = ss.tword[g]; lsm.tterm[0][tid] = ss.tterm[g];
+        for (int q = 0; q < kLmMaxCtx; ++q) lsm.ctx[0][tid][q] = ss.ctx[g * kLmMaxCtx + q];
+      }
+      if constexpr (BIAS) { bsm.bnode[0][tid] = ss.bnode[g]; bsm.bbank[0][tid] = ss.bbank[g]; }
+    }
+  }
+  int cur = 0;
   // the kept list of the next frame is loaded one frame ahead
   int pf_cnt = 0, pf_c = 0;
   float pf_l = 0.f;
@@ -430,15 +553,16 @@ __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
   }
   __syncthreads();
 
-  for (int t = 0; t < len; ++t) {
+  for (int tt = 0; tt < len; ++tt) {
+    const int t = t0 + tt;   // the frame's index in the utterance: the trie's node ids and the offsets count in it
     const int cnt = pf_cnt;
     // -- phase 1: this frame's kept classes, fresh hash and histograms
     for (int h = tid; h < kHash; h += nt) sm.hslot[h] = -1;
     if (tid < cnt) { sm.kc[tid] = pf_c; sm.kl[tid] = pf_l; sm.c2k[pf_c] = tid; }
     if (tid < 256) { sm.hist[0][tid] = 0; sm.hist[1][tid] = 0; }
     if (tid == 0) sm.ctl[4] = 0;
-    if (t + 1 < len) {
-      const int64_t f = (int64_t)b * T + t + 1;
+    if (tt + 1 < len) {
+      const int64_t f = (int64_t)b * T + tt + 1;
       pf_cnt = kcnt[f];
       if (tid < pf_cnt) { pf_c = kcls[f * n + tid]; pf_l = klp[f * n + tid]; }
     }
@@ -645,6 +769,24 @@ __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
     nb = nsel;
   }
 
+  // -- a session stops here: the beam goes back to the state as it stands, the end terms are beam_read_kernel's
+  if constexpr (STREAM) {
+    if (tid < nb) {
+      const int64_t g = (int64_t)b * W + tid;
+      ss.node[g] = sm.node[cur][tid]; ss.par[g] = sm.par[cur][tid]; ss.cls[g] = sm.cls[cur][tid];
+      ss.depth[g] = sm.depth[cur][tid]; ss.pb[g] = sm.pb[cur][tid]; ss.pnb[g] = sm.pnb[cur][tid];
+      ss.hpre[g] = sm.hpre[cur][tid]; ss.hpar[g] = sm.hpar[cur][tid];
+      if constexpr (LM) {
+        ss.tnode[g] = lsm.tnode[cur][tid]; ss.tword[g] = lsm.tword[cur][tid]; ss.tterm[g] = lsm.tterm[cur][tid];
+        // the model's own context length only: the words beyond it are never read and may hold anything
+        for (int q = 0; q < L.m; ++q) ss.ctx[g * kLmMaxCtx + q] = lsm.ctx[cur][tid][q];
+      }
+      if constexpr (BIAS) { ss.bnode[g] = bsm.bnode[cur][tid]; ss.bbank[g] = bsm.bbank[cur][tid]; }
+    }
+    if (tid == 0) { ss.hdr[b].frames = t0 + len; ss.hdr[b].nb = nb; }
+    return;
+  }
+
   // -- end of utterance (LM): the last word's term, then a stable re-sort by the final score
   if constexpr (LM) {
     if (tid < nb) lsm.fin[tid] = lr_lse2(sm.pb[cur][tid], sm.pnb[cur][tid]) + lsm.tterm[cur][tid];
@@ -709,8 +851,159 @@ __global__ __launch_bounds__(kLoopThreads) void beam_loop_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// 3. sessions: reset and read (the advance is beam_loop_kernel<.., .., true>)
+// ---------------------------------------------------------------------------------------
+__host__ __device__ inline bool stream_shape_ok(int B, int max_frames, int W) {
+  return B > 0 && max_frames > 0 && W > 0 && W <= kBeamMaxW && beam_nodes(max_frames, W) < INT32_MAX;
+}
+
+// Masked slots (all of them for mask == nullptr) go back to the empty prefix.  Under a mask the slot must already
+// carry this configuration: the sections' places depend on it, and the other slots keep theirs.
+__global__ __launch_bounds__(kStreamThreads) void beam_stream_reset_kernel(
+    StreamLaunch ss, const int32_t* __restrict__ mask, int W, int variant, const uint8_t* __restrict__ lm,
+    const uint8_t* __restrict__ bias) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (mask) {
+    if (mask[b] == 0) return;
+    const StreamHdr h = ss.hdr[b];
+    if (h.magic != kStreamMagic || h.B != (int)gridDim.x || h.W != W || h.max_frames != ss.max_frames ||
+        h.variant != variant) {
+      if (tid == 0) ss.hdr[b].status = h.status | LR_BEAM_STREAM_MISMATCH;
+      return;
+    }
+  }
+  const int bos = (variant & 1) ? reinterpret_cast<const LmHeader*>(lm)->bos : 0;
+  const int start = (variant & 2) ? reinterpret_cast<const BiasHeader*>(bias)->start : 0;
+  for (int i = tid; i < W; i += blockDim.x) {
+    const int64_t g = (int64_t)b * W + i;
+    const bool root = i == 0;
+    ss.node[g] = 0; ss.par[g] = root ? -1 : 0; ss.cls[g] = root ? -1 : 0; ss.depth[g] = 0;
+    ss.pb[g] = 0.f; ss.pnb[g] = root ? LR_NEG_INF : 0.f;
+    ss.hpre[g] = 0; ss.hpar[g] = 0;
+    if (variant & 1) {
+      ss.tnode[g] = 0; ss.tword[g] = root ? -1 : 0; ss.tterm[g] = 0.f;
+      for (int q = 0; q < kLmMaxCtx; ++q) ss.ctx[g * kLmMaxCtx + q] = root ? bos : 0;
+    }
+    if (variant & 2) { ss.bnode[g] = root ? start : 0; ss.bbank[g] = 0.f; }
+  }
+  if (tid == 0) ss.hdr[b] = StreamHdr{kStreamMagic, (int)gridDim.x, W, ss.max_frames, variant, 0, 1, 0};
+}
+
+// What the one-shot search would put out if the slot's stream ended now: the variant's end terms, the stable re-sort,
+// the chain walks; and the common prefix of all live hypotheses.  Reads the state only.  The layout comes from the
+// slot's own header, checked against the buffer's size before anything else is read.
+__global__ __launch_bounds__(kStreamThreads) void beam_read_kernel(
+    const uint8_t* __restrict__ state, size_t state_bytes, int variant, int n_out, int out_width,
+    int32_t* __restrict__ out_ids, int32_t* __restrict__ out_off, int32_t* __restrict__ out_lens,
+    float* __restrict__ out_scores, int32_t* __restrict__ out_stable, int32_t* __restrict__ out_frames,
+    int32_t* __restrict__ out_status) {
+  __shared__ float fin[kBeamMaxW];
+  __shared__ int perm[kBeamMaxW], node[kBeamMaxW], depth[kBeamMaxW];
+  __shared__ int lcp;
+  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const StreamHdr h = reinterpret_cast<const StreamHdr*>(state)[b];
+  StreamState ss{};
+  bool ok = h.magic == kStreamMagic && h.B == (int)gridDim.x && stream_shape_ok(h.B, h.max_frames, h.W) &&
+            h.variant == variant && h.frames >= 0 && h.frames <= h.max_frames && h.nb >= 0 && h.nb <= h.W;
+  ok = ok && stream_carve(const_cast<uint8_t*>(state), h.B, h.max_frames, h.W, h.variant, &ss) <= state_bytes;
+  const int nb = ok ? h.nb : 0;
+  const int W = ok ? h.W : 1;
+  const int32_t* gpar = nullptr;
+  const int32_t* gcls = nullptr;
+  const int32_t* gfrm = nullptr;
+  if (ok) {
+    const int64_t nbase = (int64_t)b * beam_nodes(h.max_frames, W);
+    gpar = ss.npar + nbase; gcls = ss.ncls + nbase; gfrm = ss.nfrm + nbase;
+  }
+  if (tid < nb) {
+    const int64_t g = (int64_t)b * W + tid;
+    node[tid] = ss.node[g];
+    depth[tid] = ss.depth[g];
+    // the one-shot end's own expressions, term by term
+    float f = lr_lse2(ss.pb[g], ss.pnb[g]);
+    if (variant & 1) f = f + ss.tterm[g];
+    if (variant & 2) f = f + ss.bbank[g];
+    fin[tid] = f;
+  }
+  __syncthreads();
+  if (tid < nb) {
+    int r = tid;   // without end terms the beam is in output order already
+    if (variant != 0) {
+      const float f = fin[tid];
+      r = 0;
+      for (int q = 0; q < nb; ++q) r += fin[q] > f || (fin[q] == f && q < tid);
+    }
+    perm[r] = tid;
+  }
+  if (tid == 0) lcp = nb > 0 ? depth[0] : 0;
+  __syncthreads();
+
+  const int64_t obase = (int64_t)b * n_out * out_width;
+  for (int64_t e = tid; e < (int64_t)n_out * out_width; e += nt) {
+    const int r = (int)(e / out_width), d = (int)(e - (int64_t)r * out_width);
+    const int dep = r < nb ? depth[perm[r]] : 0;
+    if (d >= dep) { out_ids[obase + e] = -1; out_off[obase + e] = -1; }
+  }
+  for (int r = tid; r < n_out; r += nt) {
+    out_lens[(int64_t)b * n_out + r] = r < nb ? depth[perm[r]] : 0;   // the true length, whatever out_width
+    out_scores[(int64_t)b * n_out + r] = r < nb ? -fin[perm[r]] : __builtin_inff();
+  }
+  if (tid < nb && tid < n_out) {
+    int id = node[perm[tid]];
+    int32_t* ids = out_ids + obase + (int64_t)tid * out_width;
+    int32_t* off = out_off + obase + (int64_t)tid * out_width;
+    for (int d = depth[perm[tid]] - 1; d >= 0; --d) {
+      if (d < out_width) { ids[d] = gcls[id]; off[d] = gfrm[id]; }
+      id = gpar[id];
+    }
+  }
+  // the longest common prefix of all live hypotheses: each one against beam entry 0, both chains at equal depth;
+  // the lowest position at which the classes differ bounds it
+  if (tid < nb) {
+    int a = node[tid], c = node[0], d = depth[tid], d0 = depth[0];
+    for (; d > d0; --d) a = gpar[a];
+    for (; d0 > d; --d0) c = gpar[c];
+    int l = d;
+    for (; d > 0 && a != c; --d) {
+      if (gcls[a] != gcls[c]) l = d - 1;
+      a = gpar[a];
+      c = gpar[c];
+    }
+    atomicMin(&lcp, l);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    out_stable[b] = lcp;
+    out_frames[b] = ok ? h.frames : 0;
+    out_status[b] = ok ? h.status : ((h.magic == kStreamMagic ? h.status : 0) | LR_BEAM_STREAM_MISMATCH);
+  }
+}
+
 bool beam_supported(int T, int C, int W, int n) {
   return W <= kBeamMaxW && n <= kBeamMaxN && C <= kBeamMaxC && beam_nodes(T, W) < INT32_MAX;
+}
+
+size_t stream_ws_bytes(int B, int T, int n) {
+  const size_t frames = (size_t)B * T;
+  return lr_align_up(frames * n * 4, 256) * 2 + lr_align_up(frames * 4, 256);
+}
+
+template <bool LM, bool BIAS>
+int stream_advance(const float* probs, int64_t stride_b, int64_t stride_t, const int32_t* sizes, int log_input,
+                   float cutoff_prob, int blank, const LoopArgs<BIAS>& lma, const StreamLaunch& ss, void* workspace,
+                   int B, int T, int C, int W, int n, lr_stream_t stream) {
+  const BeamWs w = beam_ws_carve(workspace, B, T, n, W);   // the node tables are the state's, not these
+  const int64_t frames = (int64_t)B * T;
+  LR_LAUNCH(beam_prune_kernel, dim3((unsigned)((frames + kPruneWaves - 1) / kPruneWaves)),
+            dim3(kPruneWaves * LR_WAVE), 0, stream, probs, stride_b, stride_t, sizes, log_input, cutoff_prob,
+            w.kcls, w.klp, w.kcnt, B, T, C, n);
+  const int st = lr_launch_status();
+  if (st != LR_OK) return st;
+  LR_LAUNCH((beam_loop_kernel<LM, BIAS, true>), dim3(B), dim3(kLoopThreads), 0, stream, w.kcls, w.klp, w.kcnt, sizes,
+            ss.npar, ss.ncls, ss.nfrm, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (float*)nullptr, T, W,
+            n, blank, C, lma, ss);
+  return lr_launch_status();
 }
 
 uint64_t pow2_at_least(uint64_t x) {
@@ -850,7 +1143,7 @@ int beam_bias_decode(const float* probs, int64_t stride_b, int64_t stride_t, con
   if (st != LR_OK) return st;
   LR_LAUNCH((beam_loop_kernel<LM, true>), dim3(B), dim3(kLoopThreads), 0, stream, w.kcls, w.klp, w.kcnt, sizes,
             w.npar, w.ncls, w.nfrm, out_ids, out_offsets, out_lens, out_scores, T, W, n, blank, C,
-            BiasLmArgs{lma, static_cast<const uint8_t*>(bias)});
+            BiasLmArgs{lma, static_cast<const uint8_t*>(bias)}, NoStream{});
   return lr_launch_status();
 }
 
@@ -880,7 +1173,7 @@ extern "C" int lr_ctc_beam_decode(const float* probs, int64_t stride_b, int64_t 
   int st = lr_launch_status();
   if (st != LR_OK) return st;
   LR_LAUNCH((beam_loop_kernel<false, false>), dim3(B), dim3(kLoopThreads), 0, stream, w.kcls, w.klp, w.kcnt, sizes,
-            w.npar, w.ncls, w.nfrm, out_ids, out_offsets, out_lens, out_scores, T, W, n, blank, C, LmArgs{});
+            w.npar, w.ncls, w.nfrm, out_ids, out_offsets, out_lens, out_scores, T, W, n, blank, C, LmArgs{}, NoStream{});
   return lr_launch_status();
 }
 
@@ -980,7 +1273,7 @@ extern "C" int lr_ctc_beam_lm_decode(const float* probs, int64_t stride_b, int64
   if (st != LR_OK) return st;
   const LmArgs lma{static_cast<const uint8_t*>(lm), class_roles, alpha, beta};
   LR_LAUNCH((beam_loop_kernel<true, false>), dim3(B), dim3(kLoopThreads), 0, stream, w.kcls, w.klp, w.kcnt, sizes,
-            w.npar, w.ncls, w.nfrm, out_ids, out_offsets, out_lens, out_scores, T, W, n, blank, C, lma);
+            w.npar, w.ncls, w.nfrm, out_ids, out_offsets, out_lens, out_scores, T, W, n, blank, C, lma, NoStream{});
   return lr_launch_status();
 }
 
@@ -1038,4 +1331,85 @@ extern "C" int lr_ctc_beam_lm_bias_decode(const float* probs, int64_t stride_b, 
   return beam_bias_decode<true>(probs, stride_b, stride_t, sizes, log_input, cutoff_top_n, cutoff_prob, beam_width,
                                 blank, lma, bias, out_ids, out_offsets, out_lens, out_scores, workspace,
                                 workspace_bytes, B, T, C, stream);
+}
+
+// ---- sessions: the same searches fed chunk by chunk ----
+
+extern "C" size_t lr_ctc_beam_stream_state_bytes(int B, int max_frames, int beam_width, int with_lm, int with_bias) {
+  if (!stream_shape_ok(B, max_frames, beam_width)) return 0;
+  StreamState s;
+  return stream_carve(nullptr, B, max_frames, beam_width, stream_variant(with_lm != 0, with_bias != 0), &s);
+}
+
+extern "C" size_t lr_ctc_beam_stream_workspace_bytes(int B, int chunk_T, int C, int beam_width, int cutoff_top_n) {
+  if (B <= 0 || chunk_T <= 0 || C <= 0 || beam_width <= 0 || cutoff_top_n <= 0) return 0;
+  if (beam_width > kBeamMaxW || cutoff_top_n > kBeamMaxN || C > kBeamMaxC) return 0;
+  if ((int64_t)B * chunk_T >= INT32_MAX) return 0;
+  return stream_ws_bytes(B, chunk_T, cutoff_top_n);
+}
+
+extern "C" int lr_ctc_beam_stream_reset(void* state, size_t state_bytes, const int32_t* mask, int B, int max_frames,
+                                        int beam_width, int with_lm, int with_bias, const void* lm, const void* bias,
+                                        lr_stream_t stream) {
+  LR_CHECK_ARG(state && B > 0 && max_frames > 0 && beam_width > 0);
+  LR_CHECK_ARG((with_lm != 0) == (lm != nullptr) && (with_bias != 0) == (bias != nullptr));
+  if (!stream_shape_ok(B, max_frames, beam_width)) return LR_ERR_UNSUPPORTED;
+  const int variant = stream_variant(with_lm != 0, with_bias != 0);
+  StreamLaunch ss{};
+  if (state_bytes < stream_carve(state, B, max_frames, beam_width, variant, &ss)) return LR_ERR_WORKSPACE;
+  ss.max_frames = max_frames;
+  LR_LAUNCH(beam_stream_reset_kernel, dim3(B), dim3(kStreamThreads), 0, stream, ss, mask, beam_width, variant,
+            static_cast<const uint8_t*>(lm), static_cast<const uint8_t*>(bias));
+  return lr_launch_status();
+}
+
+extern "C" int lr_ctc_beam_stream_advance(const float* probs, int64_t stride_b, int64_t stride_t, const int32_t* sizes,
+                                          int log_input, int cutoff_top_n, float cutoff_prob, int beam_width,
+                                          int blank, const void* lm, const int32_t* class_roles, float alpha,
+                                          float beta, const void* bias, void* state, size_t state_bytes,
+                                          int max_frames, void* workspace, size_t workspace_bytes, int B, int chunk_T,
+                                          int C, lr_stream_t stream) {
+  LR_CHECK_ARG(probs && state && workspace);
+  LR_CHECK_ARG(B > 0 && chunk_T > 0 && C > 0 && beam_width > 0 && cutoff_top_n > 0 && max_frames > 0);
+  LR_CHECK_ARG(blank >= 0 && blank < C && !(cutoff_prob != cutoff_prob));
+  LR_CHECK_ARG(!lm || (class_roles && isfinite(alpha) && isfinite(beta)));
+  const int W = beam_width, n = cutoff_top_n;
+  if (!stream_shape_ok(B, max_frames, W) || n > kBeamMaxN || C > kBeamMaxC || (int64_t)B * chunk_T >= INT32_MAX)
+    return LR_ERR_UNSUPPORTED;
+  const int variant = stream_variant(lm != nullptr, bias != nullptr);
+  StreamLaunch ss{};
+  if (state_bytes < stream_carve(state, B, max_frames, W, variant, &ss)) return LR_ERR_WORKSPACE;
+  ss.max_frames = max_frames;
+  if (workspace_bytes < stream_ws_bytes(B, chunk_T, n)) return LR_ERR_WORKSPACE;
+  const LmArgs lma{static_cast<const uint8_t*>(lm), class_roles, alpha, beta};
+  const BiasLmArgs bla{lma, static_cast<const uint8_t*>(bias)};
+  switch (variant) {
+    case 0:
+      return stream_advance<false, false>(probs, stride_b, stride_t, sizes, log_input, cutoff_prob, blank, lma, ss,
+                                          workspace, B, chunk_T, C, W, n, stream);
+    case 1:
+      return stream_advance<true, false>(probs, stride_b, stride_t, sizes, log_input, cutoff_prob, blank, lma, ss,
+                                         workspace, B, chunk_T, C, W, n, stream);
+    case 2:
+      return stream_advance<false, true>(probs, stride_b, stride_t, sizes, log_input, cutoff_prob, blank, bla, ss,
+                                         workspace, B, chunk_T, C, W, n, stream);
+    default:
+      return stream_advance<true, true>(probs, stride_b, stride_t, sizes, log_input, cutoff_prob, blank, bla, ss,
+                                        workspace, B, chunk_T, C, W, n, stream);
+  }
+}
+
+extern "C" int lr_ctc_beam_stream_read(const void* state, size_t state_bytes, const void* lm, float alpha, float beta,
+                                       const void* bias, int n_out, int out_width, int32_t* out_ids,
+                                       int32_t* out_offsets, int32_t* out_lens, float* out_scores, int32_t* out_stable,
+                                       int32_t* out_frames, int32_t* out_status, int B, lr_stream_t stream) {
+  LR_CHECK_ARG(state && out_ids && out_offsets && out_lens && out_scores && out_stable && out_frames && out_status);
+  LR_CHECK_ARG(B > 0 && n_out > 0 && out_width > 0);
+  LR_CHECK_ARG(!lm || (isfinite(alpha) && isfinite(beta)));
+  if (n_out > kBeamMaxW) return LR_ERR_UNSUPPORTED;
+  if (state_bytes < lr_align_up((size_t)B * sizeof(StreamHdr), 256)) return LR_ERR_WORKSPACE;
+  LR_LAUNCH(beam_read_kernel, dim3(B), dim3(kStreamThreads), 0, stream, static_cast<const uint8_t*>(state),
+            state_bytes, stream_variant(lm != nullptr, bias != nullptr), n_out, out_width, out_ids, out_offsets,
+            out_lens, out_scores, out_stable, out_frames, out_status);
+  return lr_launch_status();
 }

@@ -11,6 +11,8 @@ search ctcdecode runs on CPU threads after `probs.cpu()` (decoder.py:139) runs o
 (lr_ctc_beam_decode: prefix beam search) with one device->host copy.  An ARPA `lm_path` adds ctcdecode's word
 language model (lr_ctc_beam_lm_decode; the reader is lipreading_amd/lm.py); `hotwords` tell either search which
 words to expect (lr_ctc_beam_bias_decode, lr_ctc_beam_lm_bias_decode; lipreading_amd/hotwords.py).
+BeamCTCDecoder.stream() is the same search fed chunk by chunk (BeamStream on lr_ctc_beam_stream_*): partial
+transcripts with the characters that are already final, and at the end decode's answer bit for bit.
 """
 import warnings
 
@@ -152,10 +154,14 @@ class BeamCTCDecoder(Decoder):
       _host.launch(dev, "lr_ctc_beam_decode", L.lr_ctc_beam_decode, *head, *tail)
     return ids, off, lens, scores
 
-  def decode(self, probs, sizes=None):
-    """decoder.py:128-143: probs (B,T,C) -> (strings, offsets); strings[b] holds beam_width strings, best
-    first ('' for empty beam slots), offsets[b] the matching IntTensors of frame indices."""
-    ids, off, lens, _ = self.decode_ids(probs, sizes)
+  def stream(self, batch, max_frames, device):
+    """A BeamStream: this decoder's search over `batch` utterance slots fed chunk by chunk, up to `max_frames`
+    frames per slot (the trie's tables are sized for them; there is no compaction).  It keeps the decoder's
+    parameters, language model and hotwords; fed all frames it answers what decode answers, bit for bit."""
+    return BeamStream(self, batch, max_frames, device)
+
+  def _strings(self, ids, off, lens):
+    """decode's (strings, offsets) from device (B,W,T) ids / offsets and (B,W) lens: one device->host copy."""
     B, W, T = ids.shape
     host = torch.cat((ids.view(B, -1), off.view(B, -1), lens), dim=1).cpu()   # the one device->host copy
     off = host[:, W * T:2 * W * T].view(B, W, T)
@@ -167,6 +173,189 @@ class BeamCTCDecoder(Decoder):
       offsets.append([off[b, p, :n].clone() if n > 0 else torch.tensor([], dtype=torch.int)
                       for p, n in enumerate(lens[b])])
     return strings, offsets
+
+  def decode(self, probs, sizes=None):
+    """decoder.py:128-143: probs (B,T,C) -> (strings, offsets); strings[b] holds beam_width strings, best
+    first ('' for empty beam slots), offsets[b] the matching IntTensors of frame indices."""
+    ids, off, lens, _ = self.decode_ids(probs, sizes)
+    return self._strings(ids, off, lens)
+
+
+class BeamStream(object):
+  """A resumable search of a BeamCTCDecoder (lr_ctc_beam_stream_*): `batch` independent slots, each
+  fed its utterance in chunks of any lengths.  The state lives in one device tensor; feed() is two launches, every
+  read one, and a read changes nothing.  Use BeamCTCDecoder.stream()."""
+
+  def __init__(self, decoder, batch, max_frames, device):
+    device = torch.device(device)
+    if device.type != "cuda":
+      raise _C.LipReadingHipError(
+          "lipreading_amd ops run on the MI355X only; got device %s (no CPU fallback)" % device)
+    if int(batch) < 1 or int(max_frames) < 1:
+      raise ValueError("batch and max_frames must be >= 1, got %d and %d" % (batch, max_frames))
+    self.decoder, self.batch, self.max_frames = decoder, int(batch), int(max_frames)
+    d = decoder
+    L = _C.lib()
+    self._lm = d._word_lm is not None
+    self._bias = d._hotwords is not None
+    nbytes = L.lr_ctc_beam_stream_state_bytes(self.batch, self.max_frames, d.beam_width, int(self._lm),
+                                              int(self._bias))
+    if nbytes == 0:
+      raise _C.LipReadingHipError("lr_ctc_beam_stream_reset: unsupported shape B=%d max_frames=%d beam_width=%d"
+                                  % (self.batch, self.max_frames, d.beam_width))
+    self.device = torch.device(device.type, _host.device_key(device)[1])
+    # zeroed, so that the bytes the search never writes are equal from session to session
+    self.state = torch.zeros((nbytes,), dtype=torch.uint8, device=self.device)
+    self._ws = _host.GrowingWorkspace()
+    self._blob = self._roles = self._biasblob = None
+    if self._lm:
+      self._blob, self._roles = d._word_lm.tensors(self.device)
+    if self._bias:
+      self._biasblob = d._hotwords.tensor(self.device)
+    self.reset()
+
+  def reset(self, mask=None):
+    """Slots with a non-zero `mask` entry ((batch,) on the device; None: all) restart from the empty prefix with
+    0 frames; the others keep every bit."""
+    _C.require_cuda(mask)
+    m = _host.int32_vector(mask if mask is None or mask.dtype != torch.bool else mask.int(), self.batch, "mask",
+                           device=self.device)
+    L = _C.lib()
+    _host.launch(self.device, "lr_ctc_beam_stream_reset", L.lr_ctc_beam_stream_reset, self.state.data_ptr(),
+                 self.state.numel(), _C.ptr(m), self.batch, self.max_frames, self.decoder.beam_width, int(self._lm),
+                 int(self._bias), _C.ptr(self._blob), _C.ptr(self._biasblob))
+
+  def feed(self, probs, sizes=None):
+    """One advance: probs (batch, chunk_T, C), slot b consuming its first sizes[b] frames (None: all).  Strided
+    views such as all_probs[:, t0:t1] go in without a copy."""
+    _C.require_cuda(probs, sizes)
+    d = self.decoder
+    L = _C.lib()
+    probs = _host.log_probs_3d(probs, len(d.labels), "probs")
+    B, T, C = probs.shape
+    if B != self.batch:
+      raise ValueError("probs holds %d utterances, the session %d" % (B, self.batch))
+    if C != len(d.labels):
+      raise ValueError("probs has %d classes, the decoder %d labels" % (C, len(d.labels)))
+    sz = _host.int32_vector(sizes, B, "sizes", device=self.device)
+    if T == 0:
+      return self
+    W, n = d.beam_width, d.cutoff_top_n
+    nbytes = L.lr_ctc_beam_stream_workspace_bytes(B, T, C, W, n)
+    if nbytes == 0:
+      raise _C.LipReadingHipError("lr_ctc_beam_stream_advance: unsupported shape B=%d chunk_T=%d C=%d beam_width=%d "
+                                  "cutoff_top_n=%d" % (B, T, C, W, n))
+    ws = self._ws.get(self.device, nbytes)
+    alpha, beta = (d.alpha, d.beta) if self._lm else (0.0, 0.0)
+    _host.launch(self.device, "lr_ctc_beam_stream_advance", L.lr_ctc_beam_stream_advance, probs.data_ptr(),
+                 probs.stride(0), probs.stride(1), _C.ptr(sz), int(d.log_probs_input), n, d.cutoff_prob, W,
+                 d.blank_index, _C.ptr(self._blob), _C.ptr(self._roles), alpha, beta, _C.ptr(self._biasblob),
+                 self.state.data_ptr(), self.state.numel(), self.max_frames, ws.data_ptr(), ws.numel(), B, T, C)
+    return self
+
+  def read_ids(self, n_out=1, width=None):
+    """What decode_ids would answer if the stream ended now, on the device: (ids (B,n_out,width) int32, offsets
+    likewise, lens (B,n_out) the true lengths, scores (B,n_out), stable (B,), frames (B,), status (B,)).  `width`
+    None is max_frames.  The first stable[b] ids of slot b's best hypothesis are final.  The status bits
+    (_C.LR_BEAM_STREAM_OVERFLOW, _C.LR_BEAM_STREAM_MISMATCH) are the caller's to look at."""
+    d = self.decoder
+    n_out = int(n_out)
+    width = self.max_frames if width is None else int(width)
+    if not 1 <= n_out <= d.beam_width:
+      raise ValueError("n_out must be in [1, beam_width = %d], got %d" % (d.beam_width, n_out))
+    if width < 1:
+      raise ValueError("width must be >= 1, got %d" % width)
+    B, dev = self.batch, self.device
+    ids = torch.empty((B, n_out, width), dtype=torch.int32, device=dev)
+    off = torch.empty((B, n_out, width), dtype=torch.int32, device=dev)
+    lens = torch.empty((B, n_out), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, n_out), dtype=torch.float32, device=dev)
+    meta = torch.empty((3, B), dtype=torch.int32, device=dev)
+    self._read_into(n_out, width, ids, off, lens, scores, meta[0], meta[1], meta[2])
+    return ids, off, lens, scores, meta[0], meta[1], meta[2]
+
+  def _read_into(self, n_out, width, ids, off, lens, scores, stable, frames, status):
+    d = self.decoder
+    alpha, beta = (d.alpha, d.beta) if self._lm else (0.0, 0.0)
+    L = _C.lib()
+    _host.launch(self.device, "lr_ctc_beam_stream_read", L.lr_ctc_beam_stream_read, self.state.data_ptr(),
+                 self.state.numel(), _C.ptr(self._blob), alpha, beta, _C.ptr(self._biasblob), n_out, width,
+                 ids.data_ptr(), off.data_ptr(), lens.data_ptr(), scores.data_ptr(), stable.data_ptr(),
+                 frames.data_ptr(), status.data_ptr(), self.batch)
+
+  def _raise_for(self, status):
+    for b, s in enumerate(status):
+      names = [name for name, bit in (("overflow: frames past max_frames = %d were offered" % self.max_frames,
+                                       _C.LR_BEAM_STREAM_OVERFLOW),
+                                      ("mismatch: a call's configuration is not the session's",
+                                       _C.LR_BEAM_STREAM_MISMATCH)) if s & bit]
+      if names:
+        raise _C.LipReadingHipError("lr_ctc_beam_stream: slot %d has status %d (%s)" % (b, s, "; ".join(names)))
+
+  def partial(self):
+    """Per slot (best string so far, how many of its leading characters are final), one device->host copy.  A
+    status bit raises LipReadingHipError naming the slot."""
+    ids, _, lens, _, stable, _, status = self.read_ids(1, self.max_frames)
+    host = torch.cat((ids[:, 0], lens, stable[:, None], status[:, None]), dim=1).cpu().tolist()
+    T = self.max_frames
+    self._raise_for([row[T + 2] for row in host])
+    chars = self.decoder.int_to_char
+    return [(''.join(chars[i] for i in row[:row[T]]), row[T + 1]) for row in host]
+
+  def result(self):
+    """(strings, offsets) in BeamCTCDecoder.decode's contract, all beam_width hypotheses, as if the stream ended
+    now; the width is the most frames any slot consumed (at least 1).  A status bit raises LipReadingHipError."""
+    frames, status = self.read_ids(1, 1)[5:]
+    fs = torch.stack((frames, status)).cpu().tolist()
+    self._raise_for(fs[1])
+    ids, off, lens = self.read_ids(self.decoder.beam_width, max(1, max(fs[0])))[:3]
+    return self.decoder._strings(ids, off, lens)
+
+
+class ChunkedBeamDecoder(object):
+  """A BeamCTCDecoder's decode / decode_ids run through a session in chunks of `chunk` frames, one read per chunk: by
+  construction the same answers, plus the record of what a live caller would have seen.  commit_delay() turns the
+  record into analysis.commit_delay_stats' dict and clears it.  What the driver's --stream_chunk evaluates with."""
+
+  def __init__(self, decoder, chunk):
+    if int(chunk) < 1:
+      raise ValueError("chunk must be >= 1, got %d" % chunk)
+    self.decoder, self.chunk = decoder, int(chunk)
+    self._seen = []   # per batch, on the device: reads (R, 2, B), the best hypothesis's offsets (B, T) and length (B,)
+
+  def __getattr__(self, name):   # labels, scorer(), cer() ...: the decoder's
+    return getattr(self.decoder, name)
+
+  def decode_ids(self, probs, sizes=None):
+    _C.require_cuda(probs, sizes)
+    B, T = probs.shape[0], probs.shape[1]
+    st = self.decoder.stream(B, max(T, 1), probs.device)
+    sz = _host.int32_vector(sizes, B, "sizes", device=probs.device)
+    reads = []
+    for t0 in range(0, T, self.chunk):
+      t1 = min(T, t0 + self.chunk)
+      st.feed(probs[:, t0:t1], None if sz is None else (sz - t0).clamp_(0, t1 - t0))
+      got = st.read_ids(1, 1)
+      reads.append(torch.stack((got[5], got[4])))
+    ids, off, lens, scores = st.read_ids(self.decoder.beam_width, max(T, 1))[:4]
+    total = sz if sz is not None else torch.full((B,), T, dtype=torch.int32, device=probs.device)
+    if reads:
+      self._seen.append((torch.stack(reads), off[:, 0], lens[:, 0], total.clamp(0, T)))
+    return ids, off, lens, scores
+
+  def decode(self, probs, sizes=None):
+    ids, off, lens, _ = self.decode_ids(probs, sizes)
+    return self.decoder._strings(ids, off, lens)
+
+  def commit_delay(self):
+    from .analysis import commit_delay, commit_delay_stats
+    per = []
+    for reads, off, lens, total in self._seen:
+      reads, off, lens, total = reads.cpu().tolist(), off.cpu().tolist(), lens.cpu().tolist(), total.cpu().tolist()
+      for b, n in enumerate(lens):
+        per.append(commit_delay([(r[0][b], r[1][b]) for r in reads], off[b][:n], total[b]))
+    self._seen = []
+    return commit_delay_stats(per)
 
 
 class GreedyDecoder(Decoder):

@@ -45,6 +45,12 @@ DEFAULTS = dict(  # train.py:134-167
     # --hotwords=a,b,c ('' = none) tells the beam decoder which words to expect: each raises the score of the
     # hypotheses that spell it by --hotword_weight, at the start of a word (BeamCTCDecoder's hotwords)
     hotwords="", hotword_weight=10.0,
+    # --stream_chunk=N (0 = off) with --ctc_decoder=beam: the evaluation decodes every batch through a resumable
+    # session (decoder.BeamStream) fed N frames at a time with a read after every chunk, not in one
+    # call.  A session equals the one-shot search bit for bit, so the CER / WER are by construction the same as
+    # without the flag; what it adds is the validation pass's commit delay — how many frames after it was spoken a
+    # character of the final transcript became final (mean, 90th percentile, share committed only at the end)
+    stream_chunk=0,
     # the error of a model WITH the attention decoder: teacher (the live loop's sampled-token mismatch rate under
     # teacher forcing, train.eval) or beam (the edit-distance CER of the decoder's own beam-search transcript,
     # train.attention_cer, --attn_beam_width hypotheses of up to --attn_max_label_len characters) or joint (the same
@@ -182,6 +188,10 @@ def parse_flags(argv, defaults=DEFAULTS):
     raise SystemExit("--lm_path needs --ctc_decoder=beam")
   if (out.get("hotwords") or "hotword_weight" in explicit) and out.get("ctc_decoder") != "beam":
     raise SystemExit("--hotwords and --hotword_weight need --ctc_decoder=beam")
+  if int(out.get("stream_chunk") or 0) < 0:
+    raise SystemExit("--stream_chunk must be >= 0")
+  if out.get("stream_chunk") and out.get("ctc_decoder") != "beam":
+    raise SystemExit("--stream_chunk needs --ctc_decoder=beam")
   if out.get("attn_decode") not in ("teacher", "beam", "joint"):
     raise SystemExit("--attn_decode must be teacher, beam or joint")
   if out.get("attn_decode") == "joint" and not out.get("enable_ctc"):
@@ -622,7 +632,25 @@ def run(**flags):
                                  hotwords=[w for w in f["hotwords"].split(",") if w] or None,
                                  hotword_weight=f["hotword_weight"], hotword_anchor=" " in labels)
 
-  error_of = make_error_of(f, encoder, decoding_step, ctc_decoder, device, char2idx)
+  chunked = None
+  if ctc_decoder is not None and f["stream_chunk"]:
+    from .decoder import ChunkedBeamDecoder
+    chunked = ChunkedBeamDecoder(ctc_decoder, f["stream_chunk"])
+  error_of = make_error_of(f, encoder, decoding_step, chunked or ctc_decoder, device, char2idx)
+
+  def validation_error():
+    """error_of(val_loader); with --stream_chunk also the pass's commit delay, printed and returned."""
+    if chunked is None:
+      return error_of(val_loader), None
+    chunked.commit_delay()   # what the passes since the last validation left
+    cer = error_of(val_loader)
+    delay = chunked.commit_delay()
+    if delay["chars"]:
+      print("\tCommit delay (chunks of %d frames): mean %.2f frames, p90 %d, %.1f%% of %d characters only at the end"
+            % (f["stream_chunk"], delay["mean"], delay["p90"], 100.0 * delay["end_share"], delay["chars"]))
+    else:
+      print("\tCommit delay (chunks of %d frames): no characters decoded" % f["stream_chunk"])
+    return cer, delay
   mwer = None
   if f["mwer"]:
     from .mwer import MWERLoss
@@ -642,7 +670,7 @@ def run(**flags):
   graphs = T.StepGraphs(enabled=bool(f["step_graphs"]) and not pixels)
 
   print("Initial evaluation...")
-  val_cer = error_of(val_loader)
+  val_cer, commit = validation_error()
   print("\tCER: ", val_cer)
   best_val_cer, best_idx = 1.0, -1
   lr = f["learning_rate"]
@@ -679,7 +707,7 @@ def run(**flags):
                                    teacher_forcing_ratio=tfr, grad_norm=f["grad_norm"], graphs=graphs)
     print(f'\tAVG Decoder Loss: {dec_loss}')
     print(f'\tAVG CTC Loss: {ctc_loss}')
-    val_cer = error_of(val_loader)
+    val_cer, commit = validation_error()
     val_scores = error_of.last_scores   # (--score=device: the validation pass's dict, before the next pass replaces it)
     clean = augment is None and lmk_augment is None
     train_cer = error_of(train_loader if clean else train_loader.plain())   # on clean clips
@@ -701,12 +729,16 @@ def run(**flags):
     if val_scores is not None:
       history[-1]["val_wer"] = val_scores["wer"]
       print(f'\tVal WER: {val_scores["wer"]}')
+    if commit is not None:
+      history[-1]["commit_delay"] = commit
     if val_cer < best_val_cer:   # :339-341
       best_val_cer, best_idx = val_cer, epochs
     epochs += 1
   out = dict(history=history, weights_dir=weights_dir, seconds=time.time() - t0, epochs=epochs,
              graph_captures=graphs.captures, graph_replays=graphs.replays, encoder=encoder,
              decoding_step=decoding_step, char2idx=char2idx, loaders=(train_loader, val_loader, test_loader))
+  if commit is not None:
+    out["commit_delay"] = commit
   if f["align"]:
     out["align"] = write_alignments(f["align"], encoder, val_loader, device, char2idx)
     print("Aligned %(utterances)d validation utterances (%(infeasible)d too short for their caption): %(path)s"
