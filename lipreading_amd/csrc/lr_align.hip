@@ -22,15 +22,14 @@
 //               staged in LDS, word sums one word per thread.  No atomics, no scratch beyond the workspace.
 //
 // Dead lanes (s > 2L) are not masked: a state only ever reads states below it, so what they compute is never used.
-#include "lr_common.h"
+// The staging, the cell and the table's conventions are lr_lattice_dev.h's, shared with lr_spot.hip and lr_segment.hip.
+#include "lr_lattice_dev.h"
 
 namespace {
 
 constexpr int kMaxL = 256;                   // as lr_ctc_nll
 constexpr int kMaxT = LR_ALIGN_MAX_T;
-constexpr size_t kLdsBudget = 65536 - 512;   // dynamic share of the 64 KB a workgroup takes without opting in to more
 constexpr int kStageThreads = 256;           // workgroup of the one-wave kernel
-constexpr int kChunk = 16;                   // steps per back-pointer dword
 
 struct AlignPlan {
   int one_wave, sst, threads, lcap, nch;
@@ -47,18 +46,18 @@ int align_plan(int B, int T, int C, int max_label_len, AlignPlan* p) {
   p->one_wave = S <= LR_WAVE;
   p->sst = (S + LR_WAVE - 1) / LR_WAVE * LR_WAVE;
   p->lcap = max_label_len < 4 ? 4 : (max_label_len + 3) & ~3;
-  p->nch = (T + kChunk - 1) / kChunk;
+  p->nch = (T + LR_LATTICE_CHUNK - 1) / LR_LATTICE_CHUNK;
   // lab | role | tok_start | tok_end | tok_logp | word_first | word_count : lcap dwords each
   size_t off = (size_t)7 * p->lcap * 4;
   p->off_rows = (unsigned)off;
   if (!p->one_wave) off += (size_t)2 * p->sst * 4;
   p->off_lat = (unsigned)off;
   const size_t lat = lr_align_up((size_t)T * C * 4, 16);
-  p->lat_in_lds = off + lat <= kLdsBudget;
+  p->lat_in_lds = off + lat <= LR_LDS_BUDGET;
   if (p->lat_in_lds) off += lat;
   p->off_bp = (unsigned)off;
   p->bp_bytes = (size_t)p->nch * p->sst * 4;
-  p->bp_in_lds = off + p->bp_bytes <= kLdsBudget;
+  p->bp_in_lds = off + p->bp_bytes <= LR_LDS_BUDGET;
   if (p->bp_in_lds) off += p->bp_bytes;
   p->lds_bytes = off;
   // (the one-wave kernel's other three waves only stage the rows: without rows in LDS there is nothing for them to do)
@@ -95,10 +94,8 @@ struct AlignArgs {
   AlignPlan plan;
 };
 
-// v of the lane below (lane 0: -inf) — DPP wave_shr:1, a few cycles where a ds_bpermute costs an LDS round trip
-__device__ __forceinline__ float wave_up1(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(LR_NEG_INF), __float_as_int(v), 0x138, 0xf, 0xf, false));
-}
+// the end state: 2L only on a strict win of v[2L] (vb) over v[2L-1] (vc); L == 0 has state 0 alone
+__device__ __forceinline__ int end_state(int L, float vb, float vc) { return L == 0 ? 0 : (vb > vc ? 2 * L : 2 * L - 1); }
 
 // every per-sample output of a sample that is not aligned: -1 / 0 / total = -inf
 __device__ void write_empty(const AlignArgs& a, int b, int st, int nthr) {
@@ -154,7 +151,7 @@ __global__ __launch_bounds__(ONE_WAVE ? kStageThreads : 576) void align_kernel(c
     int bad = 0;
     for (int i = tid; i < L; i += nthr) {
       const int c = y[i];
-      const bool ok = (unsigned)c < (unsigned)C && c != a.blank;
+      const bool ok = lr_label_ok(c, C, a.blank);
       bad |= !ok;
       lab[i] = ok ? c : 0;
       role[i] = ok && a.roles ? a.roles[c] : 0;
@@ -170,50 +167,23 @@ __global__ __launch_bounds__(ONE_WAVE ? kStageThreads : 576) void align_kernel(c
   const float* lpb = a.lp + (int64_t)b * a.stride_b;
   const int64_t stt = a.stride_t;
 
-  // ---- the sample's n rows into LDS, coalesced, ten loads of a thread in flight at once
-  if (LAT_LDS) {
-    const int tot = n * C;
-    const bool dense = stt == C;
-    for (int i0 = 0; i0 < tot; i0 += nthr * 10) {
-      float r[10];
-#pragma unroll
-      for (int u = 0; u < 10; ++u) {   // unconditional (clamped) loads
-        int i = i0 + u * nthr + tid;
-        if (i >= tot) i = tot - 1;
-        int64_t at = i;
-        if (!dense) {
-          const int t = i / C;
-          at = (int64_t)t * stt + (i - t * C);
-        }
-        r[u] = lpb[at];
-      }
-      // (keeps the loads in front of the stores' branches — see ctc_alpha_beta_wave_body in lr_ctc.hip)
-      asm volatile("" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]));
-      asm volatile("" : "+v"(r[5]), "+v"(r[6]), "+v"(r[7]), "+v"(r[8]), "+v"(r[9]));
-#pragma unroll
-      for (int u = 0; u < 10; ++u) {
-        const int i = i0 + u * nthr + tid;
-        if (i < tot) lat[i] = r[u];
-      }
-    }
+  if (LAT_LDS) {   // ---- the sample's n rows into LDS
+    lr_stage_rows(lat, lpb, n, C, stt, tid, nthr);
     __syncthreads();
   }
 
   // ---- forward: thread s owns state s
   const int S = 2 * L + 1;
-  const int nch = (n + kChunk - 1) / kChunk;
+  const int nch = (n + LR_LATTICE_CHUNK - 1) / LR_LATTICE_CHUNK;
   if (!ONE_WAVE || wave == 0) {
     const int s = ONE_WAVE ? lane : tid;
     int cls = a.blank;
     bool skip = false;
-    if ((s & 1) && s < S) {
-      cls = lab[s >> 1];
-      skip = s >= 3 && lab[(s >> 1) - 1] != cls;
-    }
+    if ((s & 1) && s < S) lr_state_class(lab, s >> 1, cls, skip);
     auto load16 = [&](float* r, int k) {
 #pragma unroll
-      for (int j = 0; j < kChunk; ++j) {
-        int t = k * kChunk + j;
+      for (int j = 0; j < LR_LATTICE_CHUNK; ++j) {
+        int t = k * LR_LATTICE_CHUNK + j;
         if (t >= n) t = n - 1;
         r[j] = LAT_LDS ? lat[t * C + cls] : lpb[(int64_t)t * stt + cls];
       }
@@ -221,19 +191,19 @@ __global__ __launch_bounds__(ONE_WAVE ? kStageThreads : 576) void align_kernel(c
     // a virtual row before the first: 0 on state 0, so that step 0 gives v[0][0] = lp[0][blank], v[0][1] = lp[0][y[0]]
     // and -inf elsewhere (0 + x is exact); its codes are never followed
     float v = s == 0 ? 0.f : LR_NEG_INF;
-    float cur[kChunk], nxt[kChunk];
+    float cur[LR_LATTICE_CHUNK], nxt[LR_LATTICE_CHUNK];
     load16(cur, 0);
     for (int k = 0; k < nch; ++k) {
       load16(nxt, k + 1 < nch ? k + 1 : k);
       uint32_t word = 0;
 #pragma unroll
-      for (int j = 0; j < kChunk; ++j) {
-        const int t = k * kChunk + j;
+      for (int j = 0; j < LR_LATTICE_CHUNK; ++j) {
+        const int t = k * LR_LATTICE_CHUNK + j;
         if (t < n) {   // (uniform)
           float a1, a2;
           if (ONE_WAVE) {
-            a1 = wave_up1(v);
-            a2 = wave_up1(a1);
+            a1 = lr_wave_up1(v);
+            a2 = lr_wave_up1(a1);
           } else {
             float* row = rows + (t & 1) * sst;
             row[s] = v;
@@ -243,22 +213,20 @@ __global__ __launch_bounds__(ONE_WAVE ? kStageThreads : 576) void align_kernel(c
           }
           if (!skip) a2 = LR_NEG_INF;
           float best = v;
-          uint32_t code = 0;
-          if (a1 > best) { best = a1; code = 1; }
-          if (a2 > best) { best = a2; code = 2; }
+          const uint32_t code = lr_viterbi_cell(best, a1, a2);
           v = best + cur[j];
-          word |= code << (2 * j);
+          word = lr_bp_pack(word, code, j);
         }
       }
       bp[k * sst + s] = word;
 #pragma unroll
-      for (int j = 0; j < kChunk; ++j) cur[j] = nxt[j];
+      for (int j = 0; j < LR_LATTICE_CHUNK; ++j) cur[j] = nxt[j];
     }
     // ---- end state and total
     if (ONE_WAVE) {
       const float vb = __shfl(v, 2 * L, 64), vc = __shfl(v, L ? 2 * L - 1 : 0, 64);
       if (lane == 0) {
-        const int end = L == 0 ? 0 : (vb > vc ? 2 * L : 2 * L - 1);
+        const int end = end_state(L, vb, vc);
         s_flag = end;
         s_total = end == 2 * L ? vb : vc;
       }
@@ -270,7 +238,7 @@ __global__ __launch_bounds__(ONE_WAVE ? kStageThreads : 576) void align_kernel(c
   if (!ONE_WAVE && tid == 0) {
     const float* row = rows + (n & 1) * sst;
     const float vb = row[2 * L], vc = row[L ? 2 * L - 1 : 0];
-    const int end = L == 0 ? 0 : (vb > vc ? 2 * L : 2 * L - 1);
+    const int end = end_state(L, vb, vc);
     s_flag = end;
     s_total = end == 2 * L ? vb : vc;
   }
@@ -287,25 +255,24 @@ __global__ __launch_bounds__(ONE_WAVE ? kStageThreads : 576) void align_kernel(c
     int s_next = -1;
     for (int k = nch - 1; k >= 0; --k) {
       const int s_top = s;
-      const int idx = s_top - lane;
-      const uint32_t w = lane <= 2 * kChunk && idx >= 0 ? bp[k * sst + idx] : 0u;
-      const int jhi = min(kChunk - 1, n - 1 - k * kChunk);
+      const uint32_t w = lr_bp_fetch(bp, k * sst, s_top, lane);
+      const int jhi = min(LR_LATTICE_CHUNK - 1, n - 1 - k * LR_LATTICE_CHUNK);
       int ft = -1;
 #pragma unroll
-      for (int j = kChunk - 1; j >= 0; --j) {
+      for (int j = LR_LATTICE_CHUNK - 1; j >= 0; --j) {
         if (j > jhi) continue;   // (uniform)
-        const int t = k * kChunk + j;
+        const int t = k * LR_LATTICE_CHUNK + j;
         const int i = s >> 1;
         if (lane == j) ft = (s & 1) ? i : -1;
         if ((s & 1) && lane == 0) {
           tst[i] = t;
           if (s != s_next) ten[i] = t + 1;
         }
-        const uint32_t word = (uint32_t)__builtin_amdgcn_readlane((int)w, __builtin_amdgcn_readfirstlane(s_top - s));
+        const int code = lr_bp_code(w, s_top, s, j);
         s_next = s;
-        if (t > 0) s -= (int)((word >> (2 * j)) & 3u);
+        if (t > 0) s -= code;
       }
-      if (lane <= jhi) a.frame_token[(int64_t)b * T + k * kChunk + lane] = ft;
+      if (lane <= jhi) a.frame_token[(int64_t)b * T + k * LR_LATTICE_CHUNK + lane] = ft;
     }
   }
   for (int t = n + tid; t < T; t += nthr) a.frame_token[(int64_t)b * T + t] = -1;

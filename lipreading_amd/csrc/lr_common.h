@@ -30,6 +30,8 @@ static inline int lr_launch_status() {
   } while (0)
 
 static inline size_t lr_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// dynamic share of the 64 KB a workgroup takes without opting in to more (the 512 cover the kernels' static LDS, <= 272)
+constexpr size_t LR_LDS_BUDGET = 65536 - 512;
 
 #define LR_NEG_INF (-__builtin_inff())
 

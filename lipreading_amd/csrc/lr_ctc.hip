@@ -232,10 +232,10 @@ __device__ __forceinline__ void ctc_alpha_beta_wave_body(char* smem_raw, const f
         const int q = q0 + u * 128 + tid;  // inside its branch, which would serialise the ten round trips
         v4[u] = g4[q < qhi ? q : qhi - 1];
       }
-      // The values are only used under the `q < qhi` of the store loop below, so hipcc would SINK each load into its
-      // store's branch after all — ten times {branch, global_load_dwordx4, vmcnt(0), ds_write_b128}, the serialised
-      // round trips the clamped loads were written to avoid.  Two empty asm statements that take the registers as
-      // operands keep five loads each in front of a single wait.  MEASURED (round 4): 23.6 -> 21.8 us (regime R).
+      // Two register pins keep five loads each in front of a single wait, or hipcc would sink every load into its
+      // store's branch — ten times {branch, global_load_dwordx4, vmcnt(0), ds_write_b128}; the reason is written out
+      // at lr_stage_rows in lr_lattice_dev.h, the scalar form of this staging.  MEASURED (round 4): 23.6 -> 21.8 us
+      // (regime R).
 #define LR_PIN4(u) "+v"(v4[u].x), "+v"(v4[u].y), "+v"(v4[u].z), "+v"(v4[u].w)
       asm volatile("" : LR_PIN4(0), LR_PIN4(1), LR_PIN4(2), LR_PIN4(3), LR_PIN4(4));
       asm volatile("" : LR_PIN4(5), LR_PIN4(6), LR_PIN4(7), LR_PIN4(8), LR_PIN4(9));

@@ -29,8 +29,6 @@ namespace {
 
 constexpr int kMaxDist = LR_EDIT_MAX_CHARS;         // expanded characters per side, distance modes
 constexpr int kMaxAlign = LR_EDIT_MAX_ALIGN_CHARS;  // per side, alignment mode
-constexpr size_t kLdsBudget = 65536 - 512;          // dynamic share of the 64 KB a workgroup takes without opting in to more
-                                                    // (the kernels' static LDS is 264-272 bytes)
 constexpr int kOneWaveCap = 512;
 constexpr int kOut = LR_EDIT_OUT_STRIDE;
 
@@ -70,7 +68,7 @@ int edit_plan(int B, int hyp_width, int ref_width, int max_spelling, int mode, E
   p->dirs_in_lds = 0;
   if (mode == LR_EDIT_CHARS_ALIGN) {
     p->dirs_bytes = lr_align_up((size_t)p->capH * ((p->capR + 3) / 4), 4);
-    if (off + p->dirs_bytes <= kLdsBudget) {
+    if (off + p->dirs_bytes <= LR_LDS_BUDGET) {
       p->dirs_in_lds = 1;
       off += p->dirs_bytes;
     }

@@ -28,8 +28,8 @@
 //               per thread in token order.
 //
 // Every offset into the table is 64-bit: at the limits it is 538 MB per sample.  Dead lanes (s > 2L) are not masked: a
-// state only reads states below it.  Lanes below state 0 are held at -inf.
-#include "lr_common.h"
+// state only reads states below it.  Lanes below state 0 are held at -inf.  Cell and table: lr_lattice_dev.h.
+#include "lr_lattice_dev.h"
 
 namespace {
 
@@ -42,10 +42,9 @@ constexpr int kWaveOwn = LR_WAVE - kWaveHalo;         // 46 lanes a wave owns
 constexpr int kSpan = kWaves * kWaveOwn;              // 368 states a workgroup computes (besides the lowest wave's halo)
 constexpr int kHalo = 2 * kF + 2;                     // +2: state 2L-1 stays exact through the chunk's last step when 2L is a tile's first state
 constexpr int kOwn = kSpan - kHalo;                   // 238 states a workgroup owns
-constexpr int kChunk = 16;                            // steps per back-pointer dword
 constexpr int kRecWords = 16;                         // per-sample record in the workspace (64 bytes)
 constexpr int kFwdLds = 2 * kSpan * 4;                // the double-buffered exchange row
-static_assert(kF % kE == 0 && kChunk % kE == 0 && kOwn > 0, "exchanges fall on step boundaries of a dword");
+static_assert(kF % kE == 0 && LR_LATTICE_CHUNK % kE == 0 && kOwn > 0, "exchanges fall on step boundaries of a dword");
 
 enum { REC_VALUE = 0, REC_T = 1, REC_S = 2, REC_STATUS = 3 };
 
@@ -61,7 +60,7 @@ int seg_plan(int B, int T, int C, int max_tokens, SegPlan* p) {
   const int S = 2 * max_tokens + 1;
   p->tiles = (S + kOwn - 1) / kOwn;
   p->sst = p->tiles * kOwn;
-  p->nch = (T + kChunk - 1) / kChunk;
+  p->nch = (T + LR_LATTICE_CHUNK - 1) / LR_LATTICE_CHUNK;
   p->launches = (T + kF - 1) / kF;
   p->bp_words = (size_t)p->nch * p->sst;
   p->row_words = (size_t)2 * p->sst;
@@ -99,11 +98,6 @@ struct SegArgs {
   int sst, nch;
 };
 
-// v of the lane below (lane 0: -inf) — DPP wave_shr:1, as lr_align.hip's one-wave kernel
-__device__ __forceinline__ float wave_up1(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(LR_NEG_INF), __float_as_int(v), 0x138, 0xf, 0xf, false));
-}
-
 // ---- prepare: status and end record of every sample ---------------------------------------------------------------
 __global__ __launch_bounds__(256) void seg_prepare_kernel(const SegArgs a) {
   const int b = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
@@ -118,8 +112,7 @@ __global__ __launch_bounds__(256) void seg_prepare_kernel(const SegArgs a) {
     const int32_t* y = a.targets + (int64_t)b * W;
     int bad = 0;
     for (int i = tid; i < L; i += nthr) {
-      const int c = y[i];
-      bad |= !((unsigned)c < (unsigned)a.C && c != a.blank);
+      bad |= !lr_label_ok(y[i], a.C, a.blank);
     }
     if (__syncthreads_or(bad)) {
       st = LR_SEG_BAD_ID;
@@ -168,10 +161,7 @@ __global__ __launch_bounds__(kThreads) void seg_forward_kernel(const SegArgs a, 
   const int32_t* y = a.targets + (int64_t)b * a.target_stride;
   int cls = a.blank;
   bool skip = false;
-  if (s >= 0 && (s & 1) && s <= 2 * L) {
-    cls = y[s >> 1];
-    skip = s >= 3 && y[(s >> 1) - 1] != cls;
-  }
+  if (s >= 0 && (s & 1) && s <= 2 * L) lr_state_class(y, s >> 1, cls, skip);
   const bool fresh_state = s == 0 || s == 1;
   const bool free_start = a.flags & LR_SEG_FREE_START, free_end = a.flags & LR_SEG_FREE_END;
   const bool end_thread = wave_owned && s == 2 * L;   // (owned: 2L >= base, and < base + kOwn or a higher tile would hold it)
@@ -198,21 +188,21 @@ __global__ __launch_bounds__(kThreads) void seg_forward_kernel(const SegArgs a, 
   };
   auto load16 = [&](float* r, int g) {
 #pragma unroll
-    for (int j = 0; j < kChunk; ++j) {
-      int t = t0 + g * kChunk + j;
+    for (int j = 0; j < LR_LATTICE_CHUNK; ++j) {
+      int t = t0 + g * LR_LATTICE_CHUNK + j;
       if (t >= n) t = n - 1;
       r[j] = lpb[(int64_t)t * stt + cls];
     }
   };
-  const int groups = (steps + kChunk - 1) / kChunk;
-  float cur[kChunk], nxt[kChunk];
+  const int groups = (steps + LR_LATTICE_CHUNK - 1) / LR_LATTICE_CHUNK;
+  float cur[LR_LATTICE_CHUNK], nxt[LR_LATTICE_CHUNK];
   load16(cur, 0);
   for (int g = 0; g < groups; ++g) {
     load16(nxt, g + 1 < groups ? g + 1 : g);
     uint32_t word = 0;
 #pragma unroll
-    for (int j = 0; j < kChunk; ++j) {
-      const int i = g * kChunk + j;   // step of this launch
+    for (int j = 0; j < LR_LATTICE_CHUNK; ++j) {
+      const int i = g * LR_LATTICE_CHUNK + j;   // step of this launch
       if (i < steps) {                // (uniform)
         const int t = t0 + i;
         if (i > 0 && i % kE == 0) {   // exchange: halo lanes take over what the wave below computed
@@ -221,26 +211,23 @@ __global__ __launch_bounds__(kThreads) void seg_forward_kernel(const SegArgs a, 
           lr_lds_barrier();
           if (!wave_owned && pos >= 0) v = row[pos];
         }
-        float a1 = wave_up1(v);
-        float a2 = wave_up1(a1);
+        float a1 = lr_wave_up1(v), a2 = lr_wave_up1(a1);
         if (end_thread && i > 0) end_candidates(t - 1, a1, v);
         if (!skip) a2 = LR_NEG_INF;
         float best = v;
-        uint32_t code = 0;
-        if (a1 > best) { best = a1; code = 1; }
-        if (a2 > best) { best = a2; code = 2; }
+        uint32_t code = lr_viterbi_cell(best, a1, a2);
         if (fresh_state && (t == 0 || free_start) && 0.f > best) { best = 0.f; code = 3; }
         v = s < 0 ? LR_NEG_INF : best + cur[j];
-        word |= code << (2 * j);
+        word = lr_bp_pack(word, code, j);
       }
     }
-    if (owned) bp[(int64_t)(t0 / kChunk + g) * a.sst + s] = word;
+    if (owned) bp[(int64_t)(t0 / LR_LATTICE_CHUNK + g) * a.sst + s] = word;
 #pragma unroll
-    for (int j = 0; j < kChunk; ++j) cur[j] = nxt[j];
+    for (int j = 0; j < LR_LATTICE_CHUNK; ++j) cur[j] = nxt[j];
   }
   // ---- the last frame's end candidates need one more shift; the row goes out for the next chunk
   {
-    const float below = wave_up1(v);
+    const float below = lr_wave_up1(v);
     if (end_thread) {
       end_candidates(t0 + steps - 1, below, v);
       rec[REC_VALUE] = __float_as_int(ev);
@@ -275,20 +262,18 @@ __global__ __launch_bounds__(64) void seg_walk_kernel(const SegArgs a) {
   for (int t = t_end + 1 + lane; t < T; t += 64) ftb[t] = -1;
   int t_first = 0;
   bool done = false;
-  int k = t_end / kChunk;
+  int k = t_end / LR_LATTICE_CHUNK;
   for (; k >= 0 && !done; --k) {
     const int s_top = s;
-    const int idx = s_top - lane;
-    const uint32_t w = lane <= 2 * kChunk && idx >= 0 ? bp[(int64_t)k * a.sst + idx] : 0u;
-    const int jhi = min(kChunk - 1, t_end - k * kChunk);
+    const uint32_t w = lr_bp_fetch(bp, (int64_t)k * a.sst, s_top, lane);
+    const int jhi = min(LR_LATTICE_CHUNK - 1, t_end - k * LR_LATTICE_CHUNK);
     int ft = -1;
 #pragma unroll
-    for (int j = kChunk - 1; j >= 0; --j) {
+    for (int j = LR_LATTICE_CHUNK - 1; j >= 0; --j) {
       if (j > jhi || done) continue;   // (uniform)
-      const int t = k * kChunk + j;
+      const int t = k * LR_LATTICE_CHUNK + j;
       if (lane == j) ft = (s & 1) ? (s >> 1) : -1;
-      const uint32_t word = (uint32_t)__builtin_amdgcn_readlane((int)w, __builtin_amdgcn_readfirstlane(s_top - s));
-      const int code = (int)((word >> (2 * j)) & 3u);
+      const int code = lr_bp_code(w, s_top, s, j);
       if (code == 3 || t == 0) {
         done = true;
         t_first = t;
@@ -296,10 +281,10 @@ __global__ __launch_bounds__(64) void seg_walk_kernel(const SegArgs a) {
         s -= code;
       }
     }
-    if (lane <= jhi) ftb[k * kChunk + lane] = ft;
+    if (lane <= jhi) ftb[k * LR_LATTICE_CHUNK + lane] = ft;
   }
   // (k + 1 is the chunk the walk stopped in; its frames before the path were stored as -1 above)
-  for (int t = lane; t < (k + 1) * kChunk; t += 64) ftb[t] = -1;
+  for (int t = lane; t < (k + 1) * LR_LATTICE_CHUNK; t += 64) ftb[t] = -1;
   if (lane == 0) {
     a.status[b] = 0;
     a.total[b] = total;

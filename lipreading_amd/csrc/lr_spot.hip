@@ -5,9 +5,9 @@
 //
 // ONE launch per call.  A workgroup (four waves) belongs to one sample and serves four keyword slots of it, one a wave:
 //
-//   rows        the sample's n rows go into LDS once per workgroup and become ratios in place (a wave per row: maximum,
-//               one subtraction per element) while n*C*4 bytes fit; else only m[t] lies in LDS and a lane forms
-//               lp[t][cls] - m[t] as it prefetches.  Either way the same single fp32 subtraction per (t, c).
+//   rows        the sample's n rows go into LDS once per workgroup (lr_stage_rows) and become ratios in
+//               place (a wave per row: maximum, one subtraction per element) while n*C*4 bytes fit; else only m[t] lies in
+//               LDS and a lane forms lp[t][cls] - m[t] as it prefetches.  Either way one fp32 subtraction per (t, c).
 //   slots       a slot is four consecutive keywords and belongs to one wave.  The wave runs it in passes: the widest
 //               keyword left decides the segment (16 lanes up to 8 tokens, 32 up to 16, 64 up to 32) and 64 / segment
 //               keywords go side by side.  Sorted by length (spot.py does that) a slot takes one pass at 4, two at 2
@@ -27,17 +27,15 @@
 // Lanes past a keyword's last state are not masked: a state only reads states below it in its own segment.
 #include <type_traits>
 
-#include "lr_common.h"
+#include "lr_lattice_dev.h"
 
 namespace {
 
 constexpr int kMaxKw = LR_SPOT_MAX_KW_LEN;
 constexpr int kMaxT = LR_SPOT_MAX_T;
 constexpr int kMaxHits = LR_SPOT_MAX_HITS;
-constexpr size_t kLdsBudget = 65536 - 512;   // as lr_align.hip
 constexpr int kThreads = 256, kWaves = 4;
 constexpr int kSlot = 4;                     // keywords per wave slot (= keywords side by side at 16-lane segments)
-constexpr int kChunk = 16;                   // steps per prefetch block
 constexpr int kLen16 = 8, kLen32 = 16;       // the longest keyword of a 16- / 32-lane segment (2L-1 <= 15 / 31)
 
 enum { TRACE_LDS = 0, TRACE_WORKSPACE = 1, TRACE_CALLER = 2 };
@@ -56,11 +54,11 @@ int spot_plan(int B, int T, int C, int K, int max_kw_len, int H, SpotPlan* p) {
   if (max_kw_len > kMaxKw || T > kMaxT || H > kMaxHits) return LR_ERR_UNSUPPORTED;
   const size_t rows = lr_align_up((size_t)T * C * 4, 16);
   const size_t trace = (size_t)kWaves * kSlot * T * 8;   // score and start of 16 keywords in flight
-  p->rows_in_lds = rows <= kLdsBudget;
+  p->rows_in_lds = rows <= LR_LDS_BUDGET;
   size_t off = p->rows_in_lds ? rows : lr_align_up((size_t)T * 4, 16);
   p->off_trace = (unsigned)off;
   // (only beside staged rows: one threshold in T, not two)
-  p->trace_in_lds = p->rows_in_lds && off + trace <= kLdsBudget;
+  p->trace_in_lds = p->rows_in_lds && off + trace <= LR_LDS_BUDGET;
   if (p->trace_in_lds) off += trace;
   p->lds_bytes = off;
   p->ws_bytes = p->trace_in_lds ? 16 : (size_t)B * K * T * 8;
@@ -88,13 +86,6 @@ struct SpotArgs {
   int pad_trace;       // the trace is the caller's: every (b, k, t) is written
   SpotPlan plan;
 };
-
-// the lane below's value (lane 0: `fill`) — DPP wave_shr:1, as lr_align.hip
-__device__ __forceinline__ float wave_up1(float v) {
-  return __int_as_float(
-      __builtin_amdgcn_update_dpp(__float_as_int(LR_NEG_INF), __float_as_int(v), 0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ int wave_up1(int v) { return __builtin_amdgcn_update_dpp(-1, v, 0x138, 0xf, 0xf, false); }
 
 __device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
 
@@ -132,30 +123,7 @@ __global__ __launch_bounds__(kThreads) void spot_kernel(const SpotArgs a) {
 
   if (n_ok) {
     if (ROWS_LDS) {
-      // ---- the sample's n rows into LDS, coalesced, ten loads of a thread in flight (lr_align.hip)
-      const int tot = n * C;
-      const bool dense = stt == C;
-      for (int i0 = 0; i0 < tot; i0 += kThreads * 10) {
-        float r[10];
-#pragma unroll
-        for (int u = 0; u < 10; ++u) {   // unconditional (clamped) loads
-          int i = i0 + u * kThreads + tid;
-          if (i >= tot) i = tot - 1;
-          int64_t at = i;
-          if (!dense) {
-            const int t = i / C;
-            at = (int64_t)t * stt + (i - t * C);
-          }
-          r[u] = lpb[at];
-        }
-        asm volatile("" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]));
-        asm volatile("" : "+v"(r[5]), "+v"(r[6]), "+v"(r[7]), "+v"(r[8]), "+v"(r[9]));
-#pragma unroll
-        for (int u = 0; u < 10; ++u) {
-          const int i = i0 + u * kThreads + tid;
-          if (i < tot) rows[i] = r[u];
-        }
-      }
+      lr_stage_rows(rows, lpb, n, C, stt, tid, kThreads);   // ---- the sample's n rows into LDS
       __syncthreads();
       // ---- ratios in place: a wave per row
       for (int t = wave; t < n; t += kWaves) {
@@ -220,12 +188,8 @@ __global__ __launch_bounds__(kThreads) void spot_kernel(const SpotArgs a) {
       bool skip = false, bad = false;
       if (len_ok && j < S && !(j & 1)) {
         const int32_t* y = a.kw + (int64_t)k * a.kw_stride;
-        const int c = y[j >> 1];
-        bad = !((unsigned)c < (unsigned)C && c != a.blank);
-        if (!bad) {
-          cls = c;
-          skip = j >= 2 && y[(j >> 1) - 1] != c;
-        }
+        bad = !lr_label_ok(y[j >> 1], C, a.blank);
+        if (!bad) lr_state_class(y, j >> 1, cls, skip);
       }
       const unsigned long long badmask = __ballot(bad && mine);
       const unsigned long long segmask = seg == 64 ? ~0ull : ((1ull << seg) - 1);
@@ -249,28 +213,28 @@ __global__ __launch_bounds__(kThreads) void spot_kernel(const SpotArgs a) {
       // ---- the chain
       auto load16 = [&](float* r, int blk) {
 #pragma unroll
-        for (int i = 0; i < kChunk; ++i) {
-          int t = blk * kChunk + i;
+        for (int i = 0; i < LR_LATTICE_CHUNK; ++i) {
+          int t = blk * LR_LATTICE_CHUNK + i;
           if (t >= n) t = n - 1;
           r[i] = ROWS_LDS ? rows[t * C + cls] : lpb[(int64_t)t * stt + cls] - rows[t];
         }
       };
-      const int nblk = (n + kChunk - 1) / kChunk;
+      const int nblk = (n + LR_LATTICE_CHUNK - 1) / LR_LATTICE_CHUNK;
       float v = LR_NEG_INF;
       int st = -1;
-      float cur[kChunk], nxt[kChunk];
+      float cur[LR_LATTICE_CHUNK], nxt[LR_LATTICE_CHUNK];
       load16(cur, 0);
       // one block of 16 steps; FULL: all of them lie inside the clip (no per-step test, nothing to keep for the stores)
       auto block = [&](int blk, auto full) {
         constexpr bool FULL = decltype(full)::value;
-        float ev[kChunk];
-        int es[kChunk];
+        float ev[LR_LATTICE_CHUNK];
+        int es[LR_LATTICE_CHUNK];
 #pragma unroll
-        for (int i = 0; i < kChunk; ++i) {
-          const int t = blk * kChunk + i;
+        for (int i = 0; i < LR_LATTICE_CHUNK; ++i) {
+          const int t = blk * LR_LATTICE_CHUNK + i;
           if (FULL || t < n) {   // (uniform)
-            const float a1r = wave_up1(v), a2r = wave_up1(a1r);
-            const int s1r = wave_up1(st), s2r = wave_up1(s1r);
+            const float a1r = lr_wave_up1(v), a2r = lr_wave_up1(a1r);
+            const int s1r = lr_wave_up1(st), s2r = lr_wave_up1(s1r);
             const float a1 = j >= 1 ? a1r : LR_NEG_INF;
             const float a2 = skip ? a2r : LR_NEG_INF;
             float best = v;
@@ -285,24 +249,24 @@ __global__ __launch_bounds__(kThreads) void spot_kernel(const SpotArgs a) {
           es[i] = st;
         }
         if (tail) {
-          const int left = FULL ? kChunk : n - blk * kChunk;
+          const int left = FULL ? LR_LATTICE_CHUNK : n - blk * LR_LATTICE_CHUNK;
 #pragma unroll
-          for (int i = 0; i < kChunk; ++i) {
+          for (int i = 0; i < LR_LATTICE_CHUNK; ++i) {
             if (FULL || i < left) {
-              trs[blk * kChunk + i] = ev[i];
-              trst[blk * kChunk + i] = es[i];
+              trs[blk * LR_LATTICE_CHUNK + i] = ev[i];
+              trst[blk * LR_LATTICE_CHUNK + i] = es[i];
             }
           }
         }
       };
       for (int blk = 0; blk < nblk; ++blk) {
         load16(nxt, blk + 1 < nblk ? blk + 1 : blk);
-        if ((blk + 1) * kChunk <= n)
+        if ((blk + 1) * LR_LATTICE_CHUNK <= n)
           block(blk, std::true_type());
         else
           block(blk, std::false_type());
 #pragma unroll
-        for (int i = 0; i < kChunk; ++i) cur[i] = nxt[i];
+        for (int i = 0; i < LR_LATTICE_CHUNK; ++i) cur[i] = nxt[i];
       }
       // the tail lanes' stores before the other lanes' loads of them
       __threadfence_block();
