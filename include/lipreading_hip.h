@@ -500,6 +500,57 @@ int lr_xgemm(int transA, int transB, int M, int N, int K, float alpha, const flo
              const float* B, int ldb, float beta, float* C, int ldc, const float* bias, int a_exact,
              int b_exact, void* workspace, size_t workspace_bytes, lr_stream_t stream);
 
+/* ---- A3 sessions (BUILD-DEFINED, no reference symbol): the uni-directional stack fed chunk by chunk ------------ */
+/* An encoder session is one device buffer owned by the caller: for B independent slots the hidden state (LSTM: and
+ * the cell state) of every layer of a stacked uni-directional GRU / LSTM / tanh RNN (lipreading_amd/csrc/
+ * lr_rnn_stream.hip).  Fed the same frames in any chunks, in any slot of any batch, a session computes
+ * the same bits.  mode is a plain cell (LR_RNN_GRU / LR_RNN_LSTM / LR_RNN_TANH): a flagged mode is rejected.
+ * With G = 3 / 4 / 1 gates, HT = ceil(H / 16), Hp = 16 HT, a256(n) = n rounded up to a multiple of 256:
+ *   pack      per layer l (I_l = I for l = 0, else H): a256(4 * HT * (ceil(I_l / 16) + HT) * G * 256) bytes of
+ *             [W_ih | W_hh] fragments, then a256(4 * layers * 4 * Hp) bytes of biases (b_ih + b_hh per gate; the
+ *             GRU's b_in and b_hn apart)
+ *   state     a256(32 * B) bytes of slot headers (int32: magic, B, H, layers, cell, frames consumed — saturating —,
+ *             status bits, 0), then h [layers][B][Hp] in a256(4 * layers * B * Hp) bytes, then (LSTM) c likewise
+ *   workspace a256(4 * layers * max(chunk_T, 1) * B * Hp) bytes of per-frame planes, then (LSTM) a256(4 * layers * B * Hp)
+ * Limits: layers <= 16, C <= 256, chunk_T <= 2^20, B <= 16 * 65535 (else 0 bytes / LR_ERR_UNSUPPORTED).  Buffers
+ * smaller than their *_bytes answer LR_ERR_WORKSPACE, NULLs and negative sizes LR_ERR_INVALID_ARG, before any launch.
+ * state, pack and workspace must be 16-byte aligned. */
+#define LR_RNN_STREAM_MISMATCH 1 /* a call's B, H, layers or cell is not the slot's */
+
+size_t lr_rnn_stream_pack_bytes(int mode, int I, int H, int layers);              /* 0 for arguments it rejects */
+/* w_ih / w_hh / b_ih / b_hh: host arrays of `layers` device pointers, torch.nn layouts; any I >= 1, H >= 1, no
+ * alignment asked of the tensors.  Made once per weight set. */
+int lr_rnn_stream_pack(void* out, size_t out_bytes, int mode, const float* const* w_ih, const float* const* w_hh,
+                       const float* const* b_ih, const float* const* b_hh, int I, int H, int layers,
+                       lr_stream_t stream);
+size_t lr_rnn_stream_state_bytes(int mode, int B, int H, int layers);             /* 0 for arguments it rejects */
+size_t lr_rnn_stream_workspace_bytes(int mode, int B, int chunk_T, int I, int H, int layers,
+                                     int C);                                      /* C = 0: no head; 0 if rejected */
+
+/* Slots with mask[b] != 0 (mask [B] int32 on the device; NULL: all) go back to the zero state with 0 frames and no
+ * status bit; the others keep every bit.  Under a mask the slot must already carry this configuration (else it is left
+ * alone and gets LR_RNN_STREAM_MISMATCH); with NULL whatever the buffer held is overwritten. */
+int lr_rnn_stream_reset(void* state, size_t state_bytes, const int32_t* mask, int mode, int B, int H, int layers,
+                        lr_stream_t stream);
+
+/* Slot b consumes frames [0, clamp(sizes[b], 0, chunk_T)) of x[b] (x + b * stride_b + t * stride_t, I floats of unit
+ * stride; sizes NULL = chunk_T): layers * chunk_T step launches, one head launch if head_w / head_b / head_mask are
+ * given (all three or none; with them log_probs [B][chunk_T][C], without them log_probs NULL), one commit launch.
+ * y [B][chunk_T][H] (may be NULL) is the last layer's output, zero at t >= sizes[b]; log_probs there is the head of the
+ * zero row.  A slot with no frame keeps every bit of its state.  A slot whose header disagrees with B, H, layers or the
+ * cell is left alone and gets LR_RNN_STREAM_MISMATCH, which stays until a reset.  chunk_T == 0 does nothing. */
+int lr_rnn_stream_advance(int mode, const float* x, int64_t stride_b, int64_t stride_t, const int32_t* sizes,
+                          const void* pack, size_t pack_bytes, const float* head_w, const float* head_b,
+                          const float* head_mask, float* y, float* log_probs, void* state, size_t state_bytes,
+                          void* workspace, size_t workspace_bytes, int B, int chunk_T, int I, int H, int layers, int C,
+                          lr_stream_t stream);
+
+/* h [layers][B][H], c likewise (NULL unless the state is an LSTM's), frames [B], status [B] (each may be NULL, not
+ * all): what the slots hold, without changing a byte of the state.  A slot whose header is not (B, H, layers), or whose
+ * cell does not go with c, reads as zeros with LR_RNN_STREAM_MISMATCH in status[b]. */
+int lr_rnn_stream_read(const void* state, size_t state_bytes, float* h, float* c, int32_t* frames, int32_t* status,
+                       int B, int H, int layers, lr_stream_t stream);
+
 /* ---- A3 tail: output_proj + masked_log_softmax — better_model.py:92-93 ------------------ */
 
 /* log_probs[r,:] = log_softmax(hidden[r,:] @ W^T + bias + log(mask + 1e-45))

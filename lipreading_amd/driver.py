@@ -51,6 +51,10 @@ DEFAULTS = dict(  # train.py:134-167
     # without the flag; what it adds is the validation pass's commit delay — how many frames after it was spoken a
     # character of the final transcript became final (mean, 90th percentile, share committed only at the end)
     stream_chunk=0,
+    # --stream_encoder=True with --stream_chunk=N: the evaluation's encoder runs chunk by chunk as well, through a
+    # resumable encoder session (encoder_stream.ChunkedEncoder) — the whole live transcriber, not only
+    # its search.  Needs --ctc_decoder=beam, --bidirectional=False, --encoder=rnn and --frontend=none
+    stream_encoder=False,
     # the error of a model WITH the attention decoder: teacher (the live loop's sampled-token mismatch rate under
     # teacher forcing, train.eval) or beam (the edit-distance CER of the decoder's own beam-search transcript,
     # train.attention_cer, --attn_beam_width hypotheses of up to --attn_max_label_len characters) or joint (the same
@@ -192,6 +196,7 @@ def parse_flags(argv, defaults=DEFAULTS):
     raise SystemExit("--stream_chunk must be >= 0")
   if out.get("stream_chunk") and out.get("ctc_decoder") != "beam":
     raise SystemExit("--stream_chunk needs --ctc_decoder=beam")
+  stream_encoder_check(out)
   if out.get("attn_decode") not in ("teacher", "beam", "joint"):
     raise SystemExit("--attn_decode must be teacher, beam or joint")
   if out.get("attn_decode") == "joint" and not out.get("enable_ctc"):
@@ -498,6 +503,20 @@ def weights_path(root, data):
   return path
 
 
+def stream_encoder_check(f):
+  """--stream_encoder needs what an encoder session can run: SystemExit otherwise."""
+  if not f.get("stream_encoder"):
+    return
+  if not int(f.get("stream_chunk") or 0) > 0:
+    raise SystemExit("--stream_encoder needs --stream_chunk>0 (the chunk the encoder is fed in)")
+  if f.get("ctc_decoder") != "beam":
+    raise SystemExit("--stream_encoder needs --ctc_decoder=beam")
+  if f.get("bidirectional"):
+    raise SystemExit("--stream_encoder needs --bidirectional=False: a session runs causally")
+  if f.get("encoder") != "rnn" or f.get("frontend") != "none":
+    raise SystemExit("--stream_encoder needs --encoder=rnn and --frontend=none")
+
+
 def _cer(correct, count):
   return float(count - correct) / count if count else 1.0
 
@@ -565,6 +584,7 @@ def run(**flags):
   spot_check(f)
   segment_check(f)
   mwer_check(f)
+  stream_encoder_check(f)
   torch.manual_seed(f["seed"])
   rand = np.random.RandomState(seed=f["seed"])
   assert torch.cuda.is_available(), "the driver runs the HIP path: an MI355X is required (no CPU fallback)"
@@ -636,7 +656,13 @@ def run(**flags):
   if ctc_decoder is not None and f["stream_chunk"]:
     from .decoder import ChunkedBeamDecoder
     chunked = ChunkedBeamDecoder(ctc_decoder, f["stream_chunk"])
-  error_of = make_error_of(f, encoder, decoding_step, chunked or ctc_decoder, device, char2idx)
+  eval_encoder = encoder
+  if f["stream_encoder"]:
+    if chunked is None or decoding_step is not None:
+      raise SystemExit("--stream_encoder needs the encoder + CTC loop (--enable_ctc=True --ctc_only=True)")
+    from .encoder_stream import ChunkedEncoder
+    eval_encoder = ChunkedEncoder(encoder, f["stream_chunk"])
+  error_of = make_error_of(f, eval_encoder, decoding_step, chunked or ctc_decoder, device, char2idx)
 
   def validation_error():
     """error_of(val_loader); with --stream_chunk also the pass's commit delay, printed and returned."""
@@ -645,11 +671,12 @@ def run(**flags):
     chunked.commit_delay()   # what the passes since the last validation left
     cer = error_of(val_loader)
     delay = chunked.commit_delay()
+    streamed = " (encoder streamed)" if f["stream_encoder"] else ""
     if delay["chars"]:
-      print("\tCommit delay (chunks of %d frames): mean %.2f frames, p90 %d, %.1f%% of %d characters only at the end"
-            % (f["stream_chunk"], delay["mean"], delay["p90"], 100.0 * delay["end_share"], delay["chars"]))
+      print("\tCommit delay (chunks of %d frames): mean %.2f frames, p90 %d, %.1f%% of %d characters only at the end%s"
+            % (f["stream_chunk"], delay["mean"], delay["p90"], 100.0 * delay["end_share"], delay["chars"], streamed))
     else:
-      print("\tCommit delay (chunks of %d frames): no characters decoded" % f["stream_chunk"])
+      print("\tCommit delay (chunks of %d frames): no characters decoded%s" % (f["stream_chunk"], streamed))
     return cer, delay
   mwer = None
   if f["mwer"]:

@@ -485,6 +485,12 @@ class VideoEncoder(nn.Module):
       return output_log_probs, hidden_states, final_state
     return hidden_states, final_state
 
+  def stream(self, batch, device):
+    """An encoder_stream.EncoderStream: this (uni-directional) encoder over `batch` utterance slots fed chunk by
+    chunk, the recurrent state carried on the device."""
+    from .encoder_stream import EncoderStream
+    return EncoderStream(self, batch, device)
+
   def save_best_model(self, error, file_path):
     """better_model.py:114-122."""
     if error < self.best_error:
