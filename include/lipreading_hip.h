@@ -551,6 +551,62 @@ int lr_rnn_stream_advance(int mode, const float* x, int64_t stride_b, int64_t st
 int lr_rnn_stream_read(const void* state, size_t state_bytes, float* h, float* c, int32_t* frames, int32_t* status,
                        int B, int H, int layers, lr_stream_t stream);
 
+/* ---- A3 look-ahead sessions (BUILD-DEFINED, no reference symbol): the BIDIRECTIONAL stack fed chunk by chunk ----- */
+/* A latency-controlled bidirectional GRU / LSTM / tanh RNN (lipreading_amd/csrc/lr_rnn_bistream.hip).
+ * One advance hands slot b a window of window_T frames: it CONSUMES the first n_b = clamp(sizes[b], 0, chunk_T) and SEES
+ * a_b = clamp(ahead[b], 0, window_T - n_b) more; e_b = n_b + a_b.  In every layer the forward direction starts from the
+ * slot's carried state and runs over frames 0 .. e_b - 1, the state committed being the one after frame n_b - 1; the
+ * backward direction starts from ZERO at frame e_b - 1, runs down to frame 0 and carries nothing to the next advance.
+ * An upper layer's input is [fwd | bwd] of the same frame (torch's order).  Only consumed frames are returned.  With
+ * ahead = all a slot has left at every advance, outputs and state are bit for bit the single advance over the whole
+ * utterance, which is the one-shot bidirectional model.  mode is a plain cell; a flagged mode is rejected.
+ * With G = 3 / 4 / 1 gates, HT = ceil(H / 16), Hp = 16 HT, a256(n) = n rounded up to a multiple of 256:
+ *   pack      per layer l and direction (forward, then backward), with IC_l = ceil(I / 16) for l = 0 and 2 HT above
+ *             (each direction's half padded on its own): a256(4 * HT * (IC_l + HT) * G * 256) bytes of [W_ih | W_hh]
+ *             fragments, then a256(4 * layers * 2 * 4 * Hp) bytes of biases (b_ih + b_hh per gate; the GRU's b_in and
+ *             b_hn apart)
+ *   state     a256(32 * B) bytes of slot headers (int32: magic — not the causal session's —, B, H, layers, cell, frames
+ *             consumed — saturating —, status bits, 0), then the FORWARD h [layers][B][Hp] in
+ *             a256(4 * layers * B * Hp) bytes, then (LSTM) the forward c likewise
+ *   workspace a256(4 * layers * 2 * max(window_T, 1) * B * Hp) bytes of per-frame planes, then (LSTM)
+ *             a256(4 * layers * 2 * B * Hp) + a256(4 * layers * B * Hp)
+ * Limits: layers <= 16, C <= 256, chunk_T <= window_T <= 2^20, B <= 16 * 65535 (else 0 bytes / LR_ERR_UNSUPPORTED).
+ * Buffers smaller than their *_bytes answer LR_ERR_WORKSPACE, NULLs, negative sizes and window_T < chunk_T
+ * LR_ERR_INVALID_ARG, before any launch.  state, pack and workspace must be 16-byte aligned.  A causal session's state
+ * (lr_rnn_stream_*) handed to these entry points gets LR_RNN_STREAM_MISMATCH and keeps its bytes, and the other way
+ * round. */
+size_t lr_rnn_bistream_pack_bytes(int mode, int I, int H, int layers);            /* 0 for arguments it rejects */
+/* w_ih / w_hh / b_ih / b_hh: host arrays of 2 * layers device pointers, [2 l] the forward (`*_l{l}`) and [2 l + 1] the
+ * backward (`*_l{l}_reverse`) direction, torch.nn layouts (W_ih of an upper layer [G H][2 H]); any I >= 1, H >= 1, no
+ * alignment asked of the tensors.  Made once per weight set. */
+int lr_rnn_bistream_pack(void* out, size_t out_bytes, int mode, const float* const* w_ih, const float* const* w_hh,
+                         const float* const* b_ih, const float* const* b_hh, int I, int H, int layers,
+                         lr_stream_t stream);
+size_t lr_rnn_bistream_state_bytes(int mode, int B, int H, int layers);           /* 0 for arguments it rejects */
+size_t lr_rnn_bistream_workspace_bytes(int mode, int B, int chunk_T, int window_T, int I, int H, int layers,
+                                       int C);                                    /* C = 0: no head; 0 if rejected */
+
+/* As lr_rnn_stream_reset, on a look-ahead session's state. */
+int lr_rnn_bistream_reset(void* state, size_t state_bytes, const int32_t* mask, int mode, int B, int H, int layers,
+                          lr_stream_t stream);
+
+/* One advance (above).  x[b] frame t at x + b * stride_b + t * stride_t, I floats of unit stride, readable for
+ * t < e_b; sizes NULL = chunk_T, ahead NULL = 0 (both [B] int32 on the device).  layers * window_T step launches (both
+ * directions in each), one head launch if head_w [C][2 H] / head_b / head_mask are given (all three or none; with them
+ * log_probs [B][chunk_T][C], without them log_probs NULL), one commit launch.  y [B][chunk_T][2 H] (may be NULL) is the
+ * last layer's [fwd | bwd], zero at t >= n_b; log_probs there is the head of the zero row.  A slot with n_b == 0 keeps
+ * every bit of its state and its frame count, whatever ahead[b] is.  A slot whose header disagrees with B, H, layers or
+ * the cell is left alone and gets LR_RNN_STREAM_MISMATCH, which stays until a reset.  chunk_T == 0 does nothing. */
+int lr_rnn_bistream_advance(int mode, const float* x, int64_t stride_b, int64_t stride_t, const int32_t* sizes,
+                            const int32_t* ahead, const void* pack, size_t pack_bytes, const float* head_w,
+                            const float* head_b, const float* head_mask, float* y, float* log_probs, void* state,
+                            size_t state_bytes, void* workspace, size_t workspace_bytes, int B, int chunk_T,
+                            int window_T, int I, int H, int layers, int C, lr_stream_t stream);
+
+/* As lr_rnn_stream_read: h / c [layers][B][H] are the FORWARD direction's (the backward direction carries no state). */
+int lr_rnn_bistream_read(const void* state, size_t state_bytes, float* h, float* c, int32_t* frames, int32_t* status,
+                         int B, int H, int layers, lr_stream_t stream);
+
 /* ---- A3 tail: output_proj + masked_log_softmax — better_model.py:92-93 ------------------ */
 
 /* log_probs[r,:] = log_softmax(hidden[r,:] @ W^T + bias + log(mask + 1e-45))

@@ -28,3 +28,14 @@ def _is_a_rank():
 
 if _is_a_rank():
   _os.environ.setdefault("GPU_MAX_HW_QUEUES", "6")
+
+# look-ahead sessions of a bidirectional encoder (encoder_lookahead.py), resolved on first use so that
+# importing the package stays as light as it was
+_LOOKAHEAD = ("LookaheadEncoderStream", "ChunkedLookaheadEncoder", "LookaheadTranscriber")
+
+
+def __getattr__(name):
+  if name in _LOOKAHEAD:
+    from . import encoder_lookahead
+    return getattr(encoder_lookahead, name)
+  raise AttributeError("module %r has no attribute %r" % (__name__, name))

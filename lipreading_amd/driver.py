@@ -55,6 +55,12 @@ DEFAULTS = dict(  # train.py:134-167
     # resumable encoder session (encoder_stream.ChunkedEncoder) — the whole live transcriber, not only
     # its search.  Needs --ctc_decoder=beam, --bidirectional=False, --encoder=rnn and --frontend=none
     stream_encoder=False,
+    # --stream_lookahead=N (-1 = off) with --stream_chunk=M: the evaluation's BIDIRECTIONAL encoder runs chunk by chunk
+    # through a look-ahead session (encoder_lookahead.ChunkedLookaheadEncoder): the forward direction
+    # carries its state, the backward one restarts N frames past every chunk.  CER / WER against N is the model's
+    # accuracy / latency curve.  Needs --ctc_decoder=beam, --enable_ctc=True, --ctc_only=True, --bidirectional=True,
+    # --encoder=rnn and --frontend=none; not together with --stream_encoder
+    stream_lookahead=-1,
     # the error of a model WITH the attention decoder: teacher (the live loop's sampled-token mismatch rate under
     # teacher forcing, train.eval) or beam (the edit-distance CER of the decoder's own beam-search transcript,
     # train.attention_cer, --attn_beam_width hypotheses of up to --attn_max_label_len characters) or joint (the same
@@ -197,6 +203,7 @@ def parse_flags(argv, defaults=DEFAULTS):
   if out.get("stream_chunk") and out.get("ctc_decoder") != "beam":
     raise SystemExit("--stream_chunk needs --ctc_decoder=beam")
   stream_encoder_check(out)
+  stream_lookahead_check(out)
   if out.get("attn_decode") not in ("teacher", "beam", "joint"):
     raise SystemExit("--attn_decode must be teacher, beam or joint")
   if out.get("attn_decode") == "joint" and not out.get("enable_ctc"):
@@ -517,6 +524,28 @@ def stream_encoder_check(f):
     raise SystemExit("--stream_encoder needs --encoder=rnn and --frontend=none")
 
 
+def stream_lookahead_check(f):
+  """--stream_lookahead needs what a look-ahead session can run: SystemExit otherwise."""
+  n = int(-1 if f.get("stream_lookahead") is None else f.get("stream_lookahead"))
+  if n < -1:
+    raise SystemExit("--stream_lookahead must be >= 0 (or -1: off)")
+  if n < 0:
+    return
+  if f.get("stream_encoder"):
+    raise SystemExit("--stream_lookahead does not go with --stream_encoder=True (the causal session): drop one of them")
+  if not int(f.get("stream_chunk") or 0) > 0:
+    raise SystemExit("--stream_lookahead needs --stream_chunk>0 (the chunk the encoder is fed in)")
+  if f.get("ctc_decoder") != "beam":
+    raise SystemExit("--stream_lookahead needs --ctc_decoder=beam")
+  if not f.get("enable_ctc") or not f.get("ctc_only"):
+    raise SystemExit("--stream_lookahead needs the encoder + CTC loop (--enable_ctc=True --ctc_only=True)")
+  if not f.get("bidirectional"):
+    raise SystemExit("--stream_lookahead needs --bidirectional=True (a uni-directional encoder streams with "
+                     "--stream_encoder=True)")
+  if f.get("encoder") != "rnn" or f.get("frontend") != "none":
+    raise SystemExit("--stream_lookahead needs --encoder=rnn and --frontend=none")
+
+
 def _cer(correct, count):
   return float(count - correct) / count if count else 1.0
 
@@ -585,6 +614,7 @@ def run(**flags):
   segment_check(f)
   mwer_check(f)
   stream_encoder_check(f)
+  stream_lookahead_check(f)
   torch.manual_seed(f["seed"])
   rand = np.random.RandomState(seed=f["seed"])
   assert torch.cuda.is_available(), "the driver runs the HIP path: an MI355X is required (no CPU fallback)"
@@ -662,6 +692,11 @@ def run(**flags):
       raise SystemExit("--stream_encoder needs the encoder + CTC loop (--enable_ctc=True --ctc_only=True)")
     from .encoder_stream import ChunkedEncoder
     eval_encoder = ChunkedEncoder(encoder, f["stream_chunk"])
+  if f["stream_lookahead"] >= 0:
+    if chunked is None or decoding_step is not None:
+      raise SystemExit("--stream_lookahead needs the encoder + CTC loop (--enable_ctc=True --ctc_only=True)")
+    from .encoder_lookahead import ChunkedLookaheadEncoder
+    eval_encoder = ChunkedLookaheadEncoder(encoder, f["stream_chunk"], f["stream_lookahead"])
   error_of = make_error_of(f, eval_encoder, decoding_step, chunked or ctc_decoder, device, char2idx)
 
   def validation_error():
@@ -672,6 +707,8 @@ def run(**flags):
     cer = error_of(val_loader)
     delay = chunked.commit_delay()
     streamed = " (encoder streamed)" if f["stream_encoder"] else ""
+    if f["stream_lookahead"] >= 0:
+      streamed = " (encoder streamed: adds %d frames of look-ahead latency)" % f["stream_lookahead"]
     if delay["chars"]:
       print("\tCommit delay (chunks of %d frames): mean %.2f frames, p90 %d, %.1f%% of %d characters only at the end%s"
             % (f["stream_chunk"], delay["mean"], delay["p90"], 100.0 * delay["end_share"], delay["chars"], streamed))

@@ -491,6 +491,13 @@ class VideoEncoder(nn.Module):
     from .encoder_stream import EncoderStream
     return EncoderStream(self, batch, device)
 
+  def stream_lookahead(self, batch, device):
+    """An encoder_lookahead.LookaheadEncoderStream: this (bidirectional) encoder over `batch` utterance slots fed
+    window by window, the forward state carried on the device and the backward direction restarted past a bounded
+    look-ahead at every advance."""
+    from .encoder_lookahead import LookaheadEncoderStream
+    return LookaheadEncoderStream(self, batch, device)
+
   def save_best_model(self, error, file_path):
     """better_model.py:114-122."""
     if error < self.best_error:
