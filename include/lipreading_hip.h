@@ -1574,6 +1574,60 @@ int lr_unpool_code_bf16(const void* pooled, const void* code, const void* dP, vo
 int lr_bf16_to_f32(const void* in, float* out, int64_t n, lr_stream_t stream);
 int lr_f32_to_bf16(const float* in, void* out, int64_t n, lr_stream_t stream);
 
+/* ---- A8 sessions (BUILD-DEFINED, no reference symbol): the conv frontend fed chunk by chunk ---------------------- */
+/* A frontend session is one device buffer owned by the caller: for B independent slots the last two input frames of
+ * each of the three convolutions and the slot's counters (lipreading_amd/csrc/lr_conv_stream.hip).
+ * Every layer has KT = 3, pt = 1, so feature frame t depends on clip frames t-3 .. t+3: a session has an inherent
+ * look-ahead of 3 frames.  A slot's features are the one-shot frontend's on that slot's frames ALONE, zero temporal
+ * padding before frame 0 and after the last frame; fed the same frames in any chunks, in any slot of any batch, a
+ * session computes the same bits and leaves the same state bytes.  (The one-shot frontend on a PADDED batch lets the
+ * padding frames reach the last two feature frames of a shorter clip; a session has no padding to see.  The two agree
+ * on unpadded clips.)  Arithmetic as the one-shot path: byte * (1.f/255.f) rounded to bf16, bf16 operands, fp32
+ * accumulation, bias -> bf16 -> ReLU -> 2x2 max-pool on the values that would be stored, bf16 at every level.
+ * With H % 16 == 0, W % 16 == 0, a256(n) = n rounded up to a multiple of 256, plane(h, w, c) = a256(2 * h * w * c):
+ *   state     a256(32 * B) bytes of slot headers (int32: magic, H, W, frames consumed n — saturating —, features
+ *             emitted, ended, status bits, 0), then per slot 2 * (plane(H, W, 4) + plane(H/4, W/4, 32) +
+ *             plane(H/8, W/8, 64)) bytes: a ring of TWO bf16 frames [h][w][c] for the input of layer 1 (the ingested
+ *             clip), of layer 2 (pooled layer-1 output) and of layer 3 (pooled layer-2 output), older frame first
+ *   workspace a256(48 * B) + a256(48 * B * (chunk_T + 3)) bytes of plan, then B * chunk_T * plane(H, W, 4) +
+ *             B * (chunk_T + 1) * plane(H/4, W/4, 32) + B * (chunk_T + 2) * plane(H/8, W/8, 64) bytes of new frames
+ * Limits: 16 <= H, W <= 1024, B * (chunk_T + 3) <= 65535 (else 0 bytes / LR_ERR_UNSUPPORTED).  NULLs, negative sizes,
+ * H % 16 or W % 16, misaligned buffers answer LR_ERR_INVALID_ARG, buffers smaller than their *_bytes LR_ERR_WORKSPACE,
+ * before any launch.  state, workspace and the weight operands must be 16-byte aligned. */
+#define LR_CONV_STREAM_MISMATCH 1  /* a call's H or W is not the slot's */
+#define LR_CONV_STREAM_AFTER_END 2 /* frames were given to a slot whose stream had ended */
+#define LR_CONV_STREAM_F32 1       /* advance flags: x is fp32 (else uint8) */
+
+size_t lr_conv_stream_state_bytes(int B, int H, int W);                     /* 0 for arguments it rejects */
+size_t lr_conv_stream_workspace_bytes(int B, int chunk_T, int H, int W);    /* 0 for arguments it rejects */
+
+/* Slots with mask[b] != 0 (mask [B] int32 on the device; NULL: all) go back to zero rings, 0 frames, not ended and
+ * no status bit; the others keep every bit.  Under a mask the slot must already carry (H, W) (else it is left alone
+ * and gets LR_CONV_STREAM_MISMATCH); with NULL whatever the buffer held is overwritten. */
+int lr_conv_stream_reset(void* state, size_t state_bytes, const int32_t* mask, int B, int H, int W, lr_stream_t stream);
+
+/* Slot b consumes frames [0, clamp(sizes[b], 0, chunk_T)) of x[b] (x + b * stride_b + t * stride_t in elements, then
+ * (3, H, W) contiguous; uint8, or fp32 with LR_CONV_STREAM_F32 in flags; sizes NULL = chunk_T; 0: the slot is idle
+ * and keeps every bit).  end [B] int32 or NULL: non-zero = the slot's stream ends with this call's frames.
+ * w1 / w2 / w3: the layers' bf16 operands [Cout][taps][Cin_pad] of lr_conv3d_pack_weights (dgrad 0), packed once per
+ * weight set; bias1 / bias2 / bias3 fp32.  feat fp32 [B][rows][96 * (H/16) * (W/16)] with rows = chunk_T + (end ? 3 :
+ * 0), (h, w, c) order: the slot's newly completed feature frames packed from row 0, zero rows at and past counts[b].
+ * With E(n, ended) = ended ? n : max(0, n - 3): counts[b] = E(after) - E(before).  chunk_T == 0 without end does
+ * nothing; with end it is a flush.  An ended slot given frames keeps its bytes and gets LR_CONV_STREAM_AFTER_END; a slot
+ * whose header is not (H, W) keeps its bytes and gets LR_CONV_STREAM_MISMATCH; both bits stay until a reset.
+ * One plan launch, one ingest launch, three conv launches, two commit launches. */
+int lr_conv_stream_advance(const void* x, int flags, int64_t stride_b, int64_t stride_t, const int32_t* sizes,
+                           const int32_t* end, const void* w1, const void* w2, const void* w3, const float* bias1,
+                           const float* bias2, const float* bias3, float* feat, int32_t* counts, void* state,
+                           size_t state_bytes, void* workspace, size_t workspace_bytes, int B, int chunk_T, int H, int W,
+                           lr_stream_t stream);
+
+/* frames consumed, features emitted, ended, status, each [B] int32 on the device (each may be NULL, not all): what
+ * the slots hold, without changing a byte of the state.  A slot whose header is not (H, W) reads as zeros with
+ * LR_CONV_STREAM_MISMATCH in status[b]. */
+int lr_conv_stream_read(const void* state, size_t state_bytes, int32_t* frames, int32_t* emitted, int32_t* ended,
+                        int32_t* status, int B, int H, int W, lr_stream_t stream);
+
 /* Inter-layer dropout of nn.GRU / nn.LSTM(dropout = p) in training mode (better_model.py:47-49 hands rnn_dropout to
  * torch; every shipped config sets 0): mask[i] = 0 with probability p, else 1 / (1 - p) (Philox4x32-10, key = seed,
  * counter = i / 4: the same mask for a (seed, n) whatever the launch geometry), y = x * mask (x == y == NULL: only

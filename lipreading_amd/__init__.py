@@ -32,10 +32,15 @@ if _is_a_rank():
 # look-ahead sessions of a bidirectional encoder (encoder_lookahead.py), resolved on first use so that
 # importing the package stays as light as it was
 _LOOKAHEAD = ("LookaheadEncoderStream", "ChunkedLookaheadEncoder", "LookaheadTranscriber")
+# conv frontend sessions (frontend_stream.py), likewise
+_FRONTEND_STREAM = ("FrontendStream", "ChunkedFrontend", "ChunkedPixelLipReader", "PixelLiveTranscriber")
 
 
 def __getattr__(name):
   if name in _LOOKAHEAD:
     from . import encoder_lookahead
     return getattr(encoder_lookahead, name)
+  if name in _FRONTEND_STREAM:
+    from . import frontend_stream
+    return getattr(frontend_stream, name)
   raise AttributeError("module %r has no attribute %r" % (__name__, name))

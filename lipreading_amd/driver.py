@@ -61,6 +61,11 @@ DEFAULTS = dict(  # train.py:134-167
     # accuracy / latency curve.  Needs --ctc_decoder=beam, --enable_ctc=True, --ctc_only=True, --bidirectional=True,
     # --encoder=rnn and --frontend=none; not together with --stream_encoder
     stream_lookahead=-1,
+    # --stream_frontend=True with --frontend=conv3d: the evaluation's conv frontend runs chunk by chunk as well, through
+    # a frontend session (frontend_stream.ChunkedPixelLipReader) in front of the encoder session: the
+    # pixel regime streamed end to end.  Needs --encoder=rnn, --stream_chunk>0 and exactly one of --stream_encoder=True
+    # (with --bidirectional=False) or --stream_lookahead>=0.  The frontend adds 3 frames of latency
+    stream_frontend=False,
     # the error of a model WITH the attention decoder: teacher (the live loop's sampled-token mismatch rate under
     # teacher forcing, train.eval) or beam (the edit-distance CER of the decoder's own beam-search transcript,
     # train.attention_cer, --attn_beam_width hypotheses of up to --attn_max_label_len characters) or joint (the same
@@ -202,6 +207,7 @@ def parse_flags(argv, defaults=DEFAULTS):
     raise SystemExit("--stream_chunk must be >= 0")
   if out.get("stream_chunk") and out.get("ctc_decoder") != "beam":
     raise SystemExit("--stream_chunk needs --ctc_decoder=beam")
+  stream_frontend_check(out)
   stream_encoder_check(out)
   stream_lookahead_check(out)
   if out.get("attn_decode") not in ("teacher", "beam", "joint"):
@@ -520,7 +526,7 @@ def stream_encoder_check(f):
     raise SystemExit("--stream_encoder needs --ctc_decoder=beam")
   if f.get("bidirectional"):
     raise SystemExit("--stream_encoder needs --bidirectional=False: a session runs causally")
-  if f.get("encoder") != "rnn" or f.get("frontend") != "none":
+  if f.get("encoder") != "rnn" or (f.get("frontend") != "none" and not f.get("stream_frontend")):
     raise SystemExit("--stream_encoder needs --encoder=rnn and --frontend=none")
 
 
@@ -542,8 +548,28 @@ def stream_lookahead_check(f):
   if not f.get("bidirectional"):
     raise SystemExit("--stream_lookahead needs --bidirectional=True (a uni-directional encoder streams with "
                      "--stream_encoder=True)")
-  if f.get("encoder") != "rnn" or f.get("frontend") != "none":
+  if f.get("encoder") != "rnn" or (f.get("frontend") != "none" and not f.get("stream_frontend")):
     raise SystemExit("--stream_lookahead needs --encoder=rnn and --frontend=none")
+
+
+def stream_frontend_check(f):
+  """--stream_frontend needs what a frontend session and the encoder session behind it can run: SystemExit otherwise.
+  (With it, --stream_encoder and --stream_lookahead take --frontend=conv3d.)"""
+  if not f.get("stream_frontend"):
+    return
+  if f.get("frontend") != "conv3d":
+    raise SystemExit("--stream_frontend needs --frontend=conv3d (the frontend it streams)")
+  if f.get("encoder") != "rnn":
+    raise SystemExit("--stream_frontend needs --encoder=rnn (there is no session for the transformer encoder)")
+  if not int(f.get("stream_chunk") or 0) > 0:
+    raise SystemExit("--stream_frontend needs --stream_chunk>0 (the chunk the frontend is fed in)")
+  causal = bool(f.get("stream_encoder"))
+  ahead = int(-1 if f.get("stream_lookahead") is None else f.get("stream_lookahead")) >= 0
+  if causal == ahead:
+    raise SystemExit("--stream_frontend needs exactly one of --stream_encoder=True (with --bidirectional=False) or "
+                     "--stream_lookahead>=0: the encoder session its features feed")
+  if causal and f.get("bidirectional"):
+    raise SystemExit("--stream_frontend with --stream_encoder=True needs --bidirectional=False: a session runs causally")
 
 
 def _cer(correct, count):
@@ -613,6 +639,7 @@ def run(**flags):
   spot_check(f)
   segment_check(f)
   mwer_check(f)
+  stream_frontend_check(f)
   stream_encoder_check(f)
   stream_lookahead_check(f)
   torch.manual_seed(f["seed"])
@@ -690,13 +717,19 @@ def run(**flags):
   if f["stream_encoder"]:
     if chunked is None or decoding_step is not None:
       raise SystemExit("--stream_encoder needs the encoder + CTC loop (--enable_ctc=True --ctc_only=True)")
-    from .encoder_stream import ChunkedEncoder
-    eval_encoder = ChunkedEncoder(encoder, f["stream_chunk"])
+    if not f["stream_frontend"]:
+      from .encoder_stream import ChunkedEncoder
+      eval_encoder = ChunkedEncoder(encoder, f["stream_chunk"])
   if f["stream_lookahead"] >= 0:
     if chunked is None or decoding_step is not None:
       raise SystemExit("--stream_lookahead needs the encoder + CTC loop (--enable_ctc=True --ctc_only=True)")
-    from .encoder_lookahead import ChunkedLookaheadEncoder
-    eval_encoder = ChunkedLookaheadEncoder(encoder, f["stream_chunk"], f["stream_lookahead"])
+    if not f["stream_frontend"]:
+      from .encoder_lookahead import ChunkedLookaheadEncoder
+      eval_encoder = ChunkedLookaheadEncoder(encoder, f["stream_chunk"], f["stream_lookahead"])
+  if f["stream_frontend"]:
+    from .frontend_stream import ChunkedPixelLipReader
+    eval_encoder = ChunkedPixelLipReader(encoder, f["stream_chunk"],
+                                         lookahead=f["stream_lookahead"] if f["stream_lookahead"] >= 0 else None)
   error_of = make_error_of(f, eval_encoder, decoding_step, chunked or ctc_decoder, device, char2idx)
 
   def validation_error():
@@ -709,6 +742,8 @@ def run(**flags):
     streamed = " (encoder streamed)" if f["stream_encoder"] else ""
     if f["stream_lookahead"] >= 0:
       streamed = " (encoder streamed: adds %d frames of look-ahead latency)" % f["stream_lookahead"]
+    if f["stream_frontend"]:
+      streamed = streamed[:-1] + "; frontend streamed: adds 3 frames of latency)"
     if delay["chars"]:
       print("\tCommit delay (chunks of %d frames): mean %.2f frames, p90 %d, %.1f%% of %d characters only at the end%s"
             % (f["stream_chunk"], delay["mean"], delay["p90"], 100.0 * delay["end_share"], delay["chars"], streamed))

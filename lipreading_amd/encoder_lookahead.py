@@ -18,14 +18,14 @@ from . import _C, _host
 from .encoder import _MODES, _ptr_array
 
 
-def _check_encoder(encoder):
+def _check_encoder(encoder, any_projection=False):
   """What a look-ahead session cannot run, by the encoder's own attributes: raises before any device work."""
   if getattr(encoder, "rnn", None) is None or getattr(encoder, "rnn_type", None) not in _MODES:
     raise TypeError("encoder must be a recurrent VideoEncoder (GRU / LSTM / RNN), got %s" % type(encoder).__name__)
   if not encoder.bidirectional:
     raise ValueError("encoder is uni-directional: there is nothing to look ahead for; use VideoEncoder.stream "
                      "(encoder_stream.EncoderStream)")
-  if encoder.input_projection != 'f32':
+  if not any_projection and encoder.input_projection != 'f32':
     raise ValueError("encoder.input_projection is %r: a session runs the exact fp32 projection ('f32') only"
                      % (encoder.input_projection,))
 
@@ -36,8 +36,9 @@ class LookaheadEncoderStream(object):
   and change nothing.  The weights are packed once, here: call refresh() after they change.  Use
   VideoEncoder.stream_lookahead()."""
 
-  def __init__(self, encoder, batch, device):
-    _check_encoder(encoder)
+  def __init__(self, encoder, batch, device, any_projection=False):
+    _check_encoder(encoder, any_projection)
+    self.any_projection = bool(any_projection)
     device = torch.device(device)
     if device.type != "cuda":
       raise _C.LipReadingHipError("lipreading_amd ops run on the MI355X only; got device %s (no CPU fallback)" % device)
@@ -177,8 +178,9 @@ class ChunkedLookaheadEncoder(object):
   (None in its place; need_final_state=True raises), so train.ctc_cer and the other evaluation loops, which pass
   need_final_state=False, take it in the encoder's place.  lookahead >= the longest utterance is the one-shot model."""
 
-  def __init__(self, encoder, chunk, lookahead):
-    _check_encoder(encoder)
+  def __init__(self, encoder, chunk, lookahead, any_projection=False):
+    _check_encoder(encoder, any_projection)
+    self.any_projection = bool(any_projection)
     if int(chunk) < 1:
       raise ValueError("chunk must be >= 1, got %d" % chunk)
     if int(lookahead) < 0:
@@ -201,7 +203,7 @@ class ChunkedLookaheadEncoder(object):
     key = (B, _host.device_key(dev))
     st = self._streams.get(key)
     if st is None:
-      st = self._streams[key] = LookaheadEncoderStream(self.encoder, B, dev)
+      st = self._streams[key] = LookaheadEncoderStream(self.encoder, B, dev, self.any_projection)
     else:
       st.refresh().reset()
     lens = _host.int32_vector(frame_lens, B, "frame_lens", device=st.device)

@@ -15,13 +15,13 @@ from . import _C, _host
 from .encoder import _MODES, _ptr_array
 
 
-def _check_encoder(encoder):
+def _check_encoder(encoder, any_projection=False):
   """What a session cannot run, by the encoder's own attributes: raises before any device work."""
   if getattr(encoder, "rnn", None) is None or getattr(encoder, "rnn_type", None) not in _MODES:
     raise TypeError("encoder must be a recurrent VideoEncoder (GRU / LSTM / RNN), got %s" % type(encoder).__name__)
   if encoder.bidirectional:
     raise ValueError("encoder is bidirectional: a session runs causally, which needs bidirectional=False")
-  if encoder.input_projection != 'f32':
+  if not any_projection and encoder.input_projection != 'f32':
     raise ValueError("encoder.input_projection is %r: a session runs the exact fp32 projection ('f32') only"
                      % (encoder.input_projection,))
 
@@ -31,8 +31,9 @@ class EncoderStream(object):
   launch and one commit launch on the current stream; state() / frames() are one launch and change nothing.  The
   weights are packed once, here: call refresh() after they change.  Use VideoEncoder.stream()."""
 
-  def __init__(self, encoder, batch, device):
-    _check_encoder(encoder)
+  def __init__(self, encoder, batch, device, any_projection=False):
+    _check_encoder(encoder, any_projection)
+    self.any_projection = bool(any_projection)
     device = torch.device(device)
     if device.type != "cuda":
       raise _C.LipReadingHipError("lipreading_amd ops run on the MI355X only; got device %s (no CPU fallback)" % device)
@@ -171,8 +172,9 @@ class ChunkedEncoder(object):
   and returns, so train.ctc_cer and the other evaluation loops take it in the encoder's place.  Everything else
   (eval(), recurrence, enable_ctc ...) is the encoder's."""
 
-  def __init__(self, encoder, chunk):
-    _check_encoder(encoder)
+  def __init__(self, encoder, chunk, any_projection=False):
+    _check_encoder(encoder, any_projection)
+    self.any_projection = bool(any_projection)
     if int(chunk) < 1:
       raise ValueError("chunk must be >= 1, got %d" % chunk)
     self.encoder, self.chunk = encoder, int(chunk)
@@ -190,7 +192,7 @@ class ChunkedEncoder(object):
     key = (B, _host.device_key(dev))
     st = self._streams.get(key)
     if st is None:
-      st = self._streams[key] = EncoderStream(self.encoder, B, dev)
+      st = self._streams[key] = EncoderStream(self.encoder, B, dev, self.any_projection)
     else:
       st.refresh().reset()
     lens = _host.int32_vector(frame_lens, B, "frame_lens", device=st.device)

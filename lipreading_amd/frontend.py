@@ -284,6 +284,12 @@ class ConvFrontend3D(nn.Module):
     assert clips.dim() == 5 and clips.shape[2] == 3, "clips must be (B, T, 3, H, W)"
     return _ConvFrontendFunction.apply(clips, bool(out_bf16), *self.parameters_in_order())
 
+  def stream(self, batch, height, width, device):
+    """A frontend_stream.FrontendStream: this frontend over `batch` clip slots of height x width fed chunk by chunk,
+    the last two input frames of every layer carried on the device."""
+    from .frontend_stream import FrontendStream
+    return FrontendStream(self, batch, height, width, device)
+
 
 class PixelLipReader(nn.Module):
   """frontend + VideoEncoder: the (B,75,3,96,96) regime of BASELINE.json (build-defined)."""
