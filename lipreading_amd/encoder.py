@@ -289,6 +289,9 @@ class _ProjLogSoftmaxFunction(torch.autograd.Function):
     B, T, K = hidden.shape
     C = weight.shape[0]
     R = B * T
+    # the kernels take dense row-major (R, K) / (C, K) / (C,) operands: a sliced or transposed view is copied first,
+    # and the copy is what the backward reads
+    hidden, weight, bias, mask = hidden.contiguous(), weight.contiguous(), bias.contiguous(), mask.contiguous()
     lp = torch.empty((B, T, C), dtype=torch.float32, device=hidden.device)
     wbytes = L.lr_proj_workspace_bytes(R, K, C)
     ws = torch.empty(wbytes, dtype=torch.uint8, device=hidden.device)
@@ -308,9 +311,9 @@ class _ProjLogSoftmaxFunction(torch.autograd.Function):
     dev = hidden.device
     g = g.contiguous()
     dlogits = torch.empty((R, C), dtype=torch.float32, device=dev)
-    dhidden = torch.empty_like(hidden) if ctx.needs_input_grad[0] else None
+    dhidden = torch.empty((B, T, K), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
     direct = _direct_grads((weight, bias))
-    dW = weight.grad if direct else torch.empty_like(weight)
+    dW = weight.grad if direct else torch.empty((C, K), dtype=torch.float32, device=dev)
     db = bias.grad if direct else torch.empty((C,), dtype=torch.float32, device=dev)
     wbytes = L.lr_proj_workspace_bytes(R, K, C)
     ws = torch.empty(wbytes, dtype=torch.uint8, device=dev)
