@@ -849,6 +849,16 @@ int lr_attn_softmax_forward(float* scores, const int32_t* key_lens, float scale,
                             lr_stream_t stream);
 int lr_attn_softmax_backward(const float* probs, float* dprobs, float scale, int B, int Hh, int T,
                              lr_stream_t stream);
+/* Chunk-limited attention (BUILD-DEFINED): the same softmax under the chunk mask a streaming model is
+ * trained with.  chunk = C >= 1, left_chunks = Lc >= 0: query q of a sample of len = clamp(key_lens[b], 1, T) frames
+ * sits in chunk c = q / C and attends to key k iff  max(0, c - Lc) * C <= k < min(len, (c + 1) * C)  — its own chunk to
+ * the end and Lc whole chunks before it; the look-ahead is at most C - 1 frames whatever the depth of the stack.  A
+ * query with no key (only a padded one, q >= len) gets probability 0 everywhere and a zero context row: finite on every
+ * path.  chunk = 0 is lr_attn_softmax_forward (the same bits).  Masked keys have probability exactly 0, so
+ * lr_attn_softmax_backward serves both.  Negative chunk / left_chunks: LR_ERR_INVALID_ARG before any launch.  The
+ * lr_attn_fused_*_chunked and lr_tfm_*_chunked entry points below take the same two integers the same way. */
+int lr_attn_softmax_forward_chunked(float* scores, const int32_t* key_lens, float scale, int B, int Hh, int T, int chunk,
+                                    int left_chunks, lr_stream_t stream);
 /* Fused self-attention core on the bf16 matrix cores (lr_attention.hip): per (sample, head)
  * out = softmax_keys(scale * Q K^T, keys >= key_lens[b] masked) V, with Q / K / V read in place from the fused
  * projection qkv [B][T][3*nhead*dh] (head h at columns h*dh of each third), out [B][T][nhead*dh]; backward:
@@ -861,6 +871,12 @@ int lr_attn_fused_forward(const float* qkv, const int32_t* key_lens, float* out,
                           int nhead, int dh, lr_stream_t stream);
 int lr_attn_fused_backward(const float* qkv, const int32_t* key_lens, const float* dout, float* dqkv, float scale,
                            int B, int T, int nhead, int dh, lr_stream_t stream);
+/* the fused core under the chunk mask of lr_attn_softmax_forward_chunked (the backward recomputes the probabilities, so
+ * it takes the same chunk / left_chunks as the forward it differentiates); chunk = 0: the two above */
+int lr_attn_fused_forward_chunked(const float* qkv, const int32_t* key_lens, float* out, float scale, int B, int T,
+                                  int nhead, int dh, int chunk, int left_chunks, lr_stream_t stream);
+int lr_attn_fused_backward_chunked(const float* qkv, const int32_t* key_lens, const float* dout, float* dqkv, float scale,
+                                   int B, int T, int nhead, int dh, int chunk, int left_chunks, lr_stream_t stream);
 /* Products straight from the tensors as they lie in memory (lr_fgemm.hip; BUILD-DEFINED, no reference symbol):
  *   C[M][N] = epilogue(sum_k op(A)[m][k] op(B)[k][n]),  form NT: A [M][K], B [N][K];  NN: A [M][K], B [K][N];
  *   TN: A [K][M], B [K][N].  prec LR_FGEMM_X3: fp32 operands split into bf16 hi + lo on the way into LDS, three
@@ -933,6 +949,76 @@ int lr_tfm_backward_data(int mode, const int32_t* key_lens, const float* const* 
 int lr_tfm_backward_weights(int mode, const void* x, float* const* grads, int accumulate, void* reserve,
                             size_t reserve_bytes, void* workspace, size_t workspace_bytes, int B, int T, int I, int Dm,
                             int nhead, int F, int nlayers, lr_stream_t stream);
+/* the stack with every layer's self-attention under the chunk mask of lr_attn_softmax_forward_chunked (training and
+ * one-shot inference of a model that is to stream); the same reserve / workspace sizes, and lr_tfm_backward_weights
+ * as it is (attention has no weights).  backward_data must be given the forward's chunk / left_chunks.  chunk = 0: the
+ * two entry points above, bit for bit. */
+int lr_tfm_forward_chunked(int mode, const void* x, const int32_t* key_lens, const float* const* weights, const float* pe,
+                           float* h_out, void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes, int B,
+                           int T, int I, int Dm, int nhead, int F, int nlayers, float eps, int chunk, int left_chunks,
+                           lr_stream_t stream);
+int lr_tfm_backward_data_chunked(int mode, const int32_t* key_lens, const float* const* weights, const float* dh_out,
+                                 void* dx, void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
+                                 int B, int T, int I, int Dm, int nhead, int F, int nlayers, int chunk, int left_chunks,
+                                 lr_stream_t stream);
+
+/* ---- A10 sessions (BUILD-DEFINED, no reference symbol): the chunk-limited encoder stack fed chunk by chunk -------- */
+/* A transformer session is one device buffer owned by the caller: for B independent slots the input frames of the
+ * attention chunk that is not whole yet and, per layer, the keys and values of the last left_chunks * chunk positions
+ * (lipreading_amd/csrc/lr_tfm_stream.hip).  It computes, chunk by chunk, what lr_tfm_forward_chunked
+ * (mode 0: exact fp32 products, fp32 softmax) computes on the whole clip with key_lens = the frames fed: a chunk's rows
+ * are emitted once its last frame is in, or when the stream ends.  Fed the same frames in any pieces, in any slot of any
+ * batch, whatever the other slots do, a slot computes the same bits and leaves the same state bytes.  Inference only.
+ * With C = chunk, Lc = left_chunks, a256(n) = n rounded up to a multiple of 256:
+ *   state     B slots of a256(64 + a16(4 * (C - 1) * I) + 4 * nlayers * Lc * C * 2 * Dm) bytes each: 16 int32 of header
+ *             (magic, I, Dm, nhead, F, nlayers, C, Lc, frames consumed n, rows emitted, ended, status bits, 0 ...), the
+ *             PENDING frames [C - 1][I] fp32 (frames E(n) .. n - 1 from row 0, zeros behind them), then per layer a RING
+ *             [Lc * C][2 * Dm] fp32 of keys | values, position p at index p % (Lc * C)
+ *   workspace rows of this advance, R = B * (chunk_T + C - 1): the gathered input [R][I], positional rows, two [R][Dm]
+ *             activations, [nlayers][R][3 Dm] projections, one layer's intermediates, logits [R][Cv]
+ * Limits (else 0 bytes / LR_ERR_UNSUPPORTED): 1 <= C <= 32, (Lc + 1) * C <= 128, head dimension a multiple of 4 and
+ * <= 64, what lr_tfm_reserve_bytes(0, ...) accepts, B <= 65535, chunk_T <= 65536, Cv <= 4096, R <= 2^20 - 16.
+ * NULLs, negative sizes and misaligned buffers answer LR_ERR_INVALID_ARG, buffers smaller than their *_bytes
+ * LR_ERR_WORKSPACE, before any launch: nothing is written.  state and workspace must be 16-byte aligned. */
+#define LR_TFM_STREAM_MISMATCH 1   /* a call's configuration is not the slot's */
+#define LR_TFM_STREAM_AFTER_END 2  /* frames were given to a slot whose stream had ended */
+#define LR_TFM_STREAM_FULL 4       /* the slot's frames would pass pe_rows */
+
+size_t lr_tfm_stream_state_bytes(int B, int I, int Dm, int nhead, int F, int nlayers, int chunk,
+                                 int left_chunks);                                    /* 0 for arguments it rejects */
+size_t lr_tfm_stream_workspace_bytes(int B, int chunk_T, int I, int Dm, int nhead, int F, int nlayers, int Cv, int chunk,
+                                     int left_chunks);                                /* 0 for arguments it rejects */
+
+/* Slots with mask[b] != 0 (mask [B] int32 on the device; NULL: all) get the header of this configuration, no pending
+ * frame, zero rings, 0 frames, not ended and no status bit, whatever they held; the others keep every bit. */
+int lr_tfm_stream_reset(void* state, size_t state_bytes, const int32_t* mask, int B, int I, int Dm, int nhead, int F,
+                        int nlayers, int chunk, int left_chunks, lr_stream_t stream);
+
+/* Slot b consumes frames [0, clamp(sizes[b], 0, chunk_T)) of x[b] (x + b * stride_b + t * stride_t in floats, I
+ * contiguous floats; sizes NULL = chunk_T; 0 without end: the slot is idle and keeps every bit).  end [B] int32 or NULL:
+ * non-zero = the slot's stream ends with this call's frames (chunk_T == 0, x NULL: a flush).  weights / pe / eps as
+ * lr_tfm_forward (host array of 2 + 12 * nlayers device pointers); the frame at absolute position t takes pe[t], and a
+ * slot holds at most pe_rows frames.  head_w [Cv][Dm], head_b, head_mask [Cv] (all three or none; none: log_probs NULL).
+ * With E(n, ended) = ended ? n : (n / C) * C the slot emits counts[b] = E(after) - E(before) rows, packed from row 0 of
+ * h_out [B][rows][Dm] (may be NULL) and log_probs [B][rows][Cv], rows = chunk_T + C - 1; at and past counts[b] h_out
+ * holds zeros and log_probs the head of the zero row.  An advance may complete several chunks of a slot.  A slot whose
+ * header is not this configuration keeps its bytes and gets LR_TFM_STREAM_MISMATCH, an ended slot given frames
+ * LR_TFM_STREAM_AFTER_END, one whose frames would pass pe_rows LR_TFM_STREAM_FULL (counts[b] = 0; only the status word
+ * changes, and the bit stays until a reset).  Launches: 1 gather, 1 input projection, 7 per layer (QKV, cached
+ * attention, out-projection, LN1, two feed-forward products, LN2), 2 for the head, 1 commit. */
+int lr_tfm_stream_advance(const float* x, int64_t stride_b, int64_t stride_t, const int32_t* sizes, const int32_t* end,
+                          const float* const* weights, const float* pe, int pe_rows, const float* head_w,
+                          const float* head_b, const float* head_mask, float* h_out, float* log_probs, int32_t* counts,
+                          void* state, size_t state_bytes, void* workspace, size_t workspace_bytes, int B, int chunk_T,
+                          int I, int Dm, int nhead, int F, int nlayers, int Cv, int chunk, int left_chunks, float eps,
+                          lr_stream_t stream);
+
+/* frames consumed, rows emitted, ended, status, each [B] int32 on the device (each may be NULL, not all): what the
+ * slots hold, without changing a byte of the state.  A slot whose header is not this configuration reads as zeros with
+ * LR_TFM_STREAM_MISMATCH in status[b]. */
+int lr_tfm_stream_read(const void* state, size_t state_bytes, int32_t* frames, int32_t* emitted, int32_t* ended,
+                       int32_t* status, int B, int I, int Dm, int nhead, int F, int nlayers, int chunk, int left_chunks,
+                       lr_stream_t stream);
 
 /* ---- A4: CTC loss — src/train/ctc_loss.py:28-114 ---------------------------------------- */
 

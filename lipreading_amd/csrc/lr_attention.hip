@@ -75,19 +75,22 @@ __device__ __forceinline__ void stage(const float* __restrict__ src, int ld, int
 }
 
 // softmax over the keys of one query from transposed score tiles: s[kt][r] = score of key 32 kt + crow(r, h); the other
-// 48 keys of the query sit in lane ^ 32.  Returns probabilities in place.
-__device__ __forceinline__ void softmax_keys(f32x16 (&s)[3], int h, int len, float scale) {
+// 48 keys of the query sit in lane ^ 32.  Keys outside the query's window [lo, hi) are masked (lr_attn_window; an empty
+// window gives a zero row).  Returns probabilities in place.
+// CHUNKED = false: lo is 0 at compile time — the code of the plain key-length mask, instruction for instruction.
+template <bool CHUNKED>
+__device__ __forceinline__ void softmax_keys(f32x16 (&s)[3], int h, int lo, int hi, float scale) {
   float m = LR_NEG_INF;
 #pragma unroll
   for (int kt = 0; kt < 3; ++kt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int key = 32 * kt + crow(r, h);
-      s[kt][r] = key < len ? s[kt][r] * scale : LR_NEG_INF;
+      s[kt][r] = ((!CHUNKED || key >= lo) && key < hi) ? s[kt][r] * scale : LR_NEG_INF;
       m = fmaxf(m, s[kt][r]);
     }
   m = fmaxf(m, __shfl_xor(m, 32, 64));
-  if (m == LR_NEG_INF) m = 0.f;     // (no valid key: cannot happen, the callers clamp len to >= 1; kept so that it stays finite)
+  if (m == LR_NEG_INF) m = 0.f;     // (no valid key: a padded query under the chunk mask; exp(-inf) = 0 below, a zero row)
   float sum = 0.f;
 #pragma unroll
   for (int kt = 0; kt < 3; ++kt)
@@ -105,10 +108,11 @@ __device__ __forceinline__ void softmax_keys(f32x16 (&s)[3], int h, int len, flo
 }
 
 // ---- forward: grid (nhead, B), 256 threads -----------------------------------------------------------------
+template <bool CHUNKED>
 __global__ __launch_bounds__(256) void attn_fused_fwd_kernel(const float* __restrict__ qkv,
                                                              const int32_t* __restrict__ key_lens,
                                                              float* __restrict__ out, float scale, int T, int nhead,
-                                                             int dh) {
+                                                             int dh, int chunk, int left_chunks) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   bf16_t* Qs = reinterpret_cast<bf16_t*>(smem);          // [TP][LDD]
   bf16_t* Ks = Qs + TP * LDD;                            // [TP][LDD]
@@ -123,6 +127,8 @@ __global__ __launch_bounds__(256) void attn_fused_fwd_kernel(const float* __rest
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 31, h = lane >> 5;
   const int len = min(max(key_lens[b], 1), T);   // a sample of length 0 attends to key 0, as lr_attn_softmax_forward has it
+  int lo = 0, hi = len;                          // the window of this lane's query 32 wave + lr
+  if (CHUNKED) lr_attn_window(32 * wave + lr, len, chunk, left_chunks, lo, hi);
   if (wave < 3) {     // query tile `wave`: all three key tiles, so a query's 96 scores sit in two lanes
     f32x16 s[3];
 #pragma unroll
@@ -131,7 +137,7 @@ __global__ __launch_bounds__(256) void attn_fused_fwd_kernel(const float* __rest
       for (int r = 0; r < 16; ++r) s[kt][r] = 0.f;
       tile_nt(Ks, LDD, Qs, LDD, 32 * kt, 32 * wave, dh / 16, s[kt]);
     }
-    softmax_keys(s, h, len, scale);
+    softmax_keys<CHUNKED>(s, h, lo, hi, scale);
     bf16_t* prow = Ps + (32 * wave + lr) * LDT;
 #pragma unroll
     for (int kt = 0; kt < 3; ++kt)
@@ -161,10 +167,12 @@ __global__ __launch_bounds__(256) void attn_fused_fwd_kernel(const float* __rest
 }
 
 // ---- backward: grid (nhead, B), 256 threads ----------------------------------------------------------------
+template <bool CHUNKED>
 __global__ __launch_bounds__(256) void attn_fused_bwd_kernel(const float* __restrict__ qkv,
                                                              const int32_t* __restrict__ key_lens,
                                                              const float* __restrict__ dout, float* __restrict__ dqkv,
-                                                             float scale, int T, int nhead, int dh) {
+                                                             float scale, int T, int nhead, int dh, int chunk,
+                                                             int left_chunks) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   bf16_t* Qs = reinterpret_cast<bf16_t*>(smem);          // [TP][LDD]
   bf16_t* Ks = Qs + TP * LDD;                            // [TP][LDD]
@@ -186,6 +194,8 @@ __global__ __launch_bounds__(256) void attn_fused_bwd_kernel(const float* __rest
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 31, h = lane >> 5;
   const int len = min(max(key_lens[b], 1), T);   // a sample of length 0 attends to key 0, as lr_attn_softmax_forward has it
+  int lo = 0, hi = len;                          // the window of this lane's query 32 wave + lr
+  if (CHUNKED) lr_attn_window(32 * wave + lr, len, chunk, left_chunks, lo, hi);
   f32x16 p[3], dp[3];
   if (wave < 3) {
 #pragma unroll
@@ -195,7 +205,7 @@ __global__ __launch_bounds__(256) void attn_fused_bwd_kernel(const float* __rest
       tile_nt(Ks, LDD, Qs, LDD, 32 * kt, 32 * wave, dh / 16, p[kt]);      // S^T
       tile_nt(Vs, LDD, dOs, LDD, 32 * kt, 32 * wave, dh / 16, dp[kt]);    // dP^T
     }
-    softmax_keys(p, h, len, scale);
+    softmax_keys<CHUNKED>(p, h, lo, hi, scale);
     // dS = P o (dP - sum_keys P o dP) * scale   (softmax backward of scale * S)
     float delta = 0.f;
 #pragma unroll
@@ -257,35 +267,58 @@ static_assert(2 * TP * LDD >= TP * LDT, "dS must fit the V + dO staging area");
 
 extern "C" int lr_attn_fused_supported(int T, int dh) { return T >= 1 && T <= TP && (dh == 32 || dh == 64) ? 1 : 0; }
 
-extern "C" int lr_attn_fused_forward(const float* qkv, const int32_t* key_lens, float* out, float scale, int B, int T,
-                                     int nhead, int dh, lr_stream_t stream) {
-  LR_CHECK_ARG(qkv && key_lens && out && B > 0 && nhead > 0);
+extern "C" int lr_attn_fused_forward_chunked(const float* qkv, const int32_t* key_lens, float* out, float scale, int B,
+                                             int T, int nhead, int dh, int chunk, int left_chunks, lr_stream_t stream) {
+  LR_CHECK_ARG(qkv && key_lens && out && B > 0 && nhead > 0 && chunk >= 0 && left_chunks >= 0);
   if (!lr_attn_fused_supported(T, dh)) return LR_ERR_UNSUPPORTED;
   static bool attr_set = false;
   lr_clear_error();
   if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)attn_fused_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute((const void*)attn_fused_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)FWD_LDS) != hipSuccess ||
+        hipFuncSetAttribute((const void*)attn_fused_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)FWD_LDS) != hipSuccess)
       return LR_ERR_LAUNCH;
     attr_set = true;
   }
-  LR_LAUNCH(attn_fused_fwd_kernel, dim3(nhead, B), dim3(256), FWD_LDS, stream, qkv, key_lens, out, scale, T, nhead, dh);
+  // (a chunk or a left context past T is T: the same windows, and the kernel's products stay inside an int)
+  if (chunk > 0)
+    LR_LAUNCH(attn_fused_fwd_kernel<true>, dim3(nhead, B), dim3(256), FWD_LDS, stream, qkv, key_lens, out, scale, T, nhead,
+              dh, min(chunk, TP), min(left_chunks, TP));
+  else
+    LR_LAUNCH(attn_fused_fwd_kernel<false>, dim3(nhead, B), dim3(256), FWD_LDS, stream, qkv, key_lens, out, scale, T, nhead,
+              dh, 0, 0);
   return lr_launch_status();
 }
+extern "C" int lr_attn_fused_forward(const float* qkv, const int32_t* key_lens, float* out, float scale, int B, int T,
+                                     int nhead, int dh, lr_stream_t stream) {
+  return lr_attn_fused_forward_chunked(qkv, key_lens, out, scale, B, T, nhead, dh, 0, 0, stream);
+}
 
-extern "C" int lr_attn_fused_backward(const float* qkv, const int32_t* key_lens, const float* dout, float* dqkv,
-                                      float scale, int B, int T, int nhead, int dh, lr_stream_t stream) {
-  LR_CHECK_ARG(qkv && key_lens && dout && dqkv && B > 0 && nhead > 0);
+extern "C" int lr_attn_fused_backward_chunked(const float* qkv, const int32_t* key_lens, const float* dout, float* dqkv,
+                                              float scale, int B, int T, int nhead, int dh, int chunk, int left_chunks,
+                                              lr_stream_t stream) {
+  LR_CHECK_ARG(qkv && key_lens && dout && dqkv && B > 0 && nhead > 0 && chunk >= 0 && left_chunks >= 0);
   if (!lr_attn_fused_supported(T, dh)) return LR_ERR_UNSUPPORTED;
   static bool attr_set = false;
   lr_clear_error();
   if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)attn_fused_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute((const void*)attn_fused_bwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)BWD_LDS) != hipSuccess ||
+        hipFuncSetAttribute((const void*)attn_fused_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)BWD_LDS) != hipSuccess)
       return LR_ERR_LAUNCH;
     attr_set = true;
   }
-  LR_LAUNCH(attn_fused_bwd_kernel, dim3(nhead, B), dim3(256), BWD_LDS, stream, qkv, key_lens, dout, dqkv, scale, T, nhead,
-            dh);
+  if (chunk > 0)
+    LR_LAUNCH(attn_fused_bwd_kernel<true>, dim3(nhead, B), dim3(256), BWD_LDS, stream, qkv, key_lens, dout, dqkv, scale, T,
+              nhead, dh, min(chunk, TP), min(left_chunks, TP));
+  else
+    LR_LAUNCH(attn_fused_bwd_kernel<false>, dim3(nhead, B), dim3(256), BWD_LDS, stream, qkv, key_lens, dout, dqkv, scale, T,
+              nhead, dh, 0, 0);
   return lr_launch_status();
+}
+extern "C" int lr_attn_fused_backward(const float* qkv, const int32_t* key_lens, const float* dout, float* dqkv,
+                                      float scale, int B, int T, int nhead, int dh, lr_stream_t stream) {
+  return lr_attn_fused_backward_chunked(qkv, key_lens, dout, dqkv, scale, B, T, nhead, dh, 0, 0, stream);
 }

@@ -69,6 +69,19 @@ __device__ __forceinline__ float lr_wave_sum(float v) {
   return v;
 }
 
+// The keys [lo, hi) that query q of a sample of `len` valid frames attends to (include/lipreading_hip.h
+// lr_attn_*_chunked).  chunk 0: every valid key.  chunk C > 0: the query's own chunk c = q / C up to its
+// end and left_chunks whole chunks before it.  hi <= lo: no key at all (only a padded query q >= len).
+__host__ __device__ __forceinline__ void lr_attn_window(int q, int len, int chunk, int left_chunks, int& lo, int& hi) {
+  lo = 0;
+  hi = len;
+  if (chunk > 0) {
+    const int c = q / chunk;
+    lo = (c > left_chunks ? c - left_chunks : 0) * chunk;
+    hi = (c + 1) * chunk < len ? (c + 1) * chunk : len;
+  }
+}
+
 // ---- two-stage deterministic column sums (lr_misc.hip) -----------------------------------------
 // stage 1: partial[rs][col] = sum over the rs-th row slice of x[row][col]   (LR_COLSUM_SPLITS slices)
 // stage 2 (caller specific): out[col] = sum_rs partial[rs][col] in fixed order.

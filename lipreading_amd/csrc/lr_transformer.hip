@@ -87,23 +87,27 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
     partial[(int64_t)blockIdx.x * 2 * D + c] = red[c] + red[2 * D + c] + red[4 * D + c] + red[6 * D + c];
 }
 
-// In-place softmax over the keys of scores [B][Hh][T(query)][T(key)] * scale, keys >= key_lens[b]
-// masked out (probability exactly 0, as an additive -inf mask gives).  One wave per query row.
+// In-place softmax over the keys of scores [B][Hh][T(query)][T(key)] * scale, keys outside the query's window
+// [lo, hi) masked out (probability exactly 0, as an additive -inf mask gives): hi <= len = key_lens[b] clamped, and
+// with chunk > 0 the chunk rule of lr_attn_window (lr_common.h).  An empty window (a padded query) gives a zero row.
+// One wave per query row.
 __global__ __launch_bounds__(256) void attn_softmax_fwd_kernel(float* __restrict__ scores,
                                                                const int32_t* __restrict__ key_lens, float scale,
-                                                               int rows, int Hh, int T) {
+                                                               int rows, int Hh, int T, int chunk, int left_chunks) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows) return;
   const int b = row / (Hh * T);
   const int len = min(max(key_lens[b], 1), T);
+  int lo, hi;
+  lr_attn_window(row % T, len, chunk, left_chunks, lo, hi);
   float* s = scores + (int64_t)row * T;
   float m = LR_NEG_INF;
-  for (int k = lane; k < len; k += 64) m = fmaxf(m, s[k] * scale);
+  for (int k = lo + lane; k < hi; k += 64) m = fmaxf(m, s[k] * scale);
   m = lr_wave_max(m);
   float z = 0.f;
-  for (int k = lane; k < len; k += 64) z += expf(s[k] * scale - m);
+  for (int k = lo + lane; k < hi; k += 64) z += expf(s[k] * scale - m);
   z = lr_wave_sum(z);
-  for (int k = lane; k < T; k += 64) s[k] = k < len ? expf(s[k] * scale - m) / z : 0.f;
+  for (int k = lane; k < T; k += 64) s[k] = (k >= lo && k < hi && z > 0.f) ? expf(s[k] * scale - m) / z : 0.f;
 }
 
 // d scores = scale * P * (dP - sum_k dP P), in place over dP (masked keys have P = 0)
@@ -180,12 +184,18 @@ extern "C" int lr_layernorm_backward(const float* x, const float* residual, cons
   return lr_launch_status();
 }
 
+extern "C" int lr_attn_softmax_forward_chunked(float* scores, const int32_t* key_lens, float scale, int B, int Hh, int T,
+                                               int chunk, int left_chunks, lr_stream_t stream) {
+  LR_CHECK_ARG(scores && key_lens && B > 0 && Hh > 0 && T > 0 && chunk >= 0 && left_chunks >= 0);
+  const int rows = B * Hh * T;
+  // (a chunk or a left context past T is T: the same windows, and the kernel's products stay inside an int)
+  LR_LAUNCH(attn_softmax_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, scores, key_lens, scale, rows, Hh, T,
+            min(chunk, T), min(left_chunks, T));
+  return lr_launch_status();
+}
 extern "C" int lr_attn_softmax_forward(float* scores, const int32_t* key_lens, float scale, int B, int Hh, int T,
                                        lr_stream_t stream) {
-  LR_CHECK_ARG(scores && key_lens && B > 0 && Hh > 0 && T > 0);
-  const int rows = B * Hh * T;
-  LR_LAUNCH(attn_softmax_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, scores, key_lens, scale, rows, Hh, T);
-  return lr_launch_status();
+  return lr_attn_softmax_forward_chunked(scores, key_lens, scale, B, Hh, T, 0, 0, stream);
 }
 
 extern "C" int lr_attn_softmax_backward(const float* probs, float* dprobs, float scale, int B, int Hh, int T,
@@ -278,12 +288,12 @@ bool tfm_dims_ok(int mode, int B, int T, int I, int Dm, int nh, int F, int nl) {
 
 // per (sample, head): P = softmax(scale Q K^T), a = P V on the fp32 matrix cores (probs kept for the backward)
 int attention_f32_forward(const float* qkv, const int32_t* lens, float* probs, float* out, int B, int T, int nh, int dh,
-                          hipStream_t st) {
+                          int chunk, int left_chunks, hipStream_t st) {
   const int D = nh * dh, D3 = 3 * D;
   const float scale = 1.f / sqrtf((float)dh);
   LR_TRY_(lr_sgemm_batched(0, 1, T, T, dh, 1.f, qkv, D3, (int64_t)T * D3, dh, qkv + D, D3, (int64_t)T * D3, dh, 0.f, probs, T,
                            (int64_t)nh * T * T, (int64_t)T * T, B, nh, st));
-  LR_TRY_(lr_attn_softmax_forward(probs, lens, scale, B, nh, T, st));
+  LR_TRY_(lr_attn_softmax_forward_chunked(probs, lens, scale, B, nh, T, chunk, left_chunks, st));
   return lr_sgemm_batched(0, 0, T, dh, T, 1.f, probs, T, (int64_t)nh * T * T, (int64_t)T * T, qkv + 2 * D, D3, (int64_t)T * D3, dh,
                           0.f, out, D, (int64_t)T * D, dh, B, nh, st);
 }
@@ -325,10 +335,11 @@ extern "C" size_t lr_tfm_workspace_bytes(int mode, int B, int T, int I, int Dm, 
   return tfm_ws(mode, B, T, I, Dm, nhead, F, nlayers).total * sizeof(float);
 }
 
-extern "C" int lr_tfm_forward(int mode, const void* x, const int32_t* key_lens, const float* const* weights, const float* pe,
-                              float* h_out, void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
-                              int B, int T, int I, int Dm, int nhead, int F, int nlayers, float eps, lr_stream_t stream_) {
-  LR_CHECK_ARG(tfm_dims_ok(mode, B, T, I, Dm, nhead, F, nlayers));
+extern "C" int lr_tfm_forward_chunked(int mode, const void* x, const int32_t* key_lens, const float* const* weights,
+                                      const float* pe, float* h_out, void* reserve, size_t reserve_bytes, void* workspace,
+                                      size_t workspace_bytes, int B, int T, int I, int Dm, int nhead, int F, int nlayers,
+                                      float eps, int chunk, int left_chunks, lr_stream_t stream_) {
+  LR_CHECK_ARG(tfm_dims_ok(mode, B, T, I, Dm, nhead, F, nlayers) && chunk >= 0 && left_chunks >= 0);
   LR_CHECK_ARG(x && key_lens && weights && pe && h_out && reserve && workspace);
   for (int i = 0; i < 2 + 12 * nlayers; ++i) LR_CHECK_ARG(weights[i]);
   const TfmReserve r = tfm_reserve(mode, B, T, Dm, nhead, F, nlayers);
@@ -361,9 +372,10 @@ extern "C" int lr_tfm_forward(int mode, const void* x, const int32_t* key_lens, 
     if (!(rowblock && l > 0))   // (row blocks: layer l - 1's launch wrote this layer's qkv on its way out)
       LR_TRY_(lr_fgemm_launch(prec, LR_FGEMM_NT, 0, 0, &j, 1, st));
     if (mode & LR_TFM_ATTN_FUSED)
-      LR_TRY_(lr_attn_fused_forward(L + r.qkv, key_lens, L + r.a, 1.f / sqrtf((float)dh), B, T, nhead, dh, st));
+      LR_TRY_(lr_attn_fused_forward_chunked(L + r.qkv, key_lens, L + r.a, 1.f / sqrtf((float)dh), B, T, nhead, dh, chunk,
+                                            left_chunks, st));
     else
-      LR_TRY_(attention_f32_forward(L + r.qkv, key_lens, L + r.probs, L + r.a, B, T, nhead, dh, st));
+      LR_TRY_(attention_f32_forward(L + r.qkv, key_lens, L + r.probs, L + r.a, B, T, nhead, dh, chunk, left_chunks, st));
     if (rowblock) {   // out-projection .. LN2 in one launch (lr_tfm_rowblock.hip)
       const bool more = l + 1 < nlayers;   // the next layer's qkv = h2 W_qkv'^T + b' rides at the end of the chain
       LR_TRY_(lr_tfm_rb_forward(base + r.planes, l, W, L + r.a, h, L + r.s1, L + r.st1, L + r.h1, L + r.f1, L + r.s2,
@@ -391,10 +403,18 @@ extern "C" int lr_tfm_forward(int mode, const void* x, const int32_t* key_lens, 
   return LR_OK;
 }
 
-extern "C" int lr_tfm_backward_data(int mode, const int32_t* key_lens, const float* const* weights, const float* dh_out,
-                                    void* dx, void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
-                                    int B, int T, int I, int Dm, int nhead, int F, int nlayers, lr_stream_t stream_) {
-  LR_CHECK_ARG(tfm_dims_ok(mode, B, T, I, Dm, nhead, F, nlayers));
+extern "C" int lr_tfm_forward(int mode, const void* x, const int32_t* key_lens, const float* const* weights, const float* pe,
+                              float* h_out, void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
+                              int B, int T, int I, int Dm, int nhead, int F, int nlayers, float eps, lr_stream_t stream_) {
+  return lr_tfm_forward_chunked(mode, x, key_lens, weights, pe, h_out, reserve, reserve_bytes, workspace, workspace_bytes, B,
+                                T, I, Dm, nhead, F, nlayers, eps, 0, 0, stream_);
+}
+
+extern "C" int lr_tfm_backward_data_chunked(int mode, const int32_t* key_lens, const float* const* weights,
+                                            const float* dh_out, void* dx, void* reserve, size_t reserve_bytes,
+                                            void* workspace, size_t workspace_bytes, int B, int T, int I, int Dm, int nhead,
+                                            int F, int nlayers, int chunk, int left_chunks, lr_stream_t stream_) {
+  LR_CHECK_ARG(tfm_dims_ok(mode, B, T, I, Dm, nhead, F, nlayers) && chunk >= 0 && left_chunks >= 0);
   LR_CHECK_ARG(key_lens && weights && dh_out && reserve && workspace);
   const TfmReserve r = tfm_reserve(mode, B, T, Dm, nhead, F, nlayers);
   const TfmWs w = tfm_ws(mode, B, T, I, Dm, nhead, F, nlayers);
@@ -432,7 +452,8 @@ extern "C" int lr_tfm_backward_data(int mode, const int32_t* key_lens, const flo
       LR_TRY_(lr_fgemm_launch(prec, LR_FGEMM_NN, 0, 0, &j, 1, st));
     }
     if (mode & LR_TFM_ATTN_FUSED)
-      LR_TRY_(lr_attn_fused_backward(L + r.qkv, key_lens, wsb + w.da, G + w.dqkv, 1.f / sqrtf((float)dh), B, T, nhead, dh, st));
+      LR_TRY_(lr_attn_fused_backward_chunked(L + r.qkv, key_lens, wsb + w.da, G + w.dqkv, 1.f / sqrtf((float)dh), B, T, nhead, dh,
+                                             chunk, left_chunks, st));
     else
       LR_TRY_(attention_f32_backward(L + r.qkv, L + r.probs, wsb + w.da, wsb + w.dP, G + w.dqkv, B, T, nhead, dh, st));
     j = fgemm_job(G + w.dqkv, 3 * Dm, W[0], Dm, dh_prev, Dm, R, Dm, 3 * Dm);         // dh = dqkv W_qkv + ds1
@@ -447,6 +468,13 @@ extern "C" int lr_tfm_backward_data(int mode, const int32_t* key_lens, const flo
     LR_TRY_(lr_fgemm_launch(prec, LR_FGEMM_NN, 0, 0, &j, 1, st));
   }
   return LR_OK;
+}
+
+extern "C" int lr_tfm_backward_data(int mode, const int32_t* key_lens, const float* const* weights, const float* dh_out,
+                                    void* dx, void* reserve, size_t reserve_bytes, void* workspace, size_t workspace_bytes,
+                                    int B, int T, int I, int Dm, int nhead, int F, int nlayers, lr_stream_t stream_) {
+  return lr_tfm_backward_data_chunked(mode, key_lens, weights, dh_out, dx, reserve, reserve_bytes, workspace,
+                                      workspace_bytes, B, T, I, Dm, nhead, F, nlayers, 0, 0, stream_);
 }
 
 extern "C" int lr_tfm_backward_weights(int mode, const void* x, float* const* grads, int accumulate, void* reserve,

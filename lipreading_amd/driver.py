@@ -66,6 +66,14 @@ DEFAULTS = dict(  # train.py:134-167
     # pixel regime streamed end to end.  Needs --encoder=rnn, --stream_chunk>0 and exactly one of --stream_encoder=True
     # (with --bidirectional=False) or --stream_lookahead>=0.  The frontend adds 3 frames of latency
     stream_frontend=False,
+    # --tfm_chunk=N (0 = off) with --encoder=transformer: chunk-limited self-attention in training and
+    # evaluation alike — a frame attends to its own chunk of N frames and --tfm_left_chunks=M whole chunks before it, so
+    # the model looks at most N - 1 frames ahead whatever its depth, and can be run from a cache
+    tfm_chunk=0, tfm_left_chunks=0,
+    # --stream_tfm=True with --stream_chunk=N: the evaluation's transformer encoder runs chunk by chunk through a
+    # session (transformer_stream.ChunkedTransformerEncoder); with --frontend=conv3d the conv frontend
+    # runs through its own session in front of it.  Needs --encoder=transformer, --tfm_chunk>0 and --ctc_decoder=beam
+    stream_tfm=False,
     # the error of a model WITH the attention decoder: teacher (the live loop's sampled-token mismatch rate under
     # teacher forcing, train.eval) or beam (the edit-distance CER of the decoder's own beam-search transcript,
     # train.attention_cer, --attn_beam_width hypotheses of up to --attn_max_label_len characters) or joint (the same
@@ -210,6 +218,7 @@ def parse_flags(argv, defaults=DEFAULTS):
   stream_frontend_check(out)
   stream_encoder_check(out)
   stream_lookahead_check(out)
+  tfm_chunk_check(out)
   if out.get("attn_decode") not in ("teacher", "beam", "joint"):
     raise SystemExit("--attn_decode must be teacher, beam or joint")
   if out.get("attn_decode") == "joint" and not out.get("enable_ctc"):
@@ -468,7 +477,8 @@ def init_pixel_model(char2idx, f, device):
     from .transformer import TransformerVideoEncoder
     enc = TransformerVideoEncoder(frame_dim, d_model=f["hidden_size"], nhead=f["nhead"], num_layers=f["num_layers"],
                                   dim_feedforward=4 * f["hidden_size"], enable_ctc=True, vocab_size=len(char2idx),
-                                  char2idx=char2idx)
+                                  char2idx=char2idx, attn_chunk=int(f.get("tfm_chunk") or 0),
+                                  attn_left_chunks=int(f.get("tfm_left_chunks") or 0))
   else:
     enc = VideoEncoder(frame_dim, f["hidden_size"], rnn_type=f["rnn_type"], num_layers=f["num_layers"],
                        bidirectional=f["bidirectional"], rnn_dropout=f["rnn_dropout"], enable_ctc=True,
@@ -572,6 +582,32 @@ def stream_frontend_check(f):
     raise SystemExit("--stream_frontend with --stream_encoder=True needs --bidirectional=False: a session runs causally")
 
 
+def tfm_chunk_check(f):
+  """--tfm_chunk / --tfm_left_chunks / --stream_tfm need the transformer encoder (and the last one what its session and
+  the search behind it can run): SystemExit otherwise."""
+  chunk, left = int(f.get("tfm_chunk") or 0), int(f.get("tfm_left_chunks") or 0)
+  if chunk < 0:
+    raise SystemExit("--tfm_chunk must be >= 0 (0: every frame attends to the whole clip)")
+  if left < 0:
+    raise SystemExit("--tfm_left_chunks must be >= 0")
+  if chunk and f.get("encoder") != "transformer":
+    raise SystemExit("--tfm_chunk needs --encoder=transformer (the attention it limits)")
+  if left and f.get("encoder") != "transformer":
+    raise SystemExit("--tfm_left_chunks needs --encoder=transformer (the attention it limits)")
+  if left and not chunk:
+    raise SystemExit("--tfm_left_chunks needs --tfm_chunk>0 (the chunks it counts)")
+  if not f.get("stream_tfm"):
+    return
+  if f.get("encoder") != "transformer":
+    raise SystemExit("--stream_tfm needs --encoder=transformer (the encoder it streams)")
+  if not chunk:
+    raise SystemExit("--stream_tfm needs --tfm_chunk>0: a full-attention model cannot be cached")
+  if not int(f.get("stream_chunk") or 0) > 0:
+    raise SystemExit("--stream_tfm needs --stream_chunk>0 (the pieces the encoder is fed in)")
+  if f.get("ctc_decoder") != "beam":
+    raise SystemExit("--stream_tfm needs --ctc_decoder=beam")
+
+
 def _cer(correct, count):
   return float(count - correct) / count if count else 1.0
 
@@ -642,6 +678,7 @@ def run(**flags):
   stream_frontend_check(f)
   stream_encoder_check(f)
   stream_lookahead_check(f)
+  tfm_chunk_check(f)
   torch.manual_seed(f["seed"])
   rand = np.random.RandomState(seed=f["seed"])
   assert torch.cuda.is_available(), "the driver runs the HIP path: an MI355X is required (no CPU fallback)"
@@ -730,6 +767,12 @@ def run(**flags):
     from .frontend_stream import ChunkedPixelLipReader
     eval_encoder = ChunkedPixelLipReader(encoder, f["stream_chunk"],
                                          lookahead=f["stream_lookahead"] if f["stream_lookahead"] >= 0 else None)
+  if f["stream_tfm"]:
+    if chunked is None or decoding_step is not None:
+      raise SystemExit("--stream_tfm needs the encoder + CTC loop (--enable_ctc=True --ctc_only=True)")
+    from .transformer_stream import ChunkedTransformerEncoder, ChunkedTransformerPixelLipReader
+    eval_encoder = (ChunkedTransformerPixelLipReader(encoder, f["stream_chunk"]) if pixels
+                    else ChunkedTransformerEncoder(encoder, f["stream_chunk"]))
   error_of = make_error_of(f, eval_encoder, decoding_step, chunked or ctc_decoder, device, char2idx)
 
   def validation_error():
@@ -744,6 +787,9 @@ def run(**flags):
       streamed = " (encoder streamed: adds %d frames of look-ahead latency)" % f["stream_lookahead"]
     if f["stream_frontend"]:
       streamed = streamed[:-1] + "; frontend streamed: adds 3 frames of latency)"
+    if f["stream_tfm"]:
+      streamed = " (encoder streamed: adds up to %d frames of look-ahead latency%s)" % (
+          f["tfm_chunk"] - 1, "; frontend streamed: adds 3 frames of latency" if pixels else "")
     if delay["chars"]:
       print("\tCommit delay (chunks of %d frames): mean %.2f frames, p90 %d, %.1f%% of %d characters only at the end%s"
             % (f["stream_chunk"], delay["mean"], delay["p90"], 100.0 * delay["end_share"], delay["chars"], streamed))

@@ -44,7 +44,7 @@ class _StackFunction(torch.autograd.Function):
   @staticmethod
   def forward(ctx, x, lens, pe, cfg, *weights):
     L = _C.lib()
-    mode, Dm, nhead, F, nlayers, eps = cfg
+    mode, Dm, nhead, F, nlayers, eps, chunk, left = cfg
     B, T, I = x.shape
     dev = x.device
     dims = (B, T, I, Dm, nhead, F, nlayers)
@@ -54,9 +54,9 @@ class _StackFunction(torch.autograd.Function):
     reserve = torch.empty(rbytes, dtype=torch.uint8, device=dev)
     ws = torch.empty(wbytes, dtype=torch.uint8, device=dev)    # (the forward's split-K slabs; then the backward's buffers)
     h = torch.empty((B, T, Dm), dtype=torch.float32, device=dev)
-    _C.check(L.lr_tfm_forward(mode, x.data_ptr(), lens.data_ptr(), _ptr_array(weights), pe.data_ptr(), h.data_ptr(),
-                              reserve.data_ptr(), rbytes, ws.data_ptr(), wbytes, *dims, float(eps), _C.stream_handle()),
-             "lr_tfm_forward")
+    _C.check(L.lr_tfm_forward_chunked(mode, x.data_ptr(), lens.data_ptr(), _ptr_array(weights), pe.data_ptr(),
+                                      h.data_ptr(), reserve.data_ptr(), rbytes, ws.data_ptr(), wbytes, *dims, float(eps),
+                                      chunk, left, _C.stream_handle()), "lr_tfm_forward_chunked")
     if any(ctx.needs_input_grad):
       ctx.save_for_backward(x, lens, reserve, ws, *weights)
       ctx.cfg = cfg
@@ -70,14 +70,14 @@ class _StackFunction(torch.autograd.Function):
     x, lens, reserve, ws = ctx.saved_tensors[:4]
     weights = ctx.saved_tensors[4:]
     L = _C.lib()
-    mode, Dm, nhead, F, nlayers, eps = ctx.cfg
+    mode, Dm, nhead, F, nlayers, eps, chunk, left = ctx.cfg
     B, T, I = x.shape
     dims = (B, T, I, Dm, nhead, F, nlayers)
     dh = dh.contiguous()
     dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None   # (bf16 where x is: LR_TFM_DX_BF16)
-    _C.check(L.lr_tfm_backward_data(mode, lens.data_ptr(), _ptr_array(weights), dh.data_ptr(), _C.ptr(dx),
-                                    reserve.data_ptr(), reserve.numel(), ws.data_ptr(), ws.numel(), *dims,
-                                    _C.stream_handle()), "lr_tfm_backward_data")
+    _C.check(L.lr_tfm_backward_data_chunked(mode, lens.data_ptr(), _ptr_array(weights), dh.data_ptr(), _C.ptr(dx),
+                                            reserve.data_ptr(), reserve.numel(), ws.data_ptr(), ws.numel(), *dims, chunk,
+                                            left, _C.stream_handle()), "lr_tfm_backward_data_chunked")
     direct = _direct_grads(weights)
     grads = [w.grad for w in weights] if direct else [torch.empty_like(w) for w in weights]
 
@@ -107,10 +107,10 @@ class _StackFunction(torch.autograd.Function):
 
 class _AttentionFunction(torch.autograd.Function):
   """Multi-head self-attention core: qkv [B,T,3D] (fused projection) -> context [B,T,D]; keys at
-  positions >= key_lens[b] are masked."""
+  positions >= key_lens[b] are masked, and with chunk > 0 the keys outside the query's chunk window."""
 
   @staticmethod
-  def forward(ctx, qkv, key_lens, nhead, fused=False):
+  def forward(ctx, qkv, key_lens, nhead, fused=False, chunk=0, left_chunks=0):
     L = _C.lib()
     st = _C.stream_handle()
     B, T, D3 = qkv.shape
@@ -122,10 +122,10 @@ class _AttentionFunction(torch.autograd.Function):
       # one launch per (sample, head) problem set on the bf16 matrix cores; nothing T x T is written
       scale = 1.0 / math.sqrt(dh)
       out = torch.empty((B, T, D), dtype=torch.float32, device=dev)
-      _C.check(L.lr_attn_fused_forward(qkv.data_ptr(), key_lens.data_ptr(), out.data_ptr(), scale, B, T, nhead, dh, st),
-               "lr_attn_fused_forward")
+      _C.check(L.lr_attn_fused_forward_chunked(qkv.data_ptr(), key_lens.data_ptr(), out.data_ptr(), scale, B, T, nhead, dh,
+                                               chunk, left_chunks, st), "lr_attn_fused_forward_chunked")
       ctx.save_for_backward(qkv, key_lens)
-      ctx.cfg = (nhead, scale, True)
+      ctx.cfg = (nhead, scale, True, chunk, left_chunks)
       return out
     probs = torch.empty((B, nhead, T, T), dtype=torch.float32, device=dev)
     q, k, v = qkv.data_ptr(), qkv.data_ptr() + 4 * D, qkv.data_ptr() + 8 * D
@@ -133,18 +133,18 @@ class _AttentionFunction(torch.autograd.Function):
     _C.check(L.lr_sgemm_batched(0, 1, T, T, dh, 1.0, q, D3, T * D3, dh, k, D3, T * D3, dh, 0.0, probs.data_ptr(), T,
                                 nhead * T * T, T * T, B, nhead, st), "lr_sgemm_batched(QK^T)")
     scale = 1.0 / math.sqrt(dh)
-    _C.check(L.lr_attn_softmax_forward(probs.data_ptr(), key_lens.data_ptr(), scale, B, nhead, T, st),
-             "lr_attn_softmax_forward")
+    _C.check(L.lr_attn_softmax_forward_chunked(probs.data_ptr(), key_lens.data_ptr(), scale, B, nhead, T, chunk,
+                                               left_chunks, st), "lr_attn_softmax_forward_chunked")
     out = torch.empty((B, T, D), dtype=torch.float32, device=dev)
     _C.check(L.lr_sgemm_batched(0, 0, T, dh, T, 1.0, probs.data_ptr(), T, nhead * T * T, T * T, v, D3, T * D3, dh,
                                 0.0, out.data_ptr(), D, T * D, dh, B, nhead, st), "lr_sgemm_batched(PV)")
     ctx.save_for_backward(qkv, probs)
-    ctx.cfg = (nhead, scale, False)
+    ctx.cfg = (nhead, scale, False, chunk, left_chunks)
     return out
 
   @staticmethod
   def backward(ctx, dout):
-    nhead, scale, fused = ctx.cfg
+    nhead, scale, fused, chunk, left_chunks = ctx.cfg
     L = _C.lib()
     st = _C.stream_handle()
     dout = dout.contiguous()
@@ -152,9 +152,10 @@ class _AttentionFunction(torch.autograd.Function):
       qkv, key_lens = ctx.saved_tensors
       B, T, D3 = qkv.shape
       dqkv = torch.empty_like(qkv)
-      _C.check(L.lr_attn_fused_backward(qkv.data_ptr(), key_lens.data_ptr(), dout.data_ptr(), dqkv.data_ptr(), scale,
-                                        B, T, nhead, D3 // 3 // nhead, st), "lr_attn_fused_backward")
-      return dqkv, None, None, None
+      _C.check(L.lr_attn_fused_backward_chunked(qkv.data_ptr(), key_lens.data_ptr(), dout.data_ptr(), dqkv.data_ptr(),
+                                                scale, B, T, nhead, D3 // 3 // nhead, chunk, left_chunks, st),
+               "lr_attn_fused_backward_chunked")
+      return dqkv, None, None, None, None, None
     qkv, probs = ctx.saved_tensors
     B, T, D3 = qkv.shape
     D = D3 // 3
@@ -177,7 +178,7 @@ class _AttentionFunction(torch.autograd.Function):
                                 dh, B, nhead, st), "lr_sgemm_batched(dQ)")
     _C.check(L.lr_sgemm_batched(1, 0, T, dh, T, 1.0, dP.data_ptr(), T, PS, PI, q, D3, T * D3, dh, 0.0, dk, D3, T * D3,
                                 dh, B, nhead, st), "lr_sgemm_batched(dK)")
-    return dqkv, None, None, None
+    return dqkv, None, None, None, None, None
 
 
 def sinusoidal_encoding(max_len, d_model):
@@ -191,8 +192,11 @@ def sinusoidal_encoding(max_len, d_model):
 
 class TransformerVideoEncoder(nn.Module):
   def __init__(self, frame_dim, d_model=256, nhead=4, num_layers=4, dim_feedforward=1024, enable_ctc=True,
-               vocab_size=-1, char2idx=None, max_len=512):
+               vocab_size=-1, char2idx=None, max_len=512, attn_chunk=0, attn_left_chunks=0):
     super().__init__()
+    if int(attn_chunk) < 0 or int(attn_left_chunks) < 0:
+      raise ValueError("TransformerVideoEncoder: attn_chunk and attn_left_chunks must be >= 0 (got %d, %d)"
+                       % (attn_chunk, attn_left_chunks))
     assert d_model % nhead == 0 and d_model % 4 == 0 and (d_model // nhead) % 4 == 0
     # what the one-call stack (lr_tfm_*, lr_transformer.hip) takes; said HERE rather than as "unsupported shape" at the
     # first forward (the per-op path of rounds 1-4, which had no such limits, is gone)
@@ -211,6 +215,11 @@ class TransformerVideoEncoder(nn.Module):
     # projection) = fused QK^T -> masked softmax -> PV on the bf16 matrix cores, one launch per (sample, head) set
     # (lr_attention.hip; T <= 96, head dim 32 / 64)
     self.attention = 'f32'
+    # chunk-limited self-attention: attn_chunk = C > 0 lets a frame attend to its own chunk of C frames
+    # and attn_left_chunks whole chunks before it, in training and one-shot inference alike — what a model needs to
+    # be trained with before stream() can run it from a cache.  0: every frame attends to the whole clip.  Plain
+    # attributes, not part of the state_dict
+    self.attn_chunk, self.attn_left_chunks = int(attn_chunk), int(attn_left_chunks)
     self.input_proj = nn.Linear(frame_dim, d_model)
     layer = nn.TransformerEncoderLayer(d_model, nhead, dim_feedforward, dropout=0.0, activation='relu',
                                        batch_first=True, norm_first=False)
@@ -255,12 +264,18 @@ class TransformerVideoEncoder(nn.Module):
                   layer.linear1.bias, layer.linear2.weight, layer.linear2.bias, layer.norm1.weight, layer.norm1.bias,
                   layer.norm2.weight, layer.norm2.bias]
     cfg = (mode, self.d_model, self.nhead, self.layers[0].linear1.out_features, len(self.layers),
-           float(self.layers[0].norm1.eps))
+           float(self.layers[0].norm1.eps), self.attn_chunk, self.attn_left_chunks)
     h = _StackFunction.apply(x, lens, self.pe, cfg, *weights)
     if self.enable_ctc:
       lp = _ProjLogSoftmaxFunction.apply(h, self.output_proj.weight, self.output_proj.bias, self.output_mask)
       return lp, h, None
     return h, None
+
+  def stream(self, batch, device):
+    """A TransformerStream (transformer_stream.py): this encoder fed chunk by chunk over `batch`
+    independent slots, from a cache of each layer's keys and values.  Needs attn_chunk >= 1."""
+    from .transformer_stream import TransformerStream
+    return TransformerStream(self, batch, device)
 
   def save_best_model(self, error, file_path):
     import os
