@@ -806,6 +806,37 @@ int lr_decoder_lm_beam_search(int mode, int attn_type, const lr_decoder_params* 
                               float* out_scores, int32_t* rounds_host, void* workspace, size_t workspace_bytes, int B,
                               int T, int Hd, int Cd, int V, int A, lr_stream_t stream);
 
+/* Attention rescoring of CTC N-best lists, the second pass of two-pass decoding: each of an utterance's N first-pass
+ * hypotheses is scored once by the attention decoder, teacher-forced, and the list is reordered by
+ * s = (1 - ctc_weight) * a - ctc_weight * f + length_bonus * |q|.  Rule and structure:
+ * lipreading_amd/csrc/lr_attn_rescore.hip.  params / upper (drop_mask must be NULL), enc, enc_lens,
+ * h0 / c0 as lr_decoder_beam_search, plus
+ *   hyp_ids              int32 CTC classes (class v + 1 = token v), hypothesis (b, n)'s i-th class at
+ *                        hyp_ids[b*hyp_stride_b + n*hyp_stride_n + i] (strides in elements, >= 0): the (B, beam, T)
+ *                        tensor of lr_ctc_beam_decode, or a [:, :N, :W] view of it, goes in as it is
+ *   hyp_lens [B][N]      int32 classes per hypothesis (clamped to [0, W]); ids past it are never read
+ *   first_scores [B][N]  fp32 -log P of the first pass; a slot with length 0 and +inf, or with NaN, is empty
+ *   ctc_weight           lambda in [0, 1]; length_bonus: any finite value
+ *   out_order [B][N] int32, out_scores [B][N] fp32, out_attn [B][N] fp32: ranked best first, the input slot at each
+ *                        rank, its s and its a; both -inf for slots that cannot be scored (a token that is PAD, BOS,
+ *                        blank or outside [0, V)), which follow the scored ones in first-pass order, and for empty
+ *                        slots, which come last
+ * No host synchronisation.  Limits: 1 <= N <= 128, 1 <= W <= 1024, 3 <= V <= 1024, B*N <= 65535,
+ * B*N*(W+1) <= 65535*64, B*N*(W+1)*max(G*Hd, T, V, A) < 2^31 and B*T*max(G*Hd, T, V, A) < 2^31 (G gates: 3 GRU, 4 LSTM,
+ * 1 tanh), Hd % 4 == 0, the scoring head's LDS (Hd + V) * 4 <= 60 KB, with concat attention A > 0 and 2*A*4 <= 60 KB;
+ * every RNN mode, every attention type, 1 .. LR_DEC_MAX_LAYERS layers (else LR_ERR_UNSUPPORTED; the workspace query
+ * returns 0 for every request the call rejects by its sizes); a weight outside [0, 1], a non-finite weight or bonus, a
+ * NULL required pointer, a negative id stride or a drop_mask is LR_ERR_INVALID_ARG. */
+size_t lr_decoder_rescore_workspace_bytes(int mode, int attn_type, int num_layers, int B, int N, int W, int T, int Hd,
+                                          int Cd, int V, int A);
+int lr_decoder_rescore(int mode, int attn_type, const lr_decoder_params* params_host,
+                       const lr_decoder_upper* upper_host, const float* enc, const int32_t* enc_lens, const float* h0,
+                       const float* c0, const int32_t* hyp_ids, int64_t hyp_stride_b, int64_t hyp_stride_n,
+                       const int32_t* hyp_lens, const float* first_scores, int bos, int eos, int pad,
+                       double ctc_weight, double length_bonus, int32_t* out_order, float* out_scores, float* out_attn,
+                       void* workspace, size_t workspace_bytes, int B, int N, int W, int T, int Hd, int Cd, int V,
+                       int A, lr_stream_t stream);
+
 /* The decoder loss of the train loop (train_better_model.py:62,65): over the R = B*L (sample, step) rows,
  * -sum_r log_probs[r][label_r] for label_r != ignore_index (F.nll_loss(ignore_index=PAD, reduction='sum') summed
  * over the steps) divided by the number of such rows ((labels != PAD).sum()).  labels: int64, row (b, i) at

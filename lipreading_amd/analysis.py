@@ -8,7 +8,7 @@ from the decoded transcript's alignment on the device (confusion_matrix below); 
 """
 import torch
 
-from .data import BOS, host_max_len
+from .data import BOS, EOS, host_max_len
 
 # analysis.py:133-139: the 26 letters grouped by viseme (vowels and w / b p m / f v / alveolars / j / velars and x / h)
 VISEME_ORDER = list("aeiyouw" "bpm" "fv" "tdnszlr" "j" "kqcgx" "h")
@@ -52,6 +52,24 @@ def best_ids(decoding_step, hidden, frame_lens, state, beam_width, max_label_len
                         ctc_weight, pre_beam, lm)
   ids, lens = ids.cpu(), lens.cpu()
   return [ids[b, :int(lens[b])].tolist() for b in range(ids.shape[0])]
+
+
+def rescored_best(decoding_step, hidden, frame_lens, state, hyp_ids, hyp_lens, first_scores, ctc_weight=0.5,
+                  length_bonus=0.0):
+  """Two-pass decoding's answer, left on the device: the CTC N-best list (hyp_ids (B, N, W) classes,
+  hyp_lens, first_scores: BeamCTCDecoder.decode_ids' ids, lens and scores, or their [:, :N] part) rescored by
+  CharDecodingStep.rescore, and the hypothesis it ranks first returned in DECODER tokens (class - 1), cut at its first
+  EOS: (ids (B, W) int32, lens (B,) int32), lens counting the tokens before that EOS.  Nothing is read back."""
+  order = decoding_step.rescore(hidden, frame_lens, state, hyp_ids, hyp_lens, first_scores, ctc_weight=ctc_weight,
+                                length_bonus=length_bonus)[0]
+  B, _, W = hyp_ids.shape
+  best = order[:, :1].long()
+  ids = torch.gather(hyp_ids, 1, best[:, :, None].expand(B, 1, W))[:, 0] - 1
+  lens = torch.gather(hyp_lens, 1, best)[:, 0].clamp(0, W).to(torch.int32)
+  at = torch.arange(W, device=ids.device, dtype=torch.int32)[None, :]
+  eos = decoding_step.char2idx[EOS]
+  first_eos = torch.where((ids == eos) & (at < lens[:, None]), at, lens[:, None]).min(dim=1)[0]
+  return ids, first_eos.to(torch.int32)
 
 
 def inference(encoder, decoding_step, frames, frame_lens, chars, char_lens, device, char2idx, beam_width=5,

@@ -10,6 +10,7 @@ all `max_label_len` steps in ONE call into the C ABI (lr_decoder_forward / lr_de
 the loop is a strictly sequential chain of small kernels, so the host should not sit between them.
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -452,6 +453,88 @@ class CharDecodingStep(nn.Module):
                  lens.data_ptr(), scores.data_ptr(), ctypes.byref(rounds), ws.data_ptr(), wbytes, B, T, Hd, Cd, V, A)
     self.beam_rounds = int(rounds.value)
     return ids, lens, scores
+
+  def rescore(self, encoder_hidden_states, encoder_lens, previous_state, hyp_ids, hyp_lens, first_scores,
+              ctc_weight=0.5, length_bonus=0.0):
+    """Attention rescoring of a CTC N-best list, the second pass of two-pass decoding (lr_decoder_rescore; the rule is
+    in lipreading_amd/csrc/lr_attn_rescore.hip and DESIGN.md §32): every hypothesis is scored once by this decoder,
+    teacher-forced, and each utterance's list is reordered by (1 - ctc_weight) * attention - ctc_weight * first_score
+    + length_bonus * (tokens scored), entirely on the device and without a host synchronisation.
+
+    encoder_hidden_states (B, T, Hd), encoder_lens (B,), previous_state as for decode_sequence.  hyp_ids (B, N, W) int32
+    CTC classes (class v + 1 = token v, the layout of decoder.ctc_labels; any view with a contiguous last dimension
+    goes in without a copy), hyp_lens (B, N), first_scores (B, N) float32 -log P: what BeamCTCDecoder.decode_ids
+    returns, or its [:, :N] part.  Returns device tensors (order (B, N) int32, scores (B, N) float32, attn_scores
+    (B, N) float32), ranked best first: the input slot at each rank, its combined score and its attention
+    log-probability; -inf for slots that cannot be scored and for empty ones, which come last."""
+    for name, w in (("ctc_weight", ctc_weight), ("length_bonus", length_bonus)):
+      if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w):
+        raise ValueError("%s must be a finite number, got %r" % (name, w))
+    if not 0.0 <= ctc_weight <= 1.0:
+      raise ValueError("ctc_weight must be a number in [0, 1], got %r" % (ctc_weight,))
+    states = list(previous_state) if isinstance(previous_state, tuple) else [previous_state]
+    for t in [encoder_hidden_states, hyp_ids, hyp_lens, first_scores] + states:
+      if not torch.is_tensor(t):
+        raise ValueError("encoder states, previous_state, hyp_ids, hyp_lens and first_scores must be tensors")
+    if encoder_hidden_states.dim() != 3:
+      raise ValueError("encoder_hidden_states must be (B, T, hidden), got %s" % (tuple(encoder_hidden_states.shape),))
+    B, T, Hd = encoder_hidden_states.shape
+    if hyp_ids.dim() != 3 or hyp_ids.shape[0] != B or hyp_ids.shape[1] < 1 or hyp_ids.shape[2] < 1:
+      raise ValueError("hyp_ids must be (B, N, W) with B = %d, got %s" % (B, tuple(hyp_ids.shape)))
+    N, W = int(hyp_ids.shape[1]), int(hyp_ids.shape[2])
+    if N > 128 or W > 1024:
+      raise ValueError("rescore takes at most 128 hypotheses of at most 1024 classes, got N=%d, W=%d" % (N, W))
+    if hyp_ids.dtype != torch.int32:
+      raise ValueError("hyp_ids must be int32, got %s" % (hyp_ids.dtype,))
+    if tuple(hyp_lens.shape) != (B, N) or tuple(first_scores.shape) != (B, N):
+      raise ValueError("hyp_lens and first_scores must be (B, N) = (%d, %d), got %s and %s"
+                       % (B, N, tuple(hyp_lens.shape), tuple(first_scores.shape)))
+    mode = _MODES[self.rnn_type]
+    if (mode == 1) != (len(states) == 2):
+      raise ValueError("previous_state must be (h, c) for the LSTM and h otherwise")
+    if states[0].shape != (self.num_layers, B, Hd) or Hd != self.hidden_size:
+      raise ValueError("previous_state must be (num_layers, B, hidden) = (%d, %d, %d), got %s"
+                       % (self.num_layers, B, self.hidden_size, tuple(states[0].shape)))
+    if torch.is_tensor(encoder_lens):
+      if encoder_lens.numel() != B:
+        raise ValueError("encoder_lens must hold B = %d values" % B)
+    # (the shapes first, so that they are refused on any device; then the device itself)
+    dev = encoder_hidden_states.device
+    if not all(t.is_cuda for t in [encoder_hidden_states, hyp_ids, hyp_lens, first_scores] + states):
+      raise ValueError("rescore runs on the GPU: encoder states, previous_state, hyp_ids, hyp_lens and first_scores "
+                       "must be device tensors")
+    if any(t.device != dev for t in [hyp_ids, hyp_lens, first_scores] + states):
+      raise ValueError("every tensor must be on the encoder states' device")
+    L_ = _C.lib()
+    enc = encoder_hidden_states.detach().to(torch.float32).contiguous()
+    h0 = states[0].detach().to(torch.float32).contiguous()
+    c0 = states[1].detach().to(torch.float32).contiguous() if mode == 1 else None
+    enc_lens = torch.as_tensor(encoder_lens).to(device=dev, dtype=torch.int32).contiguous()
+    ids = hyp_ids.detach()
+    if ids.stride(2) != 1 or ids.stride(0) < 0 or ids.stride(1) < 0:
+      ids = ids.contiguous()
+    lens = hyp_lens.detach().to(torch.int32).contiguous()
+    first = first_scores.detach().to(torch.float32).contiguous()
+    params = self._params()
+    pstruct = _C.DecoderParams(*[_C.ptr(p) for p in params[:13]], self.output_mask.data_ptr())
+    ustruct, NL = _upper_struct(params[13:], None)
+    at = _ATT_CODE[self.attention_type]
+    Cd, V, A = self.char_dim, self.vocab_size, max(int(self.attn_hidden_size), 0)
+    wbytes = L_.lr_decoder_rescore_workspace_bytes(mode, at, NL, B, N, W, T, Hd, Cd, V, A)
+    if wbytes == 0:
+      raise ValueError("rescore does not support this shape (B=%d, N=%d, W=%d, T=%d, V=%d, Hd=%d)"
+                       % (B, N, W, T, V, Hd))
+    ws = torch.empty(wbytes, dtype=torch.uint8, device=dev)
+    order = torch.empty((B, N), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, N), dtype=torch.float32, device=dev)
+    attn = torch.empty((B, N), dtype=torch.float32, device=dev)
+    c2i = self.char2idx
+    _host.launch(dev, "lr_decoder_rescore", L_.lr_decoder_rescore, mode, at, ctypes.byref(pstruct),
+                 ctypes.byref(ustruct) if ustruct is not None else None, enc.data_ptr(), enc_lens.data_ptr(),
+                 h0.data_ptr(), _C.ptr(c0), ids.data_ptr(), ids.stride(0), ids.stride(1), lens.data_ptr(),
+                 first.data_ptr(), c2i[BOS], c2i[EOS], c2i[PAD], float(ctc_weight), float(length_bonus),
+                 order.data_ptr(), scores.data_ptr(), attn.data_ptr(), ws.data_ptr(), wbytes, B, N, W, T, Hd, Cd, V, A)
+    return order, scores, attn
 
   def forward(self, input_, previous_state, encoder_lens, encoder_hidden_states):
     """One step, reference contract (better_model.py:161-231): input_ (B,), previous_state

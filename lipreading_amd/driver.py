@@ -78,8 +78,12 @@ DEFAULTS = dict(  # train.py:134-167
     # teacher forcing, train.eval) or beam (the edit-distance CER of the decoder's own beam-search transcript,
     # train.attention_cer, --attn_beam_width hypotheses of up to --attn_max_label_len characters) or joint (the same
     # CER of the joint CTC/attention beam search, the CTC head's prefix probability weighted by --attn_ctc_weight;
-    # needs --enable_ctc)
+    # needs --enable_ctc) or rescore (two-pass decoding, DESIGN.md §32: the CER of the CTC beam search's
+    # --attn_rescore_nbest best hypotheses rescored by the attention decoder, train.rescored_cer, the first pass weighted
+    # by --attn_ctc_weight and --attn_length_bonus added per scored token; needs --enable_ctc=True, --ctc_decoder=beam
+    # and a decoder, and takes --lm_path / --hotwords for its first pass)
     attn_decode="teacher", attn_beam_width=10, attn_max_label_len=100, attn_ctc_weight=0.3,
+    attn_rescore_nbest=10, attn_length_bonus=0.0,
     # --attn_lm_path (an ARPA file, '' = none) adds a word language model to the --attn_decode=beam|joint search
     # (lm.WordLM), weighted by --attn_lm_alpha, plus --attn_lm_beta per word
     attn_lm_path="", attn_lm_alpha=0.0, attn_lm_beta=0.0,
@@ -219,8 +223,9 @@ def parse_flags(argv, defaults=DEFAULTS):
   stream_encoder_check(out)
   stream_lookahead_check(out)
   tfm_chunk_check(out)
-  if out.get("attn_decode") not in ("teacher", "beam", "joint"):
-    raise SystemExit("--attn_decode must be teacher, beam or joint")
+  if out.get("attn_decode") not in ("teacher", "beam", "joint", "rescore"):
+    raise SystemExit("--attn_decode must be teacher, beam, joint or rescore")
+  attn_rescore_check(out)
   if out.get("attn_decode") == "joint" and not out.get("enable_ctc"):
     raise SystemExit("--attn_decode=joint needs --enable_ctc (the CTC head's log-probs)")
   if out.get("attn_lm_path") and out.get("attn_decode") not in ("beam", "joint"):
@@ -526,6 +531,30 @@ def weights_path(root, data):
   return path
 
 
+def attn_rescore_check(f):
+  """--attn_decode=rescore needs both heads and the CTC beam search, and streams only through the causal RNN session:
+  SystemExit naming the flag otherwise."""
+  import math
+  if f.get("attn_decode") != "rescore":
+    return
+  nbest, bonus = f.get("attn_rescore_nbest", 10), f.get("attn_length_bonus", 0.0)
+  if isinstance(nbest, bool) or not isinstance(nbest, int) or not 1 <= nbest <= min(int(f.get("beam_width", 100)), 128):
+    raise SystemExit("--attn_rescore_nbest must be in [1, min(--beam_width, 128)]")
+  if isinstance(bonus, bool) or not isinstance(bonus, (int, float)) or not math.isfinite(bonus):
+    raise SystemExit("--attn_length_bonus must be a finite number")
+  if not f.get("enable_ctc"):
+    raise SystemExit("--attn_decode=rescore needs --enable_ctc=True (the first pass reads the CTC head)")
+  if f.get("ctc_decoder") != "beam":
+    raise SystemExit("--attn_decode=rescore needs --ctc_decoder=beam (the first pass is the CTC beam search)")
+  if f.get("ctc_only"):
+    raise SystemExit("--attn_decode=rescore needs the attention decoder: not with --ctc_only=True")
+  for name, on in (("stream_lookahead", int(-1 if f.get("stream_lookahead") is None else f["stream_lookahead"]) >= 0),
+                   ("stream_tfm", bool(f.get("stream_tfm"))), ("stream_frontend", bool(f.get("stream_frontend")))):
+    if on:
+      raise SystemExit("--attn_decode=rescore does not go with --%s: only the causal RNN session (--stream_encoder=True) "
+                       "hands the decoder a final state" % name)
+
+
 def stream_encoder_check(f):
   """--stream_encoder needs what an encoder session can run: SystemExit otherwise."""
   if not f.get("stream_encoder"):
@@ -631,11 +660,19 @@ def make_error_of(f, encoder, decoding_step, ctc_decoder, device, char2idx):
   def error_of(loader):
     """The live loop's "CER" is the sampled-token mismatch rate of the attention decoder (train.py:287-288
     via eval's correct/count), or with --attn_decode=beam the edit-distance CER of its beam-search transcripts
-    (--attn_decode=joint: of the joint CTC/attention beam search's);
+    (--attn_decode=joint: of the joint CTC/attention beam search's; --attn_decode=rescore: of the CTC beam search's
+    N-best rescored by the decoder);
     without a decoder it is the greedy-decoded CER of the CTC head (decoder.py:64-73 on :182-197, as
     archive/train_model.py:351-357 composes them), or the beam-decoded one with --ctc_decoder=beam."""
     if on_device and decoding_step is None:
       return scored(loader, decoder=ctc_decoder)
+    if decoding_step is not None and f["attn_decode"] == "rescore":
+      how = dict(ctc_weight=f["attn_ctc_weight"], length_bonus=f["attn_length_bonus"])
+      if on_device:
+        return scored(loader, decoder=ctc_decoder, decoding_step=decoding_step,
+                      rescore_nbest=f["attn_rescore_nbest"], **how)
+      return T.rescored_cer(encoder, decoding_step, loader, device, char2idx, ctc_decoder,
+                            nbest=f["attn_rescore_nbest"], **how)
     if on_device and f["attn_decode"] in ("beam", "joint"):
       return scored(loader, decoding_step=decoding_step, beam_width=f["attn_beam_width"],
                     max_label_len=f["attn_max_label_len"],
@@ -679,6 +716,7 @@ def run(**flags):
   stream_encoder_check(f)
   stream_lookahead_check(f)
   tfm_chunk_check(f)
+  attn_rescore_check(f)
   torch.manual_seed(f["seed"])
   rand = np.random.RandomState(seed=f["seed"])
   assert torch.cuda.is_available(), "the driver runs the HIP path: an MI355X is required (no CPU fallback)"
@@ -737,7 +775,8 @@ def run(**flags):
   decoder_path = os.path.join(weights_dir, "best_decoder.pth")
 
   ctc_decoder = None
-  if ctc_only and f["ctc_decoder"] == "beam":
+  two_pass = decoding_step is not None and f["attn_decode"] == "rescore"   # the first pass is the CTC beam search
+  if (ctc_only or two_pass) and f["ctc_decoder"] == "beam":
     from .decoder import BeamCTCDecoder, ctc_labels
     labels = ctc_labels(char2idx)
     ctc_decoder = BeamCTCDecoder(labels, lm_path=f["lm_path"] or None, alpha=f["lm_alpha"],
@@ -752,8 +791,9 @@ def run(**flags):
     chunked = ChunkedBeamDecoder(ctc_decoder, f["stream_chunk"])
   eval_encoder = encoder
   if f["stream_encoder"]:
-    if chunked is None or decoding_step is not None:
-      raise SystemExit("--stream_encoder needs the encoder + CTC loop (--enable_ctc=True --ctc_only=True)")
+    if chunked is None or (decoding_step is not None and not two_pass):
+      raise SystemExit("--stream_encoder needs the encoder + CTC loop (--enable_ctc=True --ctc_only=True) or "
+                       "--attn_decode=rescore")
     if not f["stream_frontend"]:
       from .encoder_stream import ChunkedEncoder
       eval_encoder = ChunkedEncoder(encoder, f["stream_chunk"])

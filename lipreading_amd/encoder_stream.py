@@ -4,7 +4,8 @@ BeamCTCDecoder.stream resumes the search; these resume the model in front of it.
 independent slots, the recurrent state of every layer in one device tensor; feed() takes the next frames of every slot
 and returns their log-probabilities — the same bits however the utterance is cut, in whichever slot it sits.
 ChunkedEncoder runs a whole padded batch through a session (what the evaluation loops take in a VideoEncoder's place),
-LiveTranscriber puts a session in front of a BeamStream.
+LiveTranscriber puts a session in front of a BeamStream, and TwoPassTranscriber adds the attention decoder's second pass
+over the search's N-best when the utterance ends.
 
 Offline decoding of whole clips stays with VideoEncoder.forward and its one-launch recurrences: a session re-reads the
 weights at every frame.  Inference only — nothing is kept for a backward.
@@ -245,3 +246,86 @@ class LiveTranscriber(object):
     self.encoder_stream.reset(mask)
     self.search.reset(mask)
     return self
+
+
+class TwoPassTranscriber(LiveTranscriber):
+  """A LiveTranscriber that also keeps every slot's encoder states, (batch, max_frames, H) on the device, for the
+  second pass of two-pass decoding: partial() / result() stay the CTC search's, live; when the
+  utterances end, rescored() has the attention decoder rescore the search's N best hypotheses
+  (CharDecodingStep.rescore) from the session's final state.  feed() writes each chunk at the slot's own frame offset
+  without a host synchronisation.  `max_frames` is at most 1024, the longest hypothesis rescore takes.  An utterance
+  longer than max_frames is an error, not a truncation: its later frames are not kept here, the search marks the slot
+  (LR_BEAM_STREAM_OVERFLOW) while the encoder session's state goes on past them, and rescored() raises for that slot
+  as result() does, until it is reset."""
+
+  def __init__(self, encoder, decoding_step, ctc_decoder, batch, max_frames, device):
+    if not 1 <= int(max_frames) <= 1024:
+      raise ValueError("max_frames must be in [1, 1024] (the longest hypothesis rescore takes), got %d" % max_frames)
+    super(TwoPassTranscriber, self).__init__(encoder, ctc_decoder, batch, max_frames, device)
+    from .decoder import ctc_labels
+    if list(ctc_decoder.labels) != ctc_labels(decoding_step.char2idx) or ctc_decoder.blank_index != 0:
+      raise ValueError("ctc_decoder's labels must be decoder.ctc_labels(decoding_step.char2idx) with blank_index 0")
+    if decoding_step.hidden_size != encoder.hidden_size or decoding_step.num_layers != encoder.num_layers:
+      raise ValueError("decoding_step was not built for this encoder (hidden size or layers differ)")
+    self.decoding_step = decoding_step
+    st = self.encoder_stream
+    self.max_frames = int(max_frames)
+    # rows (slot, frame), plus one spare row at the end that takes the writes of idle positions (never read)
+    self._rows = torch.zeros((st.batch * self.max_frames + 1, st.H), dtype=torch.float32, device=st.device)
+    self._row0 = torch.arange(st.batch, device=st.device)[:, None] * self.max_frames
+    self._at = torch.zeros((st.batch,), dtype=torch.int64, device=st.device)
+
+  @property
+  def hidden(self):
+    """(batch, max_frames, H): each slot's encoder states so far, zero past its frames."""
+    return self._rows[:-1].view(self.encoder_stream.batch, self.max_frames, self.encoder_stream.H)
+
+  def feed(self, frames, sizes=None):
+    st = self.encoder_stream
+    lp, y = st.feed(frames, sizes, need_hidden=True)
+    t = lp.shape[1]
+    if t:
+      self.search.feed(lp, sizes)
+      step = torch.arange(t, device=st.device)[None, :]
+      took = (torch.full((st.batch,), t, device=st.device) if sizes is None
+              else sizes.to(device=st.device, dtype=torch.int64).clamp(0, t))
+      pos = self._at[:, None] + step
+      row = torch.where((step < took[:, None]) & (pos < self.max_frames), self._row0 + pos,
+                        pos.new_tensor(st.batch * self.max_frames))
+      self._rows.index_copy_(0, row.reshape(-1), y.reshape(-1, st.H))
+      self._at = (self._at + took).clamp_(max=self.max_frames)
+    return self
+
+  def reset(self, mask=None):
+    super(TwoPassTranscriber, self).reset(mask)
+    if mask is None:
+      self._rows.zero_()
+      self._at.zero_()
+    else:
+      keep = (mask.to(self._at.device) == 0)
+      self.hidden.mul_(keep[:, None, None].to(self._rows.dtype))
+      self._at.mul_(keep.to(self._at.dtype))
+    return self
+
+  def rescored_ids(self, nbest=10, ctc_weight=0.5, length_bonus=0.0):
+    """The second pass on the device: (ids, offsets, lens, scores, attn_scores, status) with the search's `nbest`
+    best hypotheses reordered by CharDecodingStep.rescore — ids / offsets (batch, nbest, max_frames), the rest
+    (batch, nbest) and status (2, batch), the search's and the encoder session's: read_ids(nbest),
+    encoder_stream.read() and one rescore call."""
+    ids, off, lens, first, _, _, status = self.search.read_ids(nbest, self.max_frames)
+    h, c, frames, estatus = self.encoder_stream.read()
+    order, scores, attn = self.decoding_step.rescore(self.hidden, frames, h if c is None else (h, c), ids, lens, first,
+                                                     ctc_weight=ctc_weight, length_bonus=length_bonus)
+    o = order.long()
+    wide = o[:, :, None].expand(-1, -1, ids.shape[2])
+    return (torch.gather(ids, 1, wide), torch.gather(off, 1, wide), torch.gather(lens, 1, o), scores, attn,
+            torch.stack((status, estatus)))
+
+  def rescored(self, nbest=10, ctc_weight=0.5, length_bonus=0.0):
+    """(strings, offsets) in BeamCTCDecoder.decode's contract, the `nbest` best hypotheses of the first pass in the
+    second pass's order (best first).  A status bit of either session raises LipReadingHipError."""
+    ids, off, lens, _, _, status = self.rescored_ids(nbest, ctc_weight, length_bonus)
+    status = status.cpu().tolist()
+    self.search._raise_for(status[0])
+    self.encoder_stream._raise_for(status[1])
+    return self.search.decoder._strings(ids, off, lens)

@@ -791,6 +791,57 @@ def attention_cer(encoder, decoding_step, data_loader, device, char2idx, beam_wi
   return _host_cer(encoder, data_loader, device, char2idx, hypotheses)
 
 
+def _two_pass(encoder, decoding_step, ctc_decoder, frames, frame_lens, device, nbest, ctc_weight, length_bonus,
+              frame_lens_d=None):
+  """One batch of two-pass decoding, all enqueued: one encoder pass for log-probs, hidden states and
+  final state, the CTC search's N-best (ctc_decoder.decode_ids), then CharDecodingStep.rescore through
+  analysis.rescored_best -> (ids (B, W) int32 decoder tokens, lens (B,) int32) of the hypothesis ranked first.  Only
+  decode_ids of the CTC decoder and __call__ of the encoder are used: decoder.ChunkedBeamDecoder and
+  encoder_stream.ChunkedEncoder stand in for them unchanged.  A clip of more than 1024 frames is rescored on the first
+  1024 classes of each hypothesis, the most rescore takes (a transcript has far fewer characters than frames)."""
+  from .analysis import rescored_best
+  lens_d = frame_lens.to(device) if frame_lens_d is None else frame_lens_d
+  log_probs, hidden, state = encoder(frames.to(device), lens_d, max_len=host_max_len(frame_lens))
+  ids, _, lens, scores = ctc_decoder.decode_ids(log_probs, lens_d)
+  n = min(int(nbest), ids.shape[1])
+  return rescored_best(decoding_step, hidden, lens_d, state, ids[:, :n, :1024], lens[:, :n], scores[:, :n],
+                       ctc_weight=ctc_weight, length_bonus=length_bonus)
+
+
+def _check_two_pass(encoder, ctc_decoder, nbest, char2idx):
+  from .analysis import need_ctc_head
+  from .decoder import ctc_labels
+  need_ctc_head(encoder)
+  if not hasattr(ctc_decoder, "decode_ids") or not hasattr(ctc_decoder, "beam_width"):
+    raise TypeError("attention rescoring needs a CTC beam decoder with decode_ids() (BeamCTCDecoder)")
+  if list(ctc_decoder.labels) != ctc_labels(char2idx):
+    raise ValueError("the CTC decoder's labels are not ctc_labels(char2idx)")
+  if isinstance(nbest, bool) or not isinstance(nbest, int) or not 1 <= nbest <= min(ctc_decoder.beam_width, 128):
+    raise ValueError("nbest must be an int in [1, min(beam_width, 128)] = [1, %d], got %r"
+                     % (min(ctc_decoder.beam_width, 128), nbest))
+
+
+def rescored_cer(encoder, decoding_step, data_loader, device, char2idx, ctc_decoder, nbest=10, ctc_weight=0.5,
+                 length_bonus=0.0):
+  """CER of two-pass decoding: the CTC beam search's `nbest` best hypotheses rescored by the attention
+  decoder (CharDecodingStep.rescore: (1 - ctc_weight) * attention - ctc_weight * first-pass score + length_bonus *
+  tokens), the hypothesis ranked first cut at its first EOS and scored as attention_cer scores (the host CER loop, a
+  batch whose recurrence timed out run again on the per-step kernels).  `ctc_decoder` is a BeamCTCDecoder over
+  ctc_labels(char2idx) with log_probs_input=True, or decoder.ChunkedBeamDecoder around one; the encoder needs
+  enable_ctc."""
+  _check_two_pass(encoder, ctc_decoder, nbest, char2idx)
+  inv = {v: k for k, v in char2idx.items()}
+  decoding_step.eval()
+
+  def hypotheses(frames, frame_lens):
+    ids, lens = _two_pass(encoder, decoding_step, ctc_decoder, frames, frame_lens, device, nbest, ctc_weight,
+                          length_bonus)
+    ids, lens = ids.cpu(), lens.cpu()
+    return [''.join(inv[int(i)] for i in ids[b, :int(lens[b])]) for b in range(ids.shape[0])]
+
+  return _host_cer(encoder, data_loader, device, char2idx, hypotheses)
+
+
 # ---- scoring on the device (lipreading_amd/scoring.py, DESIGN.md §17) -------------------------------------------------
 # The three loops above copy the ids to the host every batch, join label strings and run decoder._edit_distance (a
 # pure-Python O(n m) loop) per utterance, with the GPU idle.  device_scores keeps the ids on the device: per batch
@@ -811,12 +862,13 @@ class _DeviceScoring(object):
   """What a device_scores call carries from batch to batch."""
 
   def __init__(self, encoder, device, char2idx, decoder, decoding_step, beam_width, max_label_len, ctc_weight, pre_beam,
-               units, align, n_batches, lm=None):
+               units, align, n_batches, lm=None, rescore_nbest=0, length_bonus=0.0):
     from .decoder import GreedyDecoder, ctc_labels
     from .scoring import EditScorer
     self.encoder, self.device, self.decoding_step = encoder, torch.device(device), decoding_step
     self.beam = (beam_width, max_label_len)
-    self.joint = decoding_step is not None and ctc_weight > 0
+    self.rescore_nbest, self.length_bonus = int(rescore_nbest), length_bonus
+    self.joint = decoding_step is not None and ctc_weight > 0 and not self.rescore_nbest
     self.ctc_weight, self.pre_beam, self.lm = ctc_weight, pre_beam, lm
     self.units, self.align = tuple(units), bool(align)
     inv = {v: k for k, v in char2idx.items()}
@@ -829,7 +881,8 @@ class _DeviceScoring(object):
       if list(self.decoder.labels) != labels:
         raise ValueError("the decoder's labels are not ctc_labels(char2idx)")
     else:
-      labels, self.shift, self.decoder = [inv[i] for i in range(len(inv))], 0, None
+      # (two-pass decoding keeps the CTC decoder for its first pass; its answer is in decoder tokens all the same)
+      labels, self.shift, self.decoder = [inv[i] for i in range(len(inv))], 0, decoder if self.rescore_nbest else None
     key = tuple(labels)
     self.scorer = _SCORERS.get(key)
     if self.scorer is None:
@@ -846,6 +899,9 @@ class _DeviceScoring(object):
       if len(got) == 3:
         return got[0], got[2]
       return got[0][:, 0], got[2][:, 0]       # the best hypothesis of (B, W, T) / (B, W)
+    if self.rescore_nbest:
+      return _two_pass(self.encoder, self.decoding_step, self.decoder, frames, frame_lens, self.device,
+                       self.rescore_nbest, self.ctc_weight, self.length_bonus, frame_lens_d=frame_lens_d)
     from .analysis import best_beam, encode_for_beam
     hidden, lens_d, state, y = encode_for_beam(self.encoder, frames, frame_lens, self.device, with_ctc=self.joint)
     return best_beam(self.decoding_step, hidden, lens_d, state, *self.beam, ctc_log_probs=y, ctc_weight=self.ctc_weight,
@@ -869,16 +925,21 @@ def _device_batch(ctx, k, frames, frame_lens, frame_lens_d, chars_d, char_lens_d
 
 
 def _device_score_run(encoder, data_loader, device, char2idx, decoder=None, decoding_step=None, beam_width=10,
-                      max_label_len=100, ctc_weight=0.0, pre_beam=None, units=('char', 'word'), align=False, lm=None):
+                      max_label_len=100, ctc_weight=0.0, pre_beam=None, units=('char', 'word'), align=False, lm=None,
+                      rescore_nbest=0, length_bonus=0.0):
   global last_device_score_stats
   device = torch.device(device)
   if device.type != "cuda":
     raise _C.LipReadingHipError("device scoring runs on the MI355X only (no CPU fallback)")
-  if decoding_step is not None and ctc_weight > 0:
+  if rescore_nbest:
+    if decoding_step is None:
+      raise ValueError("rescore_nbest needs a decoding_step (the second pass) next to the CTC decoder")
+    _check_two_pass(encoder, decoder, rescore_nbest, char2idx)
+  elif decoding_step is not None and ctc_weight > 0:
     from .analysis import need_ctc_head
     need_ctc_head(encoder)
   ctx = _DeviceScoring(encoder, device, char2idx, decoder, decoding_step, beam_width, max_label_len, ctc_weight, pre_beam,
-                       units, align, len(data_loader), lm=lm)
+                       units, align, len(data_loader), lm=lm, rescore_nbest=rescore_nbest, length_bonus=length_bonus)
   ctx.scorer.reset()
   encoder.eval()
   if decoding_step is not None:
@@ -909,29 +970,34 @@ def _device_score_run(encoder, data_loader, device, char2idx, decoder=None, deco
 
 
 def device_scores(encoder, data_loader, device, char2idx, decoder=None, decoding_step=None, beam_width=10,
-                  max_label_len=100, ctc_weight=0.0, pre_beam=None, units=('char', 'word'), align=False, lm=None):
-  """greedy_cer / ctc_cer / attention_cer's evaluation with the scoring on the device: the dict of
+                  max_label_len=100, ctc_weight=0.0, pre_beam=None, units=('char', 'word'), align=False, lm=None,
+                  rescore_nbest=0, length_bonus=0.0):
+  """greedy_cer / ctc_cer / attention_cer / rescored_cer's evaluation with the scoring on the device: the dict of
   scoring.EditScorer.result() — cer, wer, distance, ref_len, pairs, ... (hits / sub / ins / dele with align=True).
 
   decoder=None, decoding_step=None: the CTC head's greedy path (greedy_cer).  decoder = a BeamCTCDecoder over
   ctc_labels(char2idx): its best hypothesis (ctc_cer).  decoding_step: the attention decoder's beam search
   (attention_cer; beam_width, max_label_len, and ctc_weight > 0 with pre_beam for the joint search; `lm`, a
-  lm.WordLM, adds the word language model to that search).
+  lm.WordLM, adds the word language model to that search).  rescore_nbest > 0 with BOTH `decoder` (a BeamCTCDecoder)
+  and `decoding_step`: two-pass decoding (rescored_cer) — the decoder's rescore_nbest best hypotheses
+  rescored by the attention decoder at `ctc_weight` and `length_bonus`.
 
   Per batch nothing is read back.  A recurrence time-out is handled as in the host loops, but without their per-batch
   read: the device-side fault word gates the batch out of the totals (lr_edit_distance's `gate`), a device vector
   records which batches were gated, and after the last batch one read covers the totals and that vector; only if some
   batch was gated is the loader walked again and just those batches re-encoded with recurrence='f32' and scored."""
   return _device_score_run(encoder, data_loader, device, char2idx, decoder, decoding_step, beam_width, max_label_len,
-                           ctc_weight, pre_beam, units, align, lm)[0]
+                           ctc_weight, pre_beam, units, align, lm, rescore_nbest, length_bonus)[0]
 
 
 def device_cer(encoder, data_loader, device, char2idx, decoder=None, decoding_step=None, beam_width=10,
-               max_label_len=100, ctc_weight=0.0, pre_beam=None, lm=None):
-  """The same float as greedy_cer (no decoder), ctc_cer (`decoder`) or attention_cer (`decoding_step`): sum of
+               max_label_len=100, ctc_weight=0.0, pre_beam=None, lm=None, rescore_nbest=0, length_bonus=0.0):
+  """The same float as greedy_cer (no decoder), ctc_cer (`decoder`), attention_cer (`decoding_step`) or rescored_cer
+  (both, with rescore_nbest): sum of
   space-free edit distances / sum of space-free reference lengths, scored on the device (device_scores)."""
   return device_scores(encoder, data_loader, device, char2idx, decoder, decoding_step, beam_width, max_label_len,
-                       ctc_weight, pre_beam, units=('char',), lm=lm)["cer"]
+                       ctc_weight, pre_beam, units=('char',), lm=lm, rescore_nbest=rescore_nbest,
+                       length_bonus=length_bonus)["cer"]
 
 
 # ---- forced alignment over a loader (lipreading_amd/align.py, DESIGN.md §19) -----------------------------------------
