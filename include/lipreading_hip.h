@@ -1573,6 +1573,83 @@ int lr_ctc_nbest_risk_grad(const float* log_probs, int64_t stride_b, int64_t str
                            const float* grad_weight, const float* grad_scale, float* grad, void* workspace,
                            size_t workspace_bytes, int B, int T, int C, int N, int max_hyp_len, lr_stream_t stream);
 
+/* ---- A6i (BUILD-DEFINED, no reference symbol): the transducer head — RNN-T loss and greedy decoding ------------- */
+/* The reference has no transducer; the specification is this build's (lipreading_amd/csrc/lr_transducer.hip,
+ * lipreading_amd/transducer.py), the yardstick a float64 torch restatement kept with the tests
+ * (tests/transducer_cases.py).  V1 classes in the CTC head's layout (class 0 the blank), a joint width J, per sample b
+ * T_b = frame_lens[b] frames and U_b = label_lens[b] labels y_1 .. y_U_b:
+ *   z(t,u)      = tanh(e[b][t][:] + p[b][u][:])                           t < T_b, 0 <= u <= U_b
+ *   logits(t,u) = joint_w . z(t,u) + joint_b, classes with class_mask[c] == 0 at -inf;  lp(t,u) = log_softmax over V1
+ *   alpha(0,0) = 0;  alpha(t,u) = logaddexp(alpha(t-1,u) + lp(t-1,u)[0], alpha(t,u-1) + lp(t,u-1)[y_u])
+ *   nll[b] = -(alpha(T_b-1,U_b) + lp(T_b-1,U_b)[0]);  every sample with T_b >= 1 is feasible
+ *   sample_status[b]  0;  LR_RNNT_BAD_LENGTH: T_b < 1, T_b > T, U_b < 0 or U_b > U;  LR_RNNT_BAD_ID: a label inside the
+ *                     length that is <= 0, >= V1 or masked.  Such a sample reads nothing out of bounds, has nll 0 and
+ *                     contributes nothing to the loss or to any gradient.
+ *   N = number of samples with status 0;  loss = sum nll / max(N, 1) (LR_CTC_MEAN) or sum nll (LR_CTC_SUM);
+ *   out_status[0] = 1 when N == 0 (lr_ctc_reduce's "skip this batch" word).
+ * The gradients are those of g * loss, g = grad_scale[0] (a DEVICE scalar, NULL = 1): per node the gradient at the
+ * logits is w g (occ(t,u) softmax - occ_blank(t,u) [c == 0] - occ_label(t,u) [c == y_{u+1}]) with the occupancies
+ * exp(alpha + lp + beta - log Z), w = 1 / N or 1.
+ * Arguments:
+ *   e           element (b,t,j) at e[b*e_stride_b + t*e_stride_t + j] (the transposed view of a (T,B,J) tensor goes in
+ *               as it is);  p [B][U+1][J] contiguous;  joint_w [V1][J], joint_b [V1], class_mask [V1] fp32
+ *   labels      int32, sample b's row at labels + b*label_stride; ids past U_b are never read (NULL with U == 0)
+ *   d_e [B][T][J], d_p [B][U+1][J] contiguous, EVERY element written;  d_joint_w [V1][J], d_joint_b [V1] written, or
+ *               added onto with accumulate != 0 (as lr_tfm_backward_weights)
+ * The forward writes three floats per node (log p(blank), log p(next label), the row's log-sum-exp) and alpha; no
+ * (B,T,U+1,V1) or (B,T,U+1,J) tensor exists.  The backward recomputes z and the logits tile by tile (32 nodes of one
+ * frame).  Products are v_mfma_f32_32x32x2_f32 (fp32 operands and accumulation); alpha, beta and log Z are fp64 in log space
+ * (fp32 occupancies exp(alpha + lp + beta - log Z) lose 1e-4 of a gradient at U = 256: three numbers near 700 cancel).  Sums
+ * over u (d_e), over t (d_p) and over nodes (the weights) go through per-workgroup slabs in the workspace and a
+ * fixed-order combine; nothing is accumulated with atomics: two runs on the same inputs give the same bits.
+ * Limits, from the arguments alone (else LR_ERR_UNSUPPORTED, workspace query 0): T <= LR_RNNT_MAX_T,
+ * U <= LR_RNNT_MAX_U, V1 <= LR_RNNT_MAX_CLASSES, J <= LR_RNNT_MAX_JOINT, B <= 65535.  NULLs, B or T < 1, U < 0,
+ * V1 < 2, negative strides, a misaligned (16 bytes) workspace answer LR_ERR_INVALID_ARG, a small one LR_ERR_WORKSPACE,
+ * before any launch. */
+#define LR_RNNT_MAX_T 4096
+#define LR_RNNT_MAX_U 256
+#define LR_RNNT_MAX_CLASSES 256
+#define LR_RNNT_MAX_JOINT 512
+#define LR_RNNT_BAD_ID (-1)
+#define LR_RNNT_BAD_LENGTH (-2)
+
+/* Workspace of the two loss entries (the backward takes the forward's, unmodified); 0 for arguments it rejects. */
+size_t lr_rnnt_workspace_bytes(int B, int T, int U, int V1, int J);
+
+/* Four launches: weight operand + statuses; the joint stage, one tile per workgroup; alpha over anti-diagonals, one
+ * workgroup per sample; the batch reduction. */
+int lr_rnnt_loss_forward(const float* e, int64_t e_stride_b, int64_t e_stride_t, const float* p, const float* joint_w,
+                         const float* joint_b, const float* class_mask, const int32_t* labels, int64_t label_stride,
+                         const int32_t* frame_lens, const int32_t* label_lens, int reduction, float* nll,
+                         int32_t* sample_status, float* out_loss, int32_t* out_status, void* workspace,
+                         size_t workspace_bytes, int B, int T, int U, int V1, int J, lr_stream_t stream);
+
+/* Three launches: beta; the tiles' gradients into slabs; the combine.  nll and sample_status are the forward's. */
+int lr_rnnt_loss_backward(const float* e, int64_t e_stride_b, int64_t e_stride_t, const float* p, const float* joint_w,
+                          const float* joint_b, const float* class_mask, const int32_t* labels, int64_t label_stride,
+                          const int32_t* frame_lens, const int32_t* label_lens, const float* nll,
+                          const int32_t* sample_status, const float* grad_scale, float* d_e, float* d_p,
+                          float* d_joint_w, float* d_joint_b, int accumulate, void* workspace, size_t workspace_bytes,
+                          int B, int T, int U, int V1, int J, lr_stream_t stream);
+
+/* Greedy decoding, one launch, one workgroup per sample.  For each frame t < sizes[b] (clamped into [0, T]; NULL = T):
+ * the argmax of the masked logits of tanh(e_t + tables[0][c0] + tables[1][c1]) (ties to the lowest class), c0 the last
+ * emitted class and c1 the one before it (0 at the start; `context` 1 or 2 tables [context][V1][J], the prediction
+ * network's bias folded into table 0).  The blank ends the frame; another class is emitted, shifted into the context,
+ * and the frame is evaluated again, at most max_symbols times: a frame that emits max_symbols symbols is ended and
+ * counted in forced[b].  Symbol n of sample b goes to ids / frames / logp [b][n] for n < max_out; out_lens[b] counts
+ * every symbol, written or not.  logp is the symbol's log-probability under the masked softmax.
+ * state (may be NULL) [B][context] int32 = (c0, c1), read and written: with it out_lens and forced are read and
+ * continued, and frame_base[b] (NULL = 0) is added to the reported frames, so a clip fed in pieces at any frame
+ * boundaries gives the bits of the one-shot call.  Without it the decode starts from zeros.  At most
+ * sizes[b] * max_symbols evaluations per sample.  Limits as above; context outside {1, 2}, max_symbols or max_out < 1
+ * are LR_ERR_INVALID_ARG. */
+int lr_rnnt_greedy_decode(const float* e, int64_t e_stride_b, int64_t e_stride_t, const int32_t* sizes,
+                          const float* tables, const float* joint_w, const float* joint_b, const float* class_mask,
+                          int32_t* state, const int32_t* frame_base, int32_t* ids, int32_t* frames, float* logp,
+                          int32_t* out_lens, int32_t* forced, int B, int T, int V1, int J, int context, int max_symbols,
+                          int max_out, lr_stream_t stream);
+
 /* ---- A8 (BUILD-DEFINED, no reference symbol): 3-D conv frontend on bf16 MFMA -------------- */
 /* The reference has no conv frontend (src/models/lipreader/model.py:122,153-156 are comments, the
  * `ced` configs are empty); BASELINE.json's north_star asks for one ("im2col + MFMA GEMM for the 3D

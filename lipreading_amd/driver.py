@@ -136,6 +136,15 @@ DEFAULTS = dict(  # train.py:134-167
     # reference transcript as one more hypothesis where no beam is exact.  Needs --ctc_decoder=beam and a CTC-only
     # regime; the search is the evaluation's own (beam width, language model, hotwords).
     mwer=0, mwer_ctc_weight=0.01, mwer_unit="char", mwer_reference=False,
+    # --transducer=True: a transducer head (transducer.TransducerHead) beside the CTC head of the
+    # encoder+CTC loop, for every --frontend / --encoder combination: trained on the RNN-T loss plus
+    # --transducer_ctc_weight times the CTC loss (train.train_transducer); the validation and test errors are the CER of
+    # its greedy transcripts (at most --transducer_max_symbols characters per frame), and best_transducer.pth is kept
+    # beside best_encoder.pth.  --transducer_joint: the joint width, --transducer_embed: the label embedding's,
+    # --transducer_context=1|2: how many previous characters the prediction network sees.  Needs --enable_ctc=True
+    # --ctc_only=True; not together with --mwer, the --stream_* flags or another --attn_decode than the default
+    transducer=False, transducer_joint=256, transducer_embed=64, transducer_context=2, transducer_ctc_weight=0.3,
+    transducer_max_symbols=5,
 )
 
 
@@ -251,6 +260,7 @@ def parse_flags(argv, defaults=DEFAULTS):
   spot_check(out)
   segment_check(out)
   mwer_check(out)
+  transducer_check(out)
   return out
 
 
@@ -371,6 +381,37 @@ def mwer_check(f):
                         f.get("beam_width")))
   if not float(f.get("mwer_ctc_weight", 0.01)) >= 0.0:
     raise ValueError("--mwer_ctc_weight must be >= 0 (got %r)" % (f["mwer_ctc_weight"],))
+
+
+def transducer_check(f):
+  """ValueError for --transducer outside the encoder+CTC loop, together with a flag whose evaluation or training it
+  would replace, or with sizes the kernels do not take."""
+  if not f.get("transducer"):
+    return
+  if not (f.get("ctc_only") and f.get("enable_ctc")):
+    raise ValueError("--transducer=True trains beside the encoder+CTC loop: it needs --ctc_only=True --enable_ctc=True")
+  if f.get("mwer"):
+    raise ValueError("--transducer=True and --mwer=%d both replace the training objective: choose one" % f["mwer"])
+  streaming = [n for n in ("stream_chunk", "stream_encoder", "stream_frontend", "stream_tfm") if f.get(n)]
+  if int(f.get("stream_lookahead", -1)) >= 0:
+    streaming.append("stream_lookahead")
+  if streaming:
+    raise ValueError("--transducer=True is evaluated one-shot by its greedy decoder: not together with --%s (a live "
+                     "session over the decoder's state is not built)" % streaming[0])
+  if f.get("attn_decode", "teacher") != "teacher":
+    raise ValueError("--transducer=True has no attention decoder behind it: --attn_decode=%s does not apply"
+                     % f["attn_decode"])
+  if f.get("score", "host") != "host":
+    raise ValueError("--transducer=True is scored by the host CER loop: --score=%s does not apply" % f["score"])
+  if int(f.get("transducer_context", 2)) not in (1, 2):
+    raise ValueError("--transducer_context must be 1 or 2 (got %r)" % (f["transducer_context"],))
+  if not 1 <= int(f.get("transducer_joint", 256)) <= 512 or int(f.get("transducer_embed", 64)) < 1:
+    raise ValueError("--transducer_joint must be in [1, 512] and --transducer_embed positive (got %r, %r)"
+                     % (f.get("transducer_joint"), f.get("transducer_embed")))
+  if int(f.get("transducer_max_symbols", 5)) < 1:
+    raise ValueError("--transducer_max_symbols must be at least 1 (got %r)" % (f["transducer_max_symbols"],))
+  if not float(f.get("transducer_ctc_weight", 0.3)) >= 0.0:
+    raise ValueError("--transducer_ctc_weight must be >= 0 (got %r)" % (f["transducer_ctc_weight"],))
 
 
 def spot_check(f):
@@ -712,6 +753,7 @@ def run(**flags):
   spot_check(f)
   segment_check(f)
   mwer_check(f)
+  transducer_check(f)
   stream_frontend_check(f)
   stream_encoder_check(f)
   stream_lookahead_check(f)
@@ -814,6 +856,24 @@ def run(**flags):
     eval_encoder = (ChunkedTransformerPixelLipReader(encoder, f["stream_chunk"]) if pixels
                     else ChunkedTransformerEncoder(encoder, f["stream_chunk"]))
   error_of = make_error_of(f, eval_encoder, decoding_step, chunked or ctc_decoder, device, char2idx)
+  head, head_path = None, os.path.join(weights_dir, "best_transducer.pth")
+  if f["transducer"]:
+    from .transducer import TransducerHead
+    inner = getattr(encoder, "encoder", encoder)   # (PixelLipReader wraps the sequence encoder)
+    enc_dim = inner.d_model if hasattr(inner, "d_model") else inner.num_dirs * inner.hidden_size
+    head = TransducerHead(enc_dim, len(char2idx), char2idx, joint_dim=f["transducer_joint"],
+                          embed_dim=f["transducer_embed"], context=f["transducer_context"]).to(device)
+    flats = flats + (FlatParameters(head),)
+    # an edit-distance CER of free-running transcripts can exceed 1 (insertions): the first epoch's pair is kept whatever
+    # it scores, and replaced only by a better one
+    encoder.best_error = head.best_error = float("inf")
+    print("Transducer head: joint width %d, label embedding %d, %d characters of context, CTC weight %g"
+          % (f["transducer_joint"], f["transducer_embed"], f["transducer_context"], f["transducer_ctc_weight"]))
+
+    def error_of(loader):
+      """The CER of the transducer's greedy transcripts."""
+      return T.transducer_cer(encoder, head, loader, device, char2idx, max_symbols=f["transducer_max_symbols"])
+    error_of.last_scores = None
 
   def validation_error():
     """error_of(val_loader); with --stream_chunk also the pass's commit delay, printed and returned."""
@@ -875,6 +935,8 @@ def run(**flags):
         restore(encoder, encoder_path)
         if not ctc_only:
           restore(decoding_step, decoder_path)
+        if head is not None and os.path.isfile(head_path):
+          restore(head, head_path)
       best_idx = epochs
     tfr = max(f["min_tfr"], f["max_tfr"] - epochs / f["tr_epochs"])
     assert 0.0 <= tfr <= 1.0
@@ -887,6 +949,11 @@ def run(**flags):
                                              grad_norm=f["grad_norm"], ctc_weight=f["mwer_ctc_weight"])
       dec_loss = 0.0
       print(f'\tAVG Expected Risk: {expected_risk}')
+    elif head is not None:
+      transducer_loss, ctc_loss = T.train_transducer(encoder, head, train_loader, opt, device, char2idx,
+                                                     grad_norm=f["grad_norm"], ctc_weight=f["transducer_ctc_weight"])
+      dec_loss = 0.0
+      print(f'\tAVG Transducer Loss: {transducer_loss}')
     else:
       dec_loss, ctc_loss = T.train(encoder, decoding_step, train_loader, opt[0] if ctc_only else opt, device, char2idx,
                                    teacher_forcing_ratio=tfr, grad_norm=f["grad_norm"], graphs=graphs)
@@ -897,6 +964,8 @@ def run(**flags):
     clean = augment is None and lmk_augment is None
     train_cer = error_of(train_loader if clean else train_loader.plain())   # on clean clips
     encoder.save_best_model(val_cer, encoder_path)
+    if head is not None:
+      head.save_best_model(val_cer, head_path)
     if not ctc_only:
       decoding_step.save_best_model(val_cer, decoder_path)
     test_cer = error_of(test_loader)
@@ -911,6 +980,9 @@ def run(**flags):
                         skipped_batches=stats.get("skipped", 0), recurrence_faults=stats.get("recurrence_faults", 0)))
     if expected_risk is not None:
       history[-1]["expected_risk"] = expected_risk
+    if head is not None:
+      history[-1]["transducer_loss"] = transducer_loss
+      print(f'\tTransducer CER (val): {val_cer}')
     if val_scores is not None:
       history[-1]["val_wer"] = val_scores["wer"]
       print(f'\tVal WER: {val_scores["wer"]}')
@@ -922,6 +994,12 @@ def run(**flags):
   out = dict(history=history, weights_dir=weights_dir, seconds=time.time() - t0, epochs=epochs,
              graph_captures=graphs.captures, graph_replays=graphs.replays, encoder=encoder,
              decoding_step=decoding_step, char2idx=char2idx, loaders=(train_loader, val_loader, test_loader))
+  if head is not None:
+    out["transducer"] = head
+    if os.path.isfile(head_path) and os.path.isfile(encoder_path):
+      restore(encoder, encoder_path)   # the pair that scored best, as the annealing restores it
+      restore(head, head_path)
+    out["transducer_path"] = head_path
   if commit is not None:
     out["commit_delay"] = commit
   if f["align"]:

@@ -403,6 +403,93 @@ def train_mwer(encoder, data_loader, opt, device, char2idx, mwer, grad_norm=None
   return avg_risk, avg_ctc
 
 
+def transducer_step(encoder, head, opts, frames, frame_lens, chars, char_lens, grad_norm=None, max_len=None,
+                    ctc_weight=0.3, grad_sync=None):
+  """One optimisation step of an encoder and its transducer.TransducerHead:
+  loss = rnnt + ctc_weight * ctc_loss('mean') when the encoder has a CTC head and ctc_weight > 0, else the transducer
+  loss alone.  The labels are the CTC labels (chars[:, 1:] + 1).  opts = (the encoder's FusedAdam, the head's).
+
+  Eager, and without a host read: both Adams are skipped on the device when either loss reports a batch to skip (the
+  OR of the status words) or a recurrence timed out.  Returns (transducer loss, ctc loss or None, status, info):
+  device tensors, `info` the head's dict (nll, sample_status)."""
+  if grad_sync is not None:
+    raise NotImplementedError("data-parallel transducer steps are not built: the step has no exchange for its skip "
+                              "word; run transducer_step in a single process")
+  dev = frames.device
+  frame_lens, chars, char_lens = frame_lens.to(dev), chars.to(dev), char_lens.to(dev)
+  if (chars.dtype == torch.int64 and frame_lens.dtype == torch.int64 and char_lens.dtype == torch.int64
+      and chars.dim() == 2 and chars.stride(1) == 1):
+    labels_p1, frame_lens32, label_lens32 = opts[0].zero_grad_and_prepare_ctc(chars, frame_lens, char_lens)
+  else:
+    opts[0].zero_grad()
+    labels_p1 = (chars[:, 1:] + 1).to(torch.int32).contiguous()
+    frame_lens32, label_lens32 = frame_lens.to(torch.int32), (char_lens - 1).to(torch.int32)
+  opts[1].zero_grad()
+  out = encoder(frames, frame_lens32, max_len=max_len, need_final_state=False)
+  has_ctc = bool(getattr(encoder, "enable_ctc", False))
+  hidden = out[1] if has_ctc else out[0]
+  rnnt, status, info = head.loss(hidden, frame_lens32, labels_p1, label_lens32, 'mean')
+  total, ctc = rnnt, None
+  if has_ctc and ctc_weight > 0:
+    ctc, ctc_status, _ = ctc_loss_prepared(out[0], labels_p1, frame_lens32, label_lens32, 'mean')
+    status = status | ctc_status
+    total = rnnt + ctc_weight * ctc
+  total.backward(_one(dev))
+  _step_all(opts, grad_norm, status)
+  return rnnt.detach(), None if ctc is None else ctc.detach(), status, info
+
+
+def train_transducer(encoder, head, data_loader, opts, device, char2idx, grad_norm=None, ctc_weight=0.3):
+  """An epoch of transducer_step over `data_loader`.  Prints and returns (mean transducer loss, mean CTC loss) over
+  len(data_loader); a skipped batch adds 0 to both, as in train()."""
+  assert all(isinstance(o, FusedAdam) for o in opts) and len(opts) == 2, "opts: the encoder's FusedAdam and the head's"
+  device = torch.device(device)
+  encoder.train()
+  head.train()
+  use_ctc = bool(getattr(encoder, "enable_ctc", False)) and ctc_weight > 0
+  rnnt_sum = torch.zeros((), dtype=torch.float32, device=device)
+  ctc_sum = torch.zeros((), dtype=torch.float32, device=device)
+  skipped_before = opts[0].skipped_steps()
+  watch = RecurrenceWatch(device)
+  for frames, frame_lens, chars, char_lens in data_loader:
+    _check_framing(chars, char_lens, frame_lens, char2idx, use_ctc)
+    max_len = host_max_len(frame_lens)
+    frames, chars = frames.to(device, non_blocking=True), chars.to(device, non_blocking=True)
+    frame_lens_d, char_lens_d = frame_lens.to(device, non_blocking=True), char_lens.to(device, non_blocking=True)
+    rnnt, ctc, status, _ = transducer_step(encoder, head, opts, frames, frame_lens_d, chars, char_lens_d,
+                                           grad_norm=grad_norm, max_len=max_len, ctc_weight=ctc_weight)
+    keep = status.reshape(()) == 0
+    rnnt_sum += torch.where(keep, rnnt, torch.zeros_like(rnnt))
+    if ctc is not None:
+      ctc_sum += torch.where(keep, ctc, torch.zeros_like(ctc))
+    watch.after_step(None)
+  avg_rnnt = (rnnt_sum / len(data_loader)).item()
+  avg_ctc = (ctc_sum / len(data_loader)).item()
+  global last_epoch_stats
+  faults = int(_C.lib().lr_rnn_pair_errors())
+  last_epoch_stats = {"batches": len(data_loader), "skipped": opts[0].skipped_steps() - skipped_before,
+                      "recurrence_faults": faults}
+  if last_epoch_stats["skipped"] or faults:
+    print("\tSkipped batches: %(skipped)d of %(batches)d (recurrence time-outs: %(recurrence_faults)d)"
+          % last_epoch_stats)
+  print(f'\tTraining transducer_loss: {avg_rnnt}')
+  print(f'\tTraining ctc_loss: {avg_ctc}')
+  return avg_rnnt, avg_ctc
+
+
+def transducer_cer(encoder, head, data_loader, device, char2idx, max_symbols=5):
+  """The host CER loop (_host_cer, time-out re-decode included) over the head's greedy transcripts."""
+  head.eval()
+
+  def hypotheses(frames, frame_lens):
+    lens_d = frame_lens.to(device)
+    out = encoder(frames.to(device), lens_d, max_len=host_max_len(frame_lens), need_final_state=False)
+    hidden = out[1] if getattr(encoder, "enable_ctc", False) else out[0]
+    return head.decode_strings(hidden, lens_d, max_symbols=max_symbols)
+
+  return _host_cer(encoder, data_loader, device, char2idx, hypotheses)
+
+
 # test hook / switch: False keeps the CTC branch of a decoder step on the step's own stream
 overlap_ctc_branch = True
 _ctc_side = None
