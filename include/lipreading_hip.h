@@ -1650,6 +1650,64 @@ int lr_rnnt_greedy_decode(const float* e, int64_t e_stride_b, int64_t e_stride_t
                           int32_t* out_lens, int32_t* forced, int B, int T, int V1, int J, int context, int max_symbols,
                           int max_out, lr_stream_t stream);
 
+/* ---- A6j (BUILD-DEFINED, no reference symbol): transducer beam search — N-best lists, resumable ------------------ */
+/* Time-synchronous beam search over A6i's model (lipreading_amd/csrc/lr_transducer_beam.hip; the
+ * yardstick is the torch restatement tests/transducer_beam_cases.py).  Classes, class_mask, tables [context][V1][J]
+ * (prediction bias folded into table 0) and the context (c0 = a prefix's last label, c1 = the one before it, 0 where
+ * there is none) are A6i's.  A hypothesis is (prefix, score, frames): the label string, the log of the summed
+ * probability of every alignment of it that the search has kept, and the frame at which each label was emitted.
+ * A sample's beam starts as the empty prefix with score 0.  For every frame t < sizes[b] (clamped into [0, T]; NULL = T):
+ *   1. A = the beam (at most beam_width hypotheses, in beam order); F = empty, kept in insertion order.
+ *   2. Rounds s = 0 .. max_symbols.  For every h of A, in order,
+ *        lp = masked log_softmax(joint_w . tanh(e_t + tables[0][c0] + tables[1][c1]) + joint_b):
+ *      blank   (h.prefix, h.score + lp[0], h.frames) is offered to F.  If F holds the prefix already the two merge: the
+ *              score becomes logaddexp of the two, the frames are those of the constituent whose own, unmerged score is
+ *              larger (the earlier-inserted one on a tie), the entry keeps its insertion position.
+ *      labels  only while s < max_symbols and len(h.prefix) < max_out: every unmasked class k >= 1 gives the candidate
+ *              (h.prefix + k, h.score + lp[k], h.frames + t) of C, ordered by (rank of h in A, k).  A hypothesis
+ *              already at max_out labels gives none and adds one to truncated[b] for that round.
+ *      Then A = the first beam_width of a stable descending sort of C by score; an empty A ends the frame's rounds.
+ *      Round max_symbols offers blanks only.
+ *   3. The new beam = the first beam_width of a stable descending sort of F by score.
+ * Prefixes are equal when their label strings are, label by label.  Inside a round C holds no prefix twice; the only
+ * merges are F's.  Every frame ends with a blank, so a score is a partial sum of the alignments of A6i's loss: at most
+ * -nll(prefix), and equal to it when nothing was pruned and max_symbols >= len(prefix).
+ * Arithmetic: the joint stage (MFMA operands and accumulation) and the log-softmax are fp32; scores are accumulated,
+ * compared and merged in float64, in the kernel and in the state, and reported as float32.  No atomics: two runs give
+ * the same bits, and a clip fed in pieces at any frame boundaries gives the one-shot call's bits, outputs and state.
+ * state   an opaque device buffer of lr_rnnt_beam_state_bytes(B, beam_width, max_out) bytes (8-byte aligned), owned by
+ *         the caller: a header of 8 int32 {magic, B, beam_width, max_out, context, status, 0, 0}, then every sample's
+ *         beam (float64 scores, count, lengths, labels, frames).  fresh != 0 starts every sample from the empty prefix
+ *         and ignores the contents; fresh == 0 continues.  A state_bytes that is not the size of (B, beam_width,
+ *         max_out) is LR_ERR_INVALID_ARG before any launch; a buffer of the right size whose header names another B,
+ *         beam_width, max_out or context (or none) is refused on the device: word 5 of the header is set to
+ *         LR_RNNT_BEAM_BAD_STATE (0 by every accepted call), the rest of the buffer and `truncated` are left as they
+ *         are, and every sample answers out_count 0 with all scores -inf.  Nothing past state_bytes is read.
+ * outputs the beam's first nbest hypotheses after the call's frames: out_ids, out_frames [B][nbest][max_out] int32 (0
+ *         past the length), out_lens [B][nbest], out_scores [B][nbest] fp32 descending, -inf in empty slots (the empty
+ *         prefix is a hypothesis of length 0: empty slots are told by the score), out_count [B] = hypotheses written,
+ *         truncated [B] (read and continued when fresh == 0).  frame_base[b] (NULL = 0) is added to the frames emitted
+ *         in this call.
+ * Limits, from the arguments alone (LR_ERR_UNSUPPORTED, size queries 0): A6i's on T, V1, J and B; beam_width <=
+ * LR_RNNT_BEAM_MAX_WIDTH, max_symbols <= LR_RNNT_BEAM_MAX_SYMBOLS, max_out <= LR_RNNT_MAX_U.  NULLs, sizes below 1,
+ * context outside {1, 2}, nbest outside [1, beam_width], negative strides, a misaligned state or workspace (16 bytes)
+ * are LR_ERR_INVALID_ARG, a small workspace LR_ERR_WORKSPACE, all before any launch. */
+#define LR_RNNT_BEAM_MAX_WIDTH 32
+#define LR_RNNT_BEAM_MAX_SYMBOLS 8
+#define LR_RNNT_BEAM_BAD_STATE (-3)
+
+size_t lr_rnnt_beam_state_bytes(int B, int beam_width, int max_out);
+/* The zero-padded weight operand and the second buffer of the beams' frames. */
+size_t lr_rnnt_beam_workspace_bytes(int B, int V1, int J, int beam_width, int max_symbols);
+
+/* Two launches: the weight operand; the search, one workgroup per sample with the frame loop inside it. */
+int lr_rnnt_beam_decode(const float* e, int64_t e_stride_b, int64_t e_stride_t, const int32_t* sizes,
+                        const float* tables, const float* joint_w, const float* joint_b, const float* class_mask,
+                        void* state, size_t state_bytes, int fresh, const int32_t* frame_base, int32_t* out_ids,
+                        int32_t* out_frames, int32_t* out_lens, float* out_scores, int32_t* out_count,
+                        int32_t* truncated, void* workspace, size_t workspace_bytes, int B, int T, int V1, int J,
+                        int context, int beam_width, int max_symbols, int nbest, int max_out, lr_stream_t stream);
+
 /* ---- A8 (BUILD-DEFINED, no reference symbol): 3-D conv frontend on bf16 MFMA -------------- */
 /* The reference has no conv frontend (src/models/lipreader/model.py:122,153-156 are comments, the
  * `ced` configs are empty); BASELINE.json's north_star asks for one ("im2col + MFMA GEMM for the 3D

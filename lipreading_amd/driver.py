@@ -142,9 +142,11 @@ DEFAULTS = dict(  # train.py:134-167
     # its greedy transcripts (at most --transducer_max_symbols characters per frame), and best_transducer.pth is kept
     # beside best_encoder.pth.  --transducer_joint: the joint width, --transducer_embed: the label embedding's,
     # --transducer_context=1|2: how many previous characters the prediction network sees.  Needs --enable_ctc=True
-    # --ctc_only=True; not together with --mwer, the --stream_* flags or another --attn_decode than the default
+    # --ctc_only=True; not together with --mwer, the --stream_* flags or another --attn_decode than the default.
+    # --transducer_beam=W (0: greedy): the reported CER is that of the top hypothesis of the transducer beam search of
+    # width W <= 32 (transducer.rnnt_beam; at most --transducer_max_symbols <= 8 label rounds per frame)
     transducer=False, transducer_joint=256, transducer_embed=64, transducer_context=2, transducer_ctc_weight=0.3,
-    transducer_max_symbols=5,
+    transducer_max_symbols=5, transducer_beam=0,
 )
 
 
@@ -386,8 +388,16 @@ def mwer_check(f):
 def transducer_check(f):
   """ValueError for --transducer outside the encoder+CTC loop, together with a flag whose evaluation or training it
   would replace, or with sizes the kernels do not take."""
+  beam = int(f.get("transducer_beam", 0))
+  if beam and not f.get("transducer"):
+    raise ValueError("--transducer_beam=%d searches the transducer head: it needs --transducer=True" % beam)
   if not f.get("transducer"):
     return
+  if not 0 <= beam <= 32:
+    raise ValueError("--transducer_beam must be in [0, 32] (0: greedy; got %d)" % beam)
+  if beam > 0 and int(f.get("transducer_max_symbols", 5)) > 8:
+    raise ValueError("--transducer_beam=%d runs at most 8 label rounds per frame: --transducer_max_symbols=%d is too "
+                     "many" % (beam, int(f["transducer_max_symbols"])))
   if not (f.get("ctc_only") and f.get("enable_ctc")):
     raise ValueError("--transducer=True trains beside the encoder+CTC loop: it needs --ctc_only=True --enable_ctc=True")
   if f.get("mwer"):
@@ -871,8 +881,9 @@ def run(**flags):
           % (f["transducer_joint"], f["transducer_embed"], f["transducer_context"], f["transducer_ctc_weight"]))
 
     def error_of(loader):
-      """The CER of the transducer's greedy transcripts."""
-      return T.transducer_cer(encoder, head, loader, device, char2idx, max_symbols=f["transducer_max_symbols"])
+      """The CER of the transducer's greedy transcripts, or of its beam search's top hypotheses."""
+      return T.transducer_cer(encoder, head, loader, device, char2idx, max_symbols=f["transducer_max_symbols"],
+                              beam_width=f["transducer_beam"])
     error_of.last_scores = None
 
   def validation_error():

@@ -477,15 +477,16 @@ def train_transducer(encoder, head, data_loader, opts, device, char2idx, grad_no
   return avg_rnnt, avg_ctc
 
 
-def transducer_cer(encoder, head, data_loader, device, char2idx, max_symbols=5):
-  """The host CER loop (_host_cer, time-out re-decode included) over the head's greedy transcripts."""
+def transducer_cer(encoder, head, data_loader, device, char2idx, max_symbols=5, beam_width=0):
+  """The host CER loop (_host_cer, time-out re-decode included) over the head's greedy transcripts, or over the top
+  hypotheses of its beam search at a positive beam_width."""
   head.eval()
 
   def hypotheses(frames, frame_lens):
     lens_d = frame_lens.to(device)
     out = encoder(frames.to(device), lens_d, max_len=host_max_len(frame_lens), need_final_state=False)
     hidden = out[1] if getattr(encoder, "enable_ctc", False) else out[0]
-    return head.decode_strings(hidden, lens_d, max_symbols=max_symbols)
+    return head.decode_strings(hidden, lens_d, max_symbols=max_symbols, beam_width=beam_width)
 
   return _host_cer(encoder, data_loader, device, char2idx, hypotheses)
 

@@ -23,6 +23,9 @@ MAX_T = _C.LR_RNNT_MAX_T
 MAX_U = _C.LR_RNNT_MAX_U
 MAX_CLASSES = _C.LR_RNNT_MAX_CLASSES
 MAX_JOINT = _C.LR_RNNT_MAX_JOINT
+BEAM_MAX_WIDTH = _C.LR_RNNT_BEAM_MAX_WIDTH
+BEAM_MAX_SYMBOLS = _C.LR_RNNT_BEAM_MAX_SYMBOLS
+BEAM_BAD_STATE = _C.LR_RNNT_BEAM_BAD_STATE
 BAD_ID = _C.LR_RNNT_BAD_ID
 BAD_LENGTH = _C.LR_RNNT_BAD_LENGTH
 
@@ -186,6 +189,87 @@ def rnnt_greedy(e, sizes, tables, joint_weight, joint_bias, class_mask, state=No
   return out
 
 
+def rnnt_beam(e, sizes, tables, joint_weight, joint_bias, class_mask, beam_width=8, max_symbols=3, nbest=None,
+              state=None, max_out=None):
+  """Time-synchronous transducer beam search in one search launch (lr_rnnt_beam_decode; the specification:
+  include/lipreading_hip.h, A6j).  e, sizes, tables, joint_weight, joint_bias and class_mask as rnnt_greedy takes them.
+  beam_width in [1, 32], max_symbols in [1, 8] label rounds per frame, nbest (default beam_width) hypotheses reported,
+  max_out in [1, 256] the width of ids / frames (default min(T * max_symbols, 256); with a state, the state's).
+  `state`: None for a one-shot search, or the dict an earlier call returned, continued IN PLACE (the beams, `truncated`
+  and the frame base, which moves on by `sizes`): a clip fed in pieces at any frame boundaries gives the one-shot
+  call's bits.  A state made for another batch, width, max_out or context raises ValueError.  Returns dict(ids, frames
+  (B, nbest, max_out) int32, lens (B, nbest), scores (B, nbest) fp32 descending with -inf in empty slots, count (B,),
+  truncated (B,), state) of device tensors; state["status"] is the device's word on the buffer (0, or BEAM_BAD_STATE).
+  No host synchronisation."""
+  _C.require_cuda(e, sizes, tables, joint_weight, joint_bias, class_mask)
+  if e.dim() != 3 or tables.dim() != 3 or tables.shape[0] not in (1, 2) or tables.shape[2] != e.shape[2]:
+    raise ValueError("e must be (B, T, J) and tables (1 or 2, V1, J), got %s and %s"
+                     % (tuple(e.shape), tuple(tables.shape)))
+  B, T, J = e.shape
+  context, V1 = tables.shape[0], tables.shape[1]
+  if tuple(joint_weight.shape) != (V1, J) or tuple(joint_bias.shape) != (V1,) or tuple(class_mask.shape) != (V1,):
+    raise ValueError("joint_weight must be (%d, %d), joint_bias and class_mask (%d,)" % (V1, J, V1))
+  beam_width, max_symbols = int(beam_width), int(max_symbols)
+  if not 1 <= beam_width <= BEAM_MAX_WIDTH:
+    raise ValueError("beam_width must be in [1, %d], got %d" % (BEAM_MAX_WIDTH, beam_width))
+  if not 1 <= max_symbols <= BEAM_MAX_SYMBOLS:
+    raise ValueError("max_symbols must be in [1, %d], got %d" % (BEAM_MAX_SYMBOLS, max_symbols))
+  nbest = beam_width if nbest is None else int(nbest)
+  if not 1 <= nbest <= beam_width:
+    raise ValueError("nbest must be in [1, beam_width = %d], got %d" % (beam_width, nbest))
+  if not (1 <= B <= 65535 and 1 <= T <= MAX_T and 2 <= V1 <= MAX_CLASSES and 1 <= J <= MAX_JOINT):
+    raise ValueError("lr_rnnt_beam_decode: unsupported shape B=%d T=%d V1=%d J=%d (at most 65535, %d, %d, %d)"
+                     % (B, T, V1, J, MAX_T, MAX_CLASSES, MAX_JOINT))
+  if state is None:
+    width = int(max_out) if max_out is not None else min(T * max_symbols, MAX_U)
+  else:
+    width = state["max_out"]
+    if max_out is not None and int(max_out) != width:
+      raise ValueError("the state holds hypotheses of at most %d labels, the call asks for %d" % (width, int(max_out)))
+  if not 1 <= width <= MAX_U:
+    raise ValueError("max_out must be in [1, %d], got %d" % (MAX_U, width))
+  L = _C.lib()
+  dev = e.device
+  if state is None:
+    nbytes = L.lr_rnnt_beam_state_bytes(B, beam_width, width)
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    st = dict(buffer=buf, status=buf[:32].view(torch.int32)[5], B=B, beam_width=beam_width, max_out=width,
+              context=context, truncated=torch.zeros(B, dtype=torch.int32, device=dev),
+              frame_base=torch.zeros(B, dtype=torch.int32, device=dev))
+    fresh = 1
+  else:
+    st = state
+    if (st["B"], st["beam_width"], st["max_out"], st["context"]) != (B, beam_width, width, context):
+      raise ValueError("the state is of (B, beam_width, max_out, context) = %s, the call of %s"
+                       % ((st["B"], st["beam_width"], st["max_out"], st["context"]), (B, beam_width, width, context)))
+    _C.require_cuda(st["buffer"])
+    if st["buffer"].numel() != L.lr_rnnt_beam_state_bytes(B, beam_width, width):
+      raise ValueError("the state's buffer holds %d bytes, a state of this geometry %d"
+                       % (st["buffer"].numel(), L.lr_rnnt_beam_state_bytes(B, beam_width, width)))
+    fresh = 0
+  if e.dtype != torch.float32:
+    e = e.float()
+  if e.stride(2) != 1 or e.stride(0) < 0 or e.stride(1) < 0:
+    e = e.contiguous()
+  sz = _host.int32_vector(sizes, B, "sizes", device=dev)
+  f32 = lambda t: (t if t.dtype == torch.float32 else t.float()).contiguous()
+  ws_bytes = L.lr_rnnt_beam_workspace_bytes(B, V1, J, beam_width, max_symbols)
+  ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+  out = dict(ids=torch.empty((B, nbest, width), dtype=torch.int32, device=dev),
+             frames=torch.empty((B, nbest, width), dtype=torch.int32, device=dev),
+             lens=torch.empty((B, nbest), dtype=torch.int32, device=dev),
+             scores=torch.empty((B, nbest), dtype=torch.float32, device=dev),
+             count=torch.empty(B, dtype=torch.int32, device=dev), truncated=st["truncated"], state=st)
+  _host.launch(dev, "lr_rnnt_beam_decode", L.lr_rnnt_beam_decode, e.data_ptr(), e.stride(0), e.stride(1), _C.ptr(sz),
+               f32(tables).data_ptr(), f32(joint_weight).data_ptr(), f32(joint_bias).data_ptr(),
+               f32(class_mask).data_ptr(), st["buffer"].data_ptr(), st["buffer"].numel(), fresh,
+               st["frame_base"].data_ptr(), out["ids"].data_ptr(), out["frames"].data_ptr(), out["lens"].data_ptr(),
+               out["scores"].data_ptr(), out["count"].data_ptr(), st["truncated"].data_ptr(), ws.data_ptr(), ws_bytes,
+               B, T, V1, J, context, beam_width, max_symbols, nbest, width)
+  st["frame_base"] += (sz.clamp(0, T) if sz is not None else T)
+  return out
+
+
 class TransducerHead(nn.Module):
   """enc_proj, embed, pred_proj and joint of the transducer over `enc_dim`-wide encoder states (any encoder family:
   the head takes nothing but `hidden`).  vocab_size and char2idx as VideoEncoder takes them."""
@@ -246,12 +330,25 @@ class TransducerHead(nn.Module):
       return rnnt_greedy(self.enc_proj(hidden), sizes, self.tables(), self.joint.weight, self.joint.bias,
                          self.output_mask, state=state, max_symbols=max_symbols)
 
-  def decode_strings(self, hidden, sizes, max_symbols=5):
-    """The greedy transcripts as strings (EOS removed), after the one host read, as GreedyDecoder's."""
+  def beam(self, hidden, sizes, beam_width=8, max_symbols=3, nbest=None, state=None):
+    """dict(ids, frames, lens, scores, count, truncated, state), all device tensors, of rnnt_beam: the N-best list of
+    `hidden` (B, T, enc_dim), or of the clip so far when `state` is an earlier call's."""
+    _C.require_cuda(hidden, sizes)
+    with torch.no_grad():
+      return rnnt_beam(self.enc_proj(hidden), sizes, self.tables(), self.joint.weight, self.joint.bias,
+                       self.output_mask, beam_width=beam_width, max_symbols=max_symbols, nbest=nbest, state=state)
+
+  def decode_strings(self, hidden, sizes, max_symbols=5, beam_width=0):
+    """The transcripts as strings (EOS removed), after the one host read, as GreedyDecoder's: the greedy ones at
+    beam_width 0, the beam search's top hypothesis at a positive beam_width."""
     from .decoder import ctc_labels
     labels = ctc_labels(self.char2idx)
-    out = self.greedy(hidden, sizes, max_symbols=max_symbols)
-    ids, lens = out["ids"].cpu(), out["lens"].cpu()
+    if beam_width > 0:
+      out = self.beam(hidden, sizes, beam_width=beam_width, max_symbols=max_symbols, nbest=1)
+      ids, lens = out["ids"][:, 0].cpu(), out["lens"][:, 0].cpu()
+    else:
+      out = self.greedy(hidden, sizes, max_symbols=max_symbols)
+      ids, lens = out["ids"].cpu(), out["lens"].cpu()
     width = ids.shape[1]
     return [''.join(labels[int(c)] for c in ids[b, :min(int(lens[b]), width)]).replace(EOS, '')
             for b in range(ids.shape[0])]
